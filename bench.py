@@ -15,6 +15,12 @@ all-reduce of the fused [mean | var] buffer (RCCL over xGMI).
     python bench.py --config 4 --gpus N [--n 8192]   # BASELINE configs[3]: the sharded 2-D hierarchy (run_config)
     python bench.py --nccl-world1                    # the N = 1 step with backend nccl (RCCL) initialised and the
                                                      # fused buffer reduced unconditionally (one-GPU RCCL evidence)
+    python bench.py --full ...                       # + roofline, stage times, Cholesky alone, reduce self-check,
+                                                     # drained steps, CPU baseline and full-size parity with the oracle
+    python bench.py --dump-outputs DIR ...           # the last timed step's outputs as DIR/<name>.npy
+
+A plain run (no --full) sets up, warms up, times the steps, writes the outputs when asked and prints the
+headline line; everything else it can measure or check runs only under --full.
 """
 import argparse
 import ctypes
@@ -244,6 +250,8 @@ def run_config(args, world, rank, rehearsal):
             om, _ = oracle.mrgp_fit(xn, y, oracle.index_bounds_uniform(n, res, 2, power), specs)
             omean, ovar = oracle.mrgp_predict(xn, om, specs, (xs - mu) / sd, oracle.index_bounds_uniform(ns, res, 2, power))
             out.update(parity_fields(mean, var, omean, ovar))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, mean=mean, var=var)
         print(json.dumps(out))
         if out.get("parity_ok") is False:
             raise SystemExit("bench.py --config %d: the GPU result differs from the oracle by more than 1e-5" % args.config)
@@ -265,6 +273,15 @@ def parity_fields(mean, var, omean, ovar):
     rec["parity_ok"] = bool(rec["parity_rel_err_mean"] <= 1e-5 and rec["parity_rel_err_var"] <= 1e-5
                             and rec["parity_rel_err_var_elementwise"] <= 1e-5)
     return rec
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy in its compute precision (float64 or float32), so that two builds
+    can be compared output for output on the same seeded inputs."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64))
 
 
 def main():
@@ -298,6 +315,12 @@ def main():
                          "brings a stream of its own, a fifth queue for a runtime that serves four: round-4 record)")
     ap.add_argument("--rows-queues", type=int, default=0, choices=[0, 1, 2],
                     help="queues for the carried rows (cimrgp_set_rows_queues); 0 = the default policy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the trailing-update roofline (events in the "
+                         "timed steps), stage times, Cholesky alone, the reduce self-check, drained steps, the CPU baseline and "
+                         "full-size parity with the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     if args.config in (3, 4) and "--n" not in " ".join(sys.argv):
         args.n = None
@@ -512,111 +535,92 @@ def main():
     barrier()
     assert all(int(b["info"].item()) == 0 for b in sets), "Cholesky failed in warm-up"
 
-    # The roofline's live timing: HIP events around the trailing-update launches, on their own stream, in every
+    # The roofline's live timing (--full): HIP events around the trailing-update launches, on their own stream, in every
     # EVENT_EVERY-th timed step (two event records per launch on the update queue cost ~1 % of a step when every
     # step carries them: 120.6 against 121.3-122.3 posteriors/s without any).
+    events = args.full and not args.no_launch_events
     t0 = time.perf_counter()
     for i in range(args.steps):
-        if not args.no_launch_events and i % EVENT_EVERY == 0:
+        if events and i % EVENT_EVERY == 0:
             _lib.check(lib.cimrgp_profile_begin(), "cimrgp_profile_begin")
         step()
-        if i % EVENT_EVERY == 0:
+        if args.full and i % EVENT_EVERY == 0:
             _lib.check(lib.cimrgp_profile_pause(), "cimrgp_profile_pause")
         # stage times are read after the loop from the last step's events only
     drain()                                       # the last step's collective completes inside the timed region
     barrier()
     dt = time.perf_counter() - t0
-    tr_ms, tr_fl, tr_by, tr_cnt = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
-    _lib.check(lib.cimrgp_profile_collect_bytes(ctypes.byref(tr_ms), ctypes.byref(tr_fl), ctypes.byref(tr_by), ctypes.byref(tr_cnt)),
-               "cimrgp_profile_collect_bytes")
-    last_mean = sets[last_set[0]]["mean"].double().cpu().numpy()     # the last timed step's outputs (this rank)
-    last_var = sets[last_set[0]]["var"].double().cpu().numpy()
-    # the collective of the timed steps is started at the end of a step and waited for (by the stream) at the start
-    # of the next: its latency is hidden.  What it costs when it is NOT hidden: steps that wait for it inside.
-    drained_ms = None
-    if world > 1 or args.nccl_world1:
-        barrier()
-        t1 = time.perf_counter()
-        for _ in range(5):
-            step(wait_inside=True)
-        barrier()
-        drained_ms = (time.perf_counter() - t1) / 5 * 1e3
-    # the reduced buffer holds this rank's slice unchanged (the other ranks contribute zeros there): exact
-    step()
-    lb = sets[last_set[0]]
-    with torch.cuda.stream(streams[2] if pipeline else torch.cuda.current_stream()):
-        mine = torch.cat([lb["mean"].reshape(-1), lb["var"]]).clone()
-    drain()
-    torch.cuda.synchronize()
-    reduce_diff = float((torch.cat([lb["mean"].reshape(-1), lb["var"]]) - mine).abs().max().item())
-    # stage times: the five-call form, outside the timed region (median of 3 after a warm-up)
-    stage_runs = []
-    for rep in range(4):
-        step_in_stages()
-        torch.cuda.synchronize()
-        if rep:
-            stage_runs.append([ev[i].elapsed_time(ev[i + 1]) for i in range(4)])
-    stage_ms = np.median(np.asarray(stage_runs), axis=0)
-    # Cholesky alone (no carried rows) for the effective-GFLOP/s figure, timed separately
-    torch.cuda.synchronize()
-    chol_ms = []
-    _lib.check(lib.cimrgp_profile_begin(), "cimrgp_profile_begin")     # the same kernel without carried rows beside it
-    for rep in range(7):                          # 2 warm-ups (the host reads above let the clocks drop), median of 5
-        dev.rbf_gram(xd, ell, sf2, noise, lower_only=True, out=kbuf)
-        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        c0.record()
-        dev.potrf(kbuf, n, ws, info)
-        c1.record()
-        torch.cuda.synchronize()
-        if rep >= 2:
-            chol_ms.append(c0.elapsed_time(c1))
-    chol_ms = float(np.median(chol_ms))
-    al_ms, al_fl, al_by, al_cnt = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
-    _lib.check(lib.cimrgp_profile_collect_bytes(ctypes.byref(al_ms), ctypes.byref(al_fl), ctypes.byref(al_by), ctypes.byref(al_cnt)),
-               "cimrgp_profile_collect_bytes")
+    assert all(int(b["info"].item()) == 0 for b in sets), "Cholesky failed in a timed step"
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives: the reduced fused [mean | var] buffer (every rank's slice) and alpha = K^-1 r
+        lb = sets[last_set[0]]
+        dump_outputs(args.dump_outputs, mean=lb["fused"][:nst * q].view(nst, q), var=lb["fused"][nst * q:], alpha=lb["alpha"])
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if cabi else device)
         td.all_reduce(t, op=td.ReduceOp.MAX)
         dt = float(t.item())
-    assert int(info.item()) == 0
 
-    if rank == 0:
+    def measure_full():
+        """--full: what the headline does not need, measured after the timed region (collective: every rank runs it);
+        returns the result line's extra fields (rank 0)."""
+        tr_ms, tr_fl, tr_by, tr_cnt = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
+        _lib.check(lib.cimrgp_profile_collect_bytes(ctypes.byref(tr_ms), ctypes.byref(tr_fl), ctypes.byref(tr_by), ctypes.byref(tr_cnt)),
+                   "cimrgp_profile_collect_bytes")
+        last_mean = sets[last_set[0]]["mean"].double().cpu().numpy()     # the last timed step's outputs (this rank)
+        last_var = sets[last_set[0]]["var"].double().cpu().numpy()
+        # the collective of the timed steps is started at the end of a step and waited for (by the stream) at the start
+        # of the next: its latency is hidden.  What it costs when it is NOT hidden: steps that wait for it inside.
+        drained_ms = None
+        if world > 1 or args.nccl_world1:
+            barrier()
+            t1 = time.perf_counter()
+            for _ in range(5):
+                step(wait_inside=True)
+            barrier()
+            drained_ms = (time.perf_counter() - t1) / 5 * 1e3
+        # the reduced buffer holds this rank's slice unchanged (the other ranks contribute zeros there): exact
+        step()
+        lb = sets[last_set[0]]
+        with torch.cuda.stream(streams[2] if pipeline else torch.cuda.current_stream()):
+            mine = torch.cat([lb["mean"].reshape(-1), lb["var"]]).clone()
+        drain()
+        torch.cuda.synchronize()
+        reduce_diff = float((torch.cat([lb["mean"].reshape(-1), lb["var"]]) - mine).abs().max().item())
+        # stage times: the five-call form, outside the timed region (median of 3 after a warm-up)
+        stage_runs = []
+        for rep in range(4):
+            step_in_stages()
+            torch.cuda.synchronize()
+            if rep:
+                stage_runs.append([ev[i].elapsed_time(ev[i + 1]) for i in range(4)])
+        stage_ms = np.median(np.asarray(stage_runs), axis=0)
+        # Cholesky alone (no carried rows) for the effective-GFLOP/s figure, timed separately
+        torch.cuda.synchronize()
+        chol_ms = []
+        _lib.check(lib.cimrgp_profile_begin(), "cimrgp_profile_begin")     # the same kernel without carried rows beside it
+        for rep in range(7):                          # 2 warm-ups (the host reads above let the clocks drop), median of 5
+            dev.rbf_gram(xd, ell, sf2, noise, lower_only=True, out=kbuf)
+            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            c0.record()
+            dev.potrf(kbuf, n, ws, info)
+            c1.record()
+            torch.cuda.synchronize()
+            if rep >= 2:
+                chol_ms.append(c0.elapsed_time(c1))
+        chol_ms = float(np.median(chol_ms))
+        al_ms, al_fl, al_by, al_cnt = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
+        _lib.check(lib.cimrgp_profile_collect_bytes(ctypes.byref(al_ms), ctypes.byref(al_fl), ctypes.byref(al_by), ctypes.byref(al_cnt)),
+                   "cimrgp_profile_collect_bytes")
+        assert int(info.item()) == 0
+        if rank != 0:
+            return {}
         peak = FP64_MFMA_PEAK_TFLOPS if args.dtype == "f64" else FP32_MFMA_PEAK_TFLOPS
         achieved = (tr_fl.value / (tr_ms.value * 1e-3)) / 1e12 if tr_ms.value > 0 else 0.0
         chol_gflops = (n ** 3 / 3.0) / (chol_ms * 1e-3) / 1e9
         out = {
-            "metric": "GP posteriors/sec at N=%d (Gram + Cholesky + solve + predictive mean/var)" % n,
-            "value": world * args.steps / dt,
-            "unit": "posteriors/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: 1-D, N=%d single-resolution single-partition RBF GP "
-                                   "per GPU, q=2 outputs, N/4=%d test points, ell=0.1, sf2=1, noise=0.01" % (n, ns),
-                       "partitions_per_gpu": 1,
-                       "parallelism": "independent partitions, 1 all-reduce/step (started at the end of a step, waited for by the stream at the start of the next)",
-                       "backend": ((rehearsal or ("rccl through the C ABI (cimrgp_allreduce_sum on the step's solve queue); control plane gloo"
-                                                   if comm is not None else ("nccl (fallback: the C-ABI communicator could not be created)"
-                                                                             if fallback_group is not None else "nccl"))) if td.is_initialized() else "none"),
-                       "rows_queues": int(lib.cimrgp_get_rows_queues()),
-                       "front_queue": bool(pipeline and args.front_queue)},
             "reduce_selfcheck_max_abs_diff": reduce_diff,
             "cholesky_gflops": chol_gflops,
             "cholesky_frac_of_peak": chol_gflops / 1e3 / peak,
-            "step_is": ("ONE cimrgp_block_posterior_staged call per step on preallocated buffers (+ the collective's enqueue): consecutive steps "
-                        "are independent blocks over two rotating buffer sets; the backward solve and prediction of step i run on the "
-                        "look-ahead context's idle queue (cimrgp_solve_queue) beside the first panels of step i+1, whose Gram matrices run on the "
-                        "context's chain queue (cimrgp_front_queue) beside the last panels of step i; "
-                        "every step completes inside the timed region")
-                       if pipeline else "ONE cimrgp_block_posterior call per step on preallocated buffers (+ the collective's enqueue)",
-            "pipelined_steps": bool(pipeline),
-            "reduce_overlapped": bool(world > 1 or args.nccl_world1),
             "drained_step_ms": drained_ms,
             "stage_ms": {"measured": "the same work as five separate calls on ONE stream, after the timed region (median of 3): a different "
                                      "schedule from the timed, pipelined step -- its stages do not add up to ms_per_step",
@@ -672,6 +676,42 @@ def main():
             # posterior on the same arrays (north_star: 1e-5 relative on mean and variance, max
             # error over max magnitude as in tests/)
             out.update(parity_fields(last_mean, last_var, omean, ovar))
+        return out
+
+    extra = measure_full() if args.full else {}
+    if rank == 0:
+        out = {
+            "metric": "GP posteriors/sec at N=%d (Gram + Cholesky + solve + predictive mean/var)" % n,
+            "value": world * args.steps / dt,
+            "unit": "posteriors/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": args.dtype,
+            "data": "synthetic",
+            "config": {"workload": "BASELINE configs[1]: 1-D, N=%d single-resolution single-partition RBF GP "
+                                   "per GPU, q=2 outputs, N/4=%d test points, ell=0.1, sf2=1, noise=0.01" % (n, ns),
+                       "partitions_per_gpu": 1,
+                       "parallelism": "independent partitions, 1 all-reduce/step (started at the end of a step, waited for by the stream at the start of the next)",
+                       "backend": ((rehearsal or ("rccl through the C ABI (cimrgp_allreduce_sum on the step's solve queue); control plane gloo"
+                                                   if comm is not None else ("nccl (fallback: the C-ABI communicator could not be created)"
+                                                                             if fallback_group is not None else "nccl"))) if td.is_initialized() else "none"),
+                       "rows_queues": int(lib.cimrgp_get_rows_queues()),
+                       "front_queue": bool(pipeline and args.front_queue)},
+            "step_is": ("ONE cimrgp_block_posterior_staged call per step on preallocated buffers (+ the collective's enqueue): consecutive steps "
+                        "are independent blocks over two rotating buffer sets; the backward solve and prediction of step i run on the "
+                        "look-ahead context's idle queue (cimrgp_solve_queue) beside the first panels of step i+1, whose Gram matrices run on the "
+                        "context's chain queue (cimrgp_front_queue) beside the last panels of step i; "
+                        "every step completes inside the timed region")
+                       if pipeline else "ONE cimrgp_block_posterior call per step on preallocated buffers (+ the collective's enqueue)",
+            "pipelined_steps": bool(pipeline),
+            "reduce_overlapped": bool(world > 1 or args.nccl_world1),
+        }
+        out.update(extra)
         print(json.dumps(out))
         if out.get("parity_ok") is False:
             raise SystemExit("bench.py: the GPU posterior differs from the oracle by more than 1e-5: mean %.3e var %.3e"

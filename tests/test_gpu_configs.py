@@ -325,7 +325,7 @@ def test_bench_weak_scaling_two_ranks_reduce_is_exact():
     """``bench.py --gpus 2`` (the driver's weak-scaling command; here two ranks share the card under gloo): one line,
     two posteriors per step, and the asynchronously started reduce of the fused [mean | var] buffer returns rank
     0's slice bit for bit (the other ranks contribute zeros there; the buffer is zeroed every step)."""
-    rec = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"], {"CIMRGP_BENCH_REHEARSAL": "gloo"})
+    rec = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--full"], {"CIMRGP_BENCH_REHEARSAL": "gloo"})
     assert rec["n_gpus"] == 2 and rec["scaling"] == "weak" and rec["value"] > 0
     assert rec["config"]["backend"] == "gloo" and rec["config"]["rows_queues"] == 1
     assert rec["reduce_selfcheck_max_abs_diff"] == 0.0
@@ -335,9 +335,9 @@ def test_bench_step_under_rccl_world_of_one():
     """The real bench step with backend nccl (= RCCL) initialised and the fused [mean | var] buffer reduced
     through it unconditionally -- the only RCCL evidence obtainable on one GPU -- beside the plain run, with
     the carried rows on two queues (the multi-GPU default) and on one."""
-    plain = _run_bench(["--steps", "10", "--warmup", "3", "--no-cpu-baseline"])
-    rccl2 = _run_bench(["--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--nccl-world1"])
-    rccl1 = _run_bench(["--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--nccl-world1", "--rows-queues", "1"])
+    plain = _run_bench(["--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--full"])
+    rccl2 = _run_bench(["--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--full", "--nccl-world1"])
+    rccl1 = _run_bench(["--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--full", "--nccl-world1", "--rows-queues", "1"])
     print("ms_per_step  plain %.3f | nccl world 1, two rows queues %.3f | one rows queue %.3f"
           % (plain["ms_per_step"], rccl2["ms_per_step"], rccl1["ms_per_step"]))
     # round 5: the step's collective is the C ABI's (cimrgp_allreduce_sum) on the step's own solve queue -- no RCCL stream of
@@ -358,10 +358,30 @@ def test_bench_falls_back_to_torch_nccl_when_the_c_abi_communicator_fails():
     """bench.py's N > 1 step creates the C ABI's RCCL communicator on every rank; if that fails on any of them (it has never
     seen more than one GPU) all ranks agree -- over the gloo control plane -- to reduce through torch.distributed's nccl
     instead, so that a scaling run still yields a line.  Exercised here with a simulated failure in a world of one."""
-    rec = _run_bench(["--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--nccl-world1"], env_extra={"CIMRGP_BENCH_FAIL_COMM": "1"})
+    rec = _run_bench(["--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--full", "--nccl-world1"], env_extra={"CIMRGP_BENCH_FAIL_COMM": "1"})
     assert rec["config"]["backend"].startswith("nccl (fallback")
     assert rec["reduce_overlapped"] is True and rec["reduce_selfcheck_max_abs_diff"] == 0.0
     assert rec["value"] > 0
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain ``bench.py`` run (no --full) prints the headline fields only, and ``--dump-outputs`` writes what the last
+    timed step computed -- mean, variance and alpha = K^-1 r of the seeded block -- which the CPU oracle reproduces."""
+    steps = 3
+    rec = _run_bench(["--steps", str(steps), "--warmup", "1", "--n", "2048", "--dump-outputs", str(tmp_path)])
+    assert rec["steps"] == steps and rec["unit"] == "posteriors/s" and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+    assert rec["value"] == pytest.approx(1e3 / rec["ms_per_step"])
+    assert not {"roofline", "stage_ms", "cpu_baseline", "parity_ok", "reduce_selfcheck_max_abs_diff"} & set(rec)
+    n, ns, q = 2048, 512, 2
+    got = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("mean", "var", "alpha")}
+    assert got["mean"].shape == (ns, q) and got["var"].shape == (ns,) and got["alpha"].shape == (n, q)
+    assert all(a.dtype == np.float64 for a in got.values())
+    x, y = workloads.make_block(n, q, 1234)
+    xs = workloads.block_test_points(ns)
+    fit = oracle.block_fit(x, y, 0.1, 1.0, 0.01)
+    omean, ovar = oracle.block_predict(x, fit, xs, 0.1, 1.0, True)
+    assert _relerr(got["mean"], omean) < 1e-8 and _relerr_elem(got["var"], ovar) < 1e-5
+    assert _relerr(got["alpha"], fit["alpha"]) < 1e-8
 
 
 def test_c_abi_collective_world_of_one(ca):
@@ -459,7 +479,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
         env.pop(k, None)
     env["CIMRGP_BENCH_REHEARSAL"] = "gloo"
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--n", "2048"], env=env, capture_output=True, text=True, timeout=600)
+                          "--n", "2048", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

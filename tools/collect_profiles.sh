@@ -10,10 +10,10 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 want() { case " $parts " in *" $1 "*) return 0;; esac; return 1; }
 ( cd cimrgp_amd/csrc && cat common.hpp gemm_tile.hpp gemm_nt.hip potrf.hip gram.hip | sha256sum ) > $out/${tag}_sources.sha256
 if want bench; then
-    python3 bench.py --steps 20 --warmup 3 > $out/${tag}_bench_n8192.json 2> $out/${tag}_bench.err || { tail -5 $out/${tag}_bench.err; exit 1; }
+    python3 bench.py --full --steps 20 --warmup 3 > $out/${tag}_bench_n8192.json 2> $out/${tag}_bench.err || { tail -5 $out/${tag}_bench.err; exit 1; }
 fi
 if want stats; then
-    rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline \
+    rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline \
         > $out/${tag}_bench_n8192_under_rocprof.json 2> $out/${tag}_stats.err || { tail -5 $out/${tag}_stats.err; exit 1; }
     cp "$(ls $out/${tag}_stats/*/*kernel_stats.csv | tail -1)" $out/${tag}_bench_n8192_kernel_stats.csv
     rm -rf $out/${tag}_stats
@@ -29,7 +29,7 @@ fi
 if want pmc; then
     for pass in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64"; do
         name=$(echo $pass | cut -d' ' -f1)
-        rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $out/${tag}_pmc_$name -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline \
+        rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $out/${tag}_pmc_$name -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline \
             > /dev/null 2> $out/${tag}_pmc_$name.err || { tail -5 $out/${tag}_pmc_$name.err; exit 1; }
     done
     python3 tools/pmc_summary.py $out/${tag}_pmc_FETCH_SIZE/ $out/${tag}_pmc_WRITE_SIZE/ $out/${tag}_pmc_SQ_VALU_MFMA_BUSY_CYCLES/ > $out/${tag}_pmc_raw.json
@@ -54,7 +54,7 @@ if want configs; then
 fi
 if want rccl; then
     for mode in "" "--nccl-world1" "--nccl-world1 --comm torch" "--nccl-world1 --rows-queues 1"; do
-        python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline $mode 2>/dev/null | tail -1
+        python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline $mode 2>/dev/null | tail -1
     done > $out/${tag}_rccl_world_of_one.jsonl
 fi
 if want config5; then

@@ -21,7 +21,7 @@ for cfg in "0 0" "256 0" "256 16" "256 32" "256 48" "256 64"; do
 done
 unset CIMRGP_LIB_PATH
 timeout -k 10 900 python3 -m pytest tests -x -q -m gpu > $OUT/r03a_tests.log 2>&1 || { tail -40 $OUT/r03a_tests.log; echo TESTS FAILED; }
-timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --cpu-warmups 0 --cpu-repeats 1 > $OUT/r03a_bench.json 2> $OUT/r03a_bench.err || { tail -20 $OUT/r03a_bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 3 --cpu-warmups 0 --cpu-repeats 1 > $OUT/r03a_bench.json 2> $OUT/r03a_bench.err || { tail -20 $OUT/r03a_bench.err; exit 1; }
 tail -3 $OUT/r03a_tests.log
 cat $OUT/r03a_gemm.log
 cat $OUT/r03a_potrf.log
