@@ -5,7 +5,9 @@ protocol of the reference's ``MaternKernel`` (KernelClass.py:40-65: attributes
 ``l``, ``sf``; methods ``kernel``, ``log_kernel``, ``spectral``,
 ``log_spectral``, ``estimate_kernel``) so that it can be passed as
 ``spectral_density_obj`` (scalar or per-layer list, MRGP.py:71-79), and adds
-the Gram builder that runs on the GPU.  ``MaternKernel`` and
+the Gram builder that runs on the GPU.  ``DenseMaternKernel`` is its Matern twin for
+half-integer nu (1/2, 3/2, 5/2) in closed form: the prior that the reduced-rank
+model approximates, on the same dense path.  ``MaternKernel`` and
 ``LaplacianEigenpairs`` are host-side restatements of the reference's
 reduced-rank objects, kept for API completeness (validated against captured
 reference outputs in tests/golden/kernel_objects.npz).
@@ -29,6 +31,13 @@ class RBFKernel(object):
         self.l = float(l)
         self.sf = float(sf)
         self.noise = None if noise is None else float(noise)
+
+    #: covariance id of the C ABI (include/cimrgp.h CIMRGP_COV_RBF)
+    cov = 0
+
+    def with_noise(self, noise):
+        """The same covariance with fixed noise variance ``noise``."""
+        return RBFKernel(self.l, self.sf, noise)
 
     # ---- scalar-distance protocol (host, NumPy) ---------------------------
     def log_kernel(self, r):
@@ -129,3 +138,83 @@ class MaternKernel(object):
     def estimate_kernel(self, phi_x1, phi_x2, lambdas):
         weights = self.spectral(np.sqrt(np.asarray(lambdas, dtype=np.float64)))
         return np.einsum('np,np,p->n', phi_x1, phi_x2, weights)
+
+
+class DenseMaternKernel(object):
+    """Matern covariance of half-integer smoothness on the dense path, in closed form with
+    t = sqrt(2 nu) r / l:
+        nu = 1/2:  sf exp(-t)                  (the exponential covariance)
+        nu = 3/2:  sf (1 + t) exp(-t)          (GPy's Matern32(variance=sf, lengthscale=l))
+        nu = 5/2:  sf (1 + t + t^2 / 3) exp(-t) (GPy's Matern52)
+    ``sf`` is the signal VARIANCE and k(0) = sf, as for :class:`RBFKernel`, whose protocol this
+    follows; ``spectral`` / ``estimate_kernel`` are those of :class:`MaternKernel` (the reference's
+    convention), so that the reduced-rank model over the Laplacian basis converges to this kernel
+    up to the reference's factor sqrt(2).  General real nu stays with :class:`MaternKernel`."""
+    name = 'Matern'
+    #: nu -> covariance id of the C ABI (include/cimrgp.h CIMRGP_COV_MATERN12/32/52)
+    COV_IDS = {0.5: 1, 1.5: 2, 2.5: 3}
+
+    def __init__(self, nu=1.5, l=1., sf=1., noise=None):
+        if float(nu) not in self.COV_IDS:
+            raise ValueError('nu must be 0.5, 1.5 or 2.5 (general nu: MaternKernel, reduced-rank path only)')
+        if not l > 0:
+            raise ValueError('length-scale must be positive')
+        if not sf > 0:
+            raise ValueError('signal variance must be positive')
+        self.nu = float(nu)
+        self.l = float(l)
+        self.sf = float(sf)
+        self.noise = None if noise is None else float(noise)
+        self.cov = self.COV_IDS[self.nu]
+
+    def with_noise(self, noise):
+        """The same covariance with fixed noise variance ``noise``."""
+        return DenseMaternKernel(self.nu, self.l, self.sf, noise)
+
+    # ---- scalar-distance protocol (host, NumPy) ---------------------------
+    def _log_poly(self, t):
+        if self.nu == 0.5:
+            return np.zeros_like(t)
+        if self.nu == 1.5:
+            return np.log1p(t)
+        return np.log1p(t + t * t / 3.0)
+
+    def log_kernel(self, r):
+        t = np.sqrt(2 * self.nu) * np.abs(np.asarray(r, dtype=np.float64)) / self.l
+        return np.log(self.sf) + self._log_poly(t) - t
+
+    def kernel(self, r):
+        return np.exp(self.log_kernel(r))
+
+    def _matern(self):
+        return MaternKernel(nu=self.nu, l=self.l, sf=self.sf)
+
+    def log_spectral(self, s):
+        return self._matern().log_spectral(s)
+
+    def spectral(self, s):
+        return self._matern().spectral(s)
+
+    def estimate_kernel(self, phi_x1, phi_x2, lambdas):
+        """Reduced-rank reconstruction sum_p S(sqrt(lambda_p)) phi_p(x) phi_p(x')."""
+        return self._matern().estimate_kernel(phi_x1, phi_x2, lambdas)
+
+    # ---- dense Gram builder (device, HIP) ---------------------------------
+    def gram(self, x, x2=None, diag_add=0.0, lower_only=False):
+        """Gram matrix on the GPU (k_cov_gram).  ``x``/``x2``: CUDA tensors (n x d).  Returns a
+        torch view (n x n2) of the padded device buffer."""
+        from . import device as dev
+        if x2 is None:
+            buf = dev.rbf_gram(x, self.l, self.sf, diag_add, lower_only, cov=self.cov)
+            return buf[:x.shape[0], :x.shape[0]]
+        buf = dev.rbf_cross(x, x2, self.l, self.sf, cov=self.cov)
+        return buf[:x.shape[0], :x2.shape[0]]
+
+    def K(self, x, x2=None, dtype='f64'):
+        """NumPy in / NumPy out convenience around :meth:`gram` (computed on the GPU)."""
+        from . import device as dev
+        device = dev.require_gpu()
+        tdt = dev.as_torch_dtype(dtype)
+        xd = dev.to_device(np.atleast_2d(x), tdt, device)
+        x2d = None if x2 is None else dev.to_device(np.atleast_2d(x2), tdt, device)
+        return self.gram(xd, x2d).cpu().numpy()

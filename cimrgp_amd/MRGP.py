@@ -28,7 +28,7 @@ import torch
 from . import device as dev
 from . import dist
 from .Inputs import Inputs
-from .KernelClass import RBFKernel
+from .KernelClass import RBFKernel, DenseMaternKernel
 from .Posteriors import DensePosterior, _Fanout
 
 
@@ -130,14 +130,16 @@ class MultiResolutionGaussianProcess(object):
         else:
             self.spectral_density_obj = [spectral_density_obj] * self.n_layers
         for k in self.spectral_density_obj:
-            if not isinstance(k, RBFKernel):
-                # a spectral density without a basis-function object: neither path applies
-                raise TypeError('spectral_density_obj must be an RBFKernel when basis_function_obj is None')
+            if not isinstance(k, (RBFKernel, DenseMaternKernel)):
+                # a spectral density without a basis-function object (MaternKernel: general nu, no closed form):
+                # neither path applies
+                raise TypeError('spectral_density_obj must be an RBFKernel or a DenseMaternKernel (nu = 1/2, 3/2, 5/2) '
+                                'when basis_function_obj is None')
         if snr_ratio is not None:
             # reference: initial noise variance of layer 0 from an SNR (MRGP.py:196-199,966-971)
             self.spectral_density_obj = list(self.spectral_density_obj)
             k0 = self.spectral_density_obj[0]
-            self.spectral_density_obj[0] = RBFKernel(k0.l, k0.sf, self._compute_initial_noise_var_from_snr(y_train, snr_ratio))
+            self.spectral_density_obj[0] = k0.with_noise(self._compute_initial_noise_var_from_snr(y_train, snr_ratio))
 
         self.device = dev.require_gpu(device)
         self.dtype = dev.as_torch_dtype(dtype)

@@ -4,8 +4,9 @@ Dense twin of the reference's ``Posterior`` (Posteriors.py:9-211): constructed
 per layer, holds per-region state in lists indexed by region, and is updated
 IN PLACE from lists indexed by region (Posteriors.py:35,81,113).  Where the
 reference's ``update_scale_given_axis`` forms a diagonal precision and the
-projected targets y~ (Posteriors.py:35-78), this class builds the RBF Gram
-matrix of the region, factors it and solves for the weights -- D1, D2, D3 of
+projected targets y~ (Posteriors.py:35-78), this class builds the Gram
+matrix of the region under the layer's covariance (RBF or a half-integer Matern,
+the kernel object's ``cov``), factors it and solves for the weights -- D1, D2, D3 of
 SURVEY.md 8a' -- through the hand-written HIP kernels.
 """
 import os
@@ -113,7 +114,7 @@ class DenseBlock(object):
         else:
             self.noise = dev.noise_from_stats(stats, q, NOISE_FRACTION, NOISE_FLOOR * k.sf)
         self.r = dev.residual(y, f_bar, self.bias)
-        self.lbuf = dev.rbf_gram(self.x, k.l, k.sf, 0.0, lower_only=True)
+        self.lbuf = dev.rbf_gram(self.x, k.l, k.sf, 0.0, lower_only=True, cov=k.cov)
         dev.add_diag(self.lbuf, self.n, self.noise)
         # the targets ride through the factorisation as q extra rows: z = L^-1 r comes out of the
         # same panel sweep (no separate forward solve), then one backward solve gives alpha
@@ -142,14 +143,14 @@ class DenseBlock(object):
         variance, read from the device (no host round trip)."""
         k = self.kernel
         if var_out is None:
-            dev.predict_mean(self.x, self.alpha, xs, k.l, k.sf, self.bias, out=mean_out, accumulate=True)
+            dev.predict_mean(self.x, self.alpha, xs, k.l, k.sf, self.bias, out=mean_out, accumulate=True, cov=k.cov)
             return
         if self.lbuf is None:
             raise RuntimeError('predictive variance needs the Cholesky factor: fit with keep_factors=True')
         ns = xs.shape[0]
         for s0 in range(0, ns, chunk):
             s1 = min(ns, s0 + chunk)
-            w = dev.rbf_cross(xs[s0:s1], self.x, k.l, k.sf)
+            w = dev.rbf_cross(xs[s0:s1], self.x, k.l, k.sf, cov=k.cov)
             dev.trsm_rows(self.lbuf, self.n, self.ws, w, s1 - s0)
             dev.predict_from_w(w, s1 - s0, self.n, self.z, k.sf, extra_var, self.bias,
                                mean_out[s0:s1], var_out[s0:s1], accumulate=True,
@@ -297,7 +298,7 @@ class DensePosterior(object):
             starts = torch.tensor(rows_y, dtype=torch.int64).to(device, non_blocking=True)
             dev.layer_fit(x_all, y_all, f_all, t_all, starts, n, k.l, k.sf, -1.0 if k.noise is None else float(k.noise),
                           NOISE_FRACTION, NOISE_FLOOR * k.sf, shared_bias, shared_noise, karena, ws_arena, info, bias, noise,
-                          z, alpha)
+                          z, alpha, cov=k.cov)
             batch = _FittedBatch(sub, n, starts, karena, ws_arena, z, bias, noise) if keep_factors else None
             if batch is not None:
                 self.batches.append(batch)
@@ -340,7 +341,7 @@ class DensePosterior(object):
                     t_starts = torch.tensor([a for _, a in part], dtype=torch.int64).to(xs.device, non_blocking=True)
                     dev.layer_predict(x_all, bt.starts[i0:i0 + nb], bt.n, xs, t_starts, ns, self.kernel.l, self.kernel.sf,
                                       bt.karena[i0:i0 + nb], bt.ws_arena[i0:i0 + nb], bt.z[i0:i0 + nb], bt.bias[i0:i0 + nb],
-                                      bt.noise[i0:i0 + nb] if add_noise else None, mean, var)
+                                      bt.noise[i0:i0 + nb] if add_noise else None, mean, var, cov=self.kernel.cov)
                 done.update(bt.regions[i] for i, _ in items)
         rest = [l for l in owned if l not in done]
         if not rest:

@@ -12,6 +12,11 @@ default ``'lbfgsb'`` wraps) on the log marginal likelihood over (variance, lengt
 noise), all constrained positive through a log transform, starting from those defaults;
 objective and gradient are evaluated on the GPU (one Cholesky, K^-1 = L^-T L^-1 through the
 MFMA kernels, one fused reduction for the gradient).  Default is fixed hyper-parameters.
+
+``GP_Matern`` is the same plugin with a half-integer Matern covariance (nu = 1/2, 3/2, 5/2;
+GPy's ``Matern32(variance, lengthscale)`` is ``GP_Matern(1.5, lengthscale, variance)``): it
+differs from ``GP_RBF`` only in the kernel object ``_make_kernel`` builds, whose ``cov`` selects
+the covariance of every Gram, gradient and prediction kernel.
 """
 import abc
 
@@ -19,7 +24,7 @@ import numpy as np
 import torch
 
 from . import device as dev
-from .KernelClass import RBFKernel
+from .KernelClass import RBFKernel, DenseMaternKernel
 from .Posteriors import DenseBlock, NOISE_FRACTION
 
 
@@ -84,7 +89,7 @@ class GP_RBF(RegressionMethod):
         self._initial = (float(lengthscale), float(variance))
         self.ARD = bool(ARD)
         self.lengthscales = None             # ARD: (d,) vector after fit
-        self.kernel = RBFKernel(l=lengthscale, sf=variance)
+        self.kernel = self._make_kernel(lengthscale, variance)
         self.dtype = dev.as_torch_dtype(dtype)
         self.device = device
         self.block = None
@@ -92,12 +97,17 @@ class GP_RBF(RegressionMethod):
         self.max_iters = max_iters
         self.optimizer_result = None
 
+    def _make_kernel(self, l, sf, noise=None):
+        """The plugin's covariance object (the one hook of a subclass with another covariance)."""
+        return RBFKernel(l=l, sf=sf, noise=noise)
+
     # ---- log marginal likelihood and its gradient, on the GPU ----------------------------
     def log_marginal_likelihood(self, x, y, ell, sf, noise, want_grad=True):
         """LML of targets y (device, n x q) under K = sf E(ell) + noise I, and its gradient
         w.r.t. (log sf, log ell, log noise).  Raises LinAlgError if K is not PD."""
         n, q = y.shape
-        kbuf = dev.rbf_gram(x, ell, sf, noise, lower_only=True)
+        cov = self.kernel.cov
+        kbuf = dev.rbf_gram(x, ell, sf, noise, lower_only=True, cov=cov)
         ws, info = dev.potrf(kbuf, n)
         alpha = y.clone()
         dev.potrs(kbuf, n, ws, alpha)
@@ -116,7 +126,7 @@ class GP_RBF(RegressionMethod):
         kinv.zero_()
         dev.syrk_lower(kinv, u, n, n)            # lower(kinv) = -K^-1
         kinv.neg_()
-        grad = dev.lml_grad(x, kinv, n, alpha, ell, sf, noise).cpu().numpy()
+        grad = dev.lml_grad(x, kinv, n, alpha, ell, sf, noise, cov=cov).cpu().numpy()
         return lml, grad
 
     def log_marginal_likelihood_ard(self, x, y, ells, sf, noise):
@@ -125,7 +135,8 @@ class GP_RBF(RegressionMethod):
         scale = torch.as_tensor(1.0 / np.asarray(ells, dtype=np.float64), dtype=x.dtype, device=x.device)
         xs = (x * scale).contiguous()
         n, q = y.shape
-        kbuf = dev.rbf_gram(xs, 1.0, sf, noise, lower_only=True)
+        cov = self.kernel.cov
+        kbuf = dev.rbf_gram(xs, 1.0, sf, noise, lower_only=True, cov=cov)
         ws, info = dev.potrf(kbuf, n)
         alpha = y.clone()
         dev.potrs(kbuf, n, ws, alpha)
@@ -140,7 +151,7 @@ class GP_RBF(RegressionMethod):
         kinv.zero_()
         dev.syrk_lower(kinv, u, n, n)
         kinv.neg_()
-        return lml, dev.lml_grad_ard(xs, kinv, n, alpha, sf, noise).cpu().numpy()
+        return lml, dev.lml_grad_ard(xs, kinv, n, alpha, sf, noise, cov=cov).cpu().numpy()
 
     def _optimize_ard(self, x, y, noise0):
         from scipy.optimize import minimize
@@ -158,7 +169,7 @@ class GP_RBF(RegressionMethod):
         res = minimize(objective, theta0, jac=True, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
         self.optimizer_result = res
         self.lengthscales = np.exp(res.x[1:1 + d])
-        self.kernel = RBFKernel(l=1.0, sf=float(np.exp(res.x[0])), noise=float(np.exp(res.x[-1])))
+        self.kernel = self._make_kernel(1.0, float(np.exp(res.x[0])), float(np.exp(res.x[-1])))
 
     def _optimize(self, x, y, noise0):
         from scipy.optimize import minimize
@@ -175,7 +186,7 @@ class GP_RBF(RegressionMethod):
         res = minimize(objective, theta0, jac=True, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
         self.optimizer_result = res
         sf, ell, noise = np.exp(res.x)
-        self.kernel = RBFKernel(l=float(ell), sf=float(sf), noise=float(noise))
+        self.kernel = self._make_kernel(float(ell), float(sf), float(noise))
 
     def _fit(self, train_data):
         inputs, labels = train_data
@@ -184,7 +195,7 @@ class GP_RBF(RegressionMethod):
         labels = np.atleast_2d(np.asarray(labels, dtype=np.float64))
         # every fit starts from the constructor's values (a re-fit does not start from the
         # previous optimum); the noise of the plugin is a property of the (z-scored) labels as a whole
-        self.kernel = RBFKernel(l=self._initial[0], sf=self._initial[1])
+        self.kernel = self._make_kernel(self._initial[0], self._initial[1])
         self.kernel.noise = float(labels.var()) * NOISE_FRACTION
         x = dev.to_device(inputs, self.dtype, device)
         y = dev.to_device(labels, self.dtype, device)
@@ -193,7 +204,7 @@ class GP_RBF(RegressionMethod):
                 self._optimize_ard(x, y, self.kernel.noise)
             else:
                 self.lengthscales = np.full(x.shape[1], self.kernel.l)
-                self.kernel = RBFKernel(l=1.0, sf=self.kernel.sf, noise=self.kernel.noise)
+                self.kernel = self._make_kernel(1.0, self.kernel.sf, self.kernel.noise)
             self._scale = torch.as_tensor(1.0 / self.lengthscales, dtype=self.dtype, device=device)
             x = (x * self._scale).contiguous()           # unit length-scale from here on
         elif self.optimize:
@@ -228,3 +239,20 @@ class GP_RBF(RegressionMethod):
         if self.preprocess:
             mean = self._reverse_trans_labels(mean)
         return mean, var
+
+
+class GP_Matern(GP_RBF):
+    """``GP_RBF`` with the Matern covariance of smoothness ``nu`` in {0.5, 1.5, 2.5}
+    (:class:`~cimrgp_amd.KernelClass.DenseMaternKernel`): the same z-scoring, noise rule,
+    L-BFGS-B optimisation of the log-transformed (variance, length-scale(s), noise), ARD and
+    ``predict_with_variance``.  GPy's ``Matern32(input_dim, variance, lengthscale)`` maps to
+    ``GP_Matern(1.5, lengthscale, variance)``, ``Matern52`` to ``nu = 2.5``."""
+    name = 'GP_Matern'
+
+    def __init__(self, nu=1.5, lengthscale=1., variance=1., dtype='f64', device=None, optimize=True, max_iters=1000, ARD=False):
+        DenseMaternKernel(nu)                # ValueError for an unsupported nu, before anything else
+        self.nu = float(nu)
+        super(GP_Matern, self).__init__(lengthscale, variance, dtype, device, optimize, max_iters, ARD)
+
+    def _make_kernel(self, l, sf, noise=None):
+        return DenseMaternKernel(nu=self.nu, l=l, sf=sf, noise=noise)

@@ -7,13 +7,13 @@ over hand-written HIP kernels reached through the C ABI of ``libcimrgp.so``
 GPU, computing does.
 """
 from .IndexSetGenerator import IndexSetUniform
-from .KernelClass import RBFKernel, MaternKernel, LaplacianEigenpairs
+from .KernelClass import RBFKernel, DenseMaternKernel, MaternKernel, LaplacianEigenpairs
 from .BasisInterval import BasisInterval
-from .RegressionInput import RegressionMethod, GP_RBF
+from .RegressionInput import RegressionMethod, GP_RBF, GP_Matern
 from .Inputs import space_filling_order
 from .Posteriors import DensePosterior, DenseBlock
 from .MRGP import MultiResolutionGaussianProcess
 from . import _lib, device, dist
 
-__all__ = ["IndexSetUniform", "RBFKernel", "MaternKernel", "LaplacianEigenpairs", "BasisInterval", "RegressionMethod",
-           "GP_RBF", "DensePosterior", "DenseBlock", "MultiResolutionGaussianProcess", "space_filling_order", "device", "dist"]
+__all__ = ["IndexSetUniform", "RBFKernel", "DenseMaternKernel", "MaternKernel", "LaplacianEigenpairs", "BasisInterval", "RegressionMethod",
+           "GP_RBF", "GP_Matern", "DensePosterior", "DenseBlock", "MultiResolutionGaussianProcess", "space_filling_order", "device", "dist"]

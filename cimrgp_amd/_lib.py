@@ -8,6 +8,8 @@ import ctypes as C
 import os
 
 F32, F64 = 0, 1
+#: include/cimrgp.h CIMRGP_COV_*
+COV_RBF, COV_MATERN12, COV_MATERN32, COV_MATERN52 = 0, 1, 2, 3
 NB = 256
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -22,6 +24,8 @@ SIGNATURES = {
     "cimrgp_device_count": (_i32, []),
     "cimrgp_rbf_gram": (_i32, [_i32, _vp, _i64, _i32, _dbl, _dbl, _dbl, _vp, _i64, _i32, _vp]),
     "cimrgp_rbf_cross": (_i32, [_i32, _vp, _i64, _vp, _i64, _i32, _dbl, _dbl, _vp, _i64, _vp]),
+    "cimrgp_cov_gram": (_i32, [_i32, _i32, _vp, _i64, _i32, _dbl, _dbl, _dbl, _vp, _i64, _i32, _vp]),
+    "cimrgp_cov_cross": (_i32, [_i32, _i32, _vp, _i64, _vp, _i64, _i32, _dbl, _dbl, _vp, _i64, _vp]),
     "cimrgp_potrf_workspace_bytes": (_sz, [_i32, _i64]),
     "cimrgp_potrf": (_i32, [_i32, _vp, _i64, _i64, _vp, _sz, _vp, _vp]),
     "cimrgp_potrf_rows": (_i32, [_i32, _vp, _i64, _i64, _vp, _sz, _vp, _vp, _i64, _i64, _vp]),
@@ -37,6 +41,7 @@ SIGNATURES = {
     "cimrgp_potrs": (_i32, [_i32, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
     "cimrgp_trsm_rows": (_i32, [_i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp]),
     "cimrgp_predict_mean": (_i32, [_i32, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _dbl, _dbl, _vp, _vp, _i32, _vp]),
+    "cimrgp_cov_predict_mean": (_i32, [_i32, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _dbl, _dbl, _vp, _vp, _i32, _vp]),
     "cimrgp_predict_from_w": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _i32, _vp]),
     "cimrgp_block_stats": (_i32, [_i32, _vp, _vp, _i64, _i32, _vp, _vp]),
     "cimrgp_residual": (_i32, [_i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
@@ -48,6 +53,8 @@ SIGNATURES = {
     "cimrgp_lml_grad_scratch_bytes": (_sz, [_i64]),
     "cimrgp_lml_grad": (_i32, [_i32, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp]),
     "cimrgp_lml_grad_ard": (_i32, [_i32, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp]),
+    "cimrgp_cov_lml_grad": (_i32, [_i32, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp]),
+    "cimrgp_cov_lml_grad_ard": (_i32, [_i32, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp]),
     "cimrgp_laplace_basis": (_i32, [_i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     "cimrgp_basis_moments_scratch_bytes": (_sz, [_i64, _i32, _i32]),
     "cimrgp_basis_moments": (_i32, [_i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
@@ -56,6 +63,10 @@ SIGNATURES = {
                                 _vp, _i64, _i64, _vp, _sz, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cimrgp_layer_predict": (_i32, [_i32, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _dbl, _dbl, _vp, _i64, _i64, _vp, _sz,
                                     _vp, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "cimrgp_layer_fit_cov": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _vp,
+                                    _vp, _vp, _i64, _i64, _vp, _sz, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cimrgp_layer_predict_cov": (_i32, [_i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _dbl, _dbl, _vp, _i64, _i64, _vp,
+                                        _sz, _vp, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "cimrgp_comm_unique_id": (_i32, [_vp]),
     "cimrgp_comm_create": (_i32, [_i32, _i32, _vp, C.POINTER(_vp)]),
     "cimrgp_comm_destroy": (_i32, [_vp]),

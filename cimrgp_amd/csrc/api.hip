@@ -94,9 +94,10 @@ static int layer_fit_typed(const void* x, const void* y, const void* fbar, void*
                            int64_t n, int d, int q, double ell, double sf2, double noise_fixed, double noise_frac,
                            double noise_floor, const void* shared_bias, const void* shared_noise, void* k, int64_t ldk,
                            int64_t k_stride, void* ws, size_t ws_stride_bytes, int32_t* info, void* rows, int64_t ldr, void* z,
-                           void* alpha, void* bias, void* noise, void* scratch, hipStream_t st)
+                           void* alpha, void* bias, void* noise, void* scratch, hipStream_t st, int cov)
 {
     LayerFit<T> a;
+    a.cov = cov;
     a.x = (const T*)x; a.y = (const T*)y; a.fbar = (const T*)fbar; a.train_out = (T*)train_out; a.starts = starts;
     a.batch = batch; a.n = n; a.d = d; a.q = q;
     a.ell = ell; a.sf2 = sf2; a.noise_fixed = noise_fixed; a.noise_frac = noise_frac; a.noise_floor = noise_floor;
@@ -111,9 +112,10 @@ template <typename T>
 static int layer_predict_typed(const void* x, const int64_t* starts, int64_t n, int d, const void* xs, const int64_t* t_starts,
                                int64_t ns, int batch, double ell, double sf2, const void* l, int64_t ldl, int64_t l_stride,
                                const void* ws, size_t ws_stride_bytes, const void* z, int q, const void* bias, const void* noise,
-                               void* w, int64_t ldw, int64_t w_stride, void* mean, void* var, hipStream_t st)
+                               void* w, int64_t ldw, int64_t w_stride, void* mean, void* var, hipStream_t st, int cov)
 {
     LayerPredict<T> a;
+    a.cov = cov;
     a.x = (const T*)x; a.starts = starts; a.n = n; a.d = d; a.xs = (const T*)xs; a.t_starts = t_starts; a.ns = ns; a.batch = batch;
     a.ell = ell; a.sf2 = sf2; a.l = (const T*)l; a.ldl = ldl; a.sl = l_stride; a.ws = (const T*)ws;
     a.sws = (int64_t)(ws_stride_bytes / sizeof(T)); a.z = (const T*)z; a.q = q; a.bias = (const T*)bias; a.noise = (const T*)noise;
@@ -331,6 +333,34 @@ int cimrgp_rbf_cross(int dtype, const void* xa_dev, int64_t na, const void* xb_d
                                   ld, false, false, S(stream)));
 }
 
+int cimrgp_cov_gram(int dtype, int cov, const void* x_dev, int64_t n, int d, double ell, double sf2, double diag_add,
+                    void* k_dev, int64_t ldk, int lower_only, void* stream)
+{
+    const char* fn = "cimrgp_cov_gram";
+    CIMRGP_REQUIRE(x_dev && k_dev, fn, "null pointer");
+    CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
+    CIMRGP_REQUIRE(n >= 0, fn, "negative size");
+    DISPATCH(dtype, fn,
+             rbf_gram_run<float>((const float*)x_dev, n, (const float*)x_dev, n, d, ell, sf2, diag_add, (float*)k_dev, ldk,
+                                 true, lower_only != 0, S(stream), cov, fn),
+             rbf_gram_run<double>((const double*)x_dev, n, (const double*)x_dev, n, d, ell, sf2, diag_add, (double*)k_dev,
+                                  ldk, true, lower_only != 0, S(stream), cov, fn));
+}
+
+int cimrgp_cov_cross(int dtype, int cov, const void* xa_dev, int64_t na, const void* xb_dev, int64_t nb, int d, double ell,
+                     double sf2, void* kab_dev, int64_t ld, void* stream)
+{
+    const char* fn = "cimrgp_cov_cross";
+    CIMRGP_REQUIRE(xa_dev && xb_dev && kab_dev, fn, "null pointer");
+    CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
+    CIMRGP_REQUIRE(na >= 0 && nb >= 0, fn, "negative size");
+    DISPATCH(dtype, fn,
+             rbf_gram_run<float>((const float*)xa_dev, na, (const float*)xb_dev, nb, d, ell, sf2, 0.0, (float*)kab_dev, ld,
+                                 false, false, S(stream), cov, fn),
+             rbf_gram_run<double>((const double*)xa_dev, na, (const double*)xb_dev, nb, d, ell, sf2, 0.0, (double*)kab_dev,
+                                  ld, false, false, S(stream), cov, fn));
+}
+
 size_t cimrgp_potrf_workspace_bytes(int dtype, int64_t n)
 {
     if (n <= 0) return 0;
@@ -523,6 +553,21 @@ int cimrgp_predict_mean(int dtype, const void* x_dev, int64_t n, int d, const vo
                                       ell, sf2, (const double*)bias_dev, (double*)mean_dev, accumulate, S(stream)));
 }
 
+int cimrgp_cov_predict_mean(int dtype, int cov, const void* x_dev, int64_t n, int d, const void* alpha_dev, int q,
+                            const void* xs_dev, int64_t ns, double ell, double sf2, const void* bias_dev, void* mean_dev,
+                            int accumulate, void* stream)
+{
+    const char* fn = "cimrgp_cov_predict_mean";
+    CIMRGP_REQUIRE(x_dev && alpha_dev && xs_dev && mean_dev, fn, "null pointer");
+    CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
+    CIMRGP_REQUIRE(n >= 0 && ns >= 0, fn, "negative size");
+    DISPATCH(dtype, fn,
+             predict_mean_run<float>((const float*)x_dev, n, d, (const float*)alpha_dev, q, (const float*)xs_dev, ns, ell,
+                                     sf2, (const float*)bias_dev, (float*)mean_dev, accumulate, S(stream), cov, fn),
+             predict_mean_run<double>((const double*)x_dev, n, d, (const double*)alpha_dev, q, (const double*)xs_dev, ns,
+                                      ell, sf2, (const double*)bias_dev, (double*)mean_dev, accumulate, S(stream), cov, fn));
+}
+
 int cimrgp_predict_from_w(int dtype, const void* w_dev, int64_t ns, int64_t n, int64_t ldw, const void* z_dev, int q,
                           double sf2, double extra_var, const void* extra_var_dev, const void* bias_dev, void* mean_dev,
                           void* var_dev, int accumulate, void* stream)
@@ -640,6 +685,37 @@ int cimrgp_lml_grad_ard(int dtype, const void* xs_dev, int64_t n, int d, const v
                                   sf2, noise, out_dev, scratch_dev, S(stream), true));
 }
 
+int cimrgp_cov_lml_grad(int dtype, int cov, const void* x_dev, int64_t n, int d, const void* kinv_dev, int64_t ldk,
+                        const void* alpha_dev, int q, double ell, double sf2, double noise, double* out_dev, double* scratch_dev,
+                        void* stream)
+{
+    const char* fn = "cimrgp_cov_lml_grad";
+    CIMRGP_REQUIRE(x_dev && kinv_dev && alpha_dev && out_dev && scratch_dev, fn, "null pointer");
+    CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
+    CIMRGP_REQUIRE(ldk >= n, fn, "bad dimensions");
+    CIMRGP_REQUIRE(ell > 0.0, fn, "length-scale must be positive");
+    DISPATCH(dtype, fn,
+             lml_grad_run<float>((const float*)x_dev, n, d, (const float*)kinv_dev, ldk, (const float*)alpha_dev, q, ell, sf2,
+                                 noise, out_dev, scratch_dev, S(stream), false, cov, fn),
+             lml_grad_run<double>((const double*)x_dev, n, d, (const double*)kinv_dev, ldk, (const double*)alpha_dev, q, ell,
+                                  sf2, noise, out_dev, scratch_dev, S(stream), false, cov, fn));
+}
+
+int cimrgp_cov_lml_grad_ard(int dtype, int cov, const void* xs_dev, int64_t n, int d, const void* kinv_dev, int64_t ldk,
+                            const void* alpha_dev, int q, double sf2, double noise, double* out_dev, double* scratch_dev,
+                            void* stream)
+{
+    const char* fn = "cimrgp_cov_lml_grad_ard";
+    CIMRGP_REQUIRE(xs_dev && kinv_dev && alpha_dev && out_dev && scratch_dev, fn, "null pointer");
+    CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
+    CIMRGP_REQUIRE(ldk >= n, fn, "bad dimensions");
+    DISPATCH(dtype, fn,
+             lml_grad_run<float>((const float*)xs_dev, n, d, (const float*)kinv_dev, ldk, (const float*)alpha_dev, q, 1.0, sf2,
+                                 noise, out_dev, scratch_dev, S(stream), true, cov, fn),
+             lml_grad_run<double>((const double*)xs_dev, n, d, (const double*)kinv_dev, ldk, (const double*)alpha_dev, q, 1.0,
+                                  sf2, noise, out_dev, scratch_dev, S(stream), true, cov, fn));
+}
+
 size_t cimrgp_lml_grad_scratch_bytes(int64_t n)
 {
     if (n <= 0) return 0;
@@ -690,14 +766,14 @@ int cimrgp_basis_apply(int dtype, const void* x_dev, int64_t n, int d, const dou
                                      (double*)mean_dev, (double*)var_dev, accumulate, S(stream)));
 }
 
-int cimrgp_layer_fit(int dtype, const void* x_dev, const void* y_dev, const void* fbar_dev, void* train_out_dev,
-                     const int64_t* starts_dev, int batch, int64_t n, int d, int q, double ell, double sf2, double noise_fixed,
-                     double noise_frac, double noise_floor, const void* shared_bias_dev, const void* shared_noise_dev,
-                     void* k_arena_dev, int64_t ldk, int64_t k_stride, void* ws_arena_dev, size_t ws_stride_bytes,
-                     int32_t* info_dev, void* rows_arena_dev, int64_t ldr, void* z_dev, void* alpha_dev, void* bias_dev,
-                     void* noise_dev, void* scratch_dev, void* stream)
+// cimrgp_layer_fit[_cov] and cimrgp_layer_predict[_cov]; `fn` names the entry point in error messages
+static int layer_fit_impl(const char* fn, int dtype, int cov, const void* x_dev, const void* y_dev, const void* fbar_dev,
+                          void* train_out_dev, const int64_t* starts_dev, int batch, int64_t n, int d, int q, double ell, double sf2,
+                          double noise_fixed, double noise_frac, double noise_floor, const void* shared_bias_dev,
+                          const void* shared_noise_dev, void* k_arena_dev, int64_t ldk, int64_t k_stride, void* ws_arena_dev,
+                          size_t ws_stride_bytes, int32_t* info_dev, void* rows_arena_dev, int64_t ldr, void* z_dev, void* alpha_dev,
+                          void* bias_dev, void* noise_dev, void* scratch_dev, void* stream)
 {
-    const char* fn = "cimrgp_layer_fit";
     CIMRGP_REQUIRE(x_dev && y_dev && train_out_dev && starts_dev && k_arena_dev && ws_arena_dev && info_dev && rows_arena_dev &&
                    z_dev && alpha_dev && bias_dev && noise_dev && scratch_dev, fn, "null pointer");
     CIMRGP_REQUIRE(dtype == CIMRGP_F32 || dtype == CIMRGP_F64, fn, "unknown dtype");
@@ -712,20 +788,19 @@ int cimrgp_layer_fit(int dtype, const void* x_dev, const void* y_dev, const void
              layer_fit_typed<float>(x_dev, y_dev, fbar_dev, train_out_dev, starts_dev, batch, n, d, q, ell, sf2, noise_fixed,
                                     noise_frac, noise_floor, shared_bias_dev, shared_noise_dev, k_arena_dev, ldk, k_stride,
                                     ws_arena_dev, ws_stride_bytes, info_dev, rows_arena_dev, ldr, z_dev, alpha_dev, bias_dev,
-                                    noise_dev, scratch_dev, S(stream)),
+                                    noise_dev, scratch_dev, S(stream), cov),
              layer_fit_typed<double>(x_dev, y_dev, fbar_dev, train_out_dev, starts_dev, batch, n, d, q, ell, sf2, noise_fixed,
                                      noise_frac, noise_floor, shared_bias_dev, shared_noise_dev, k_arena_dev, ldk, k_stride,
                                      ws_arena_dev, ws_stride_bytes, info_dev, rows_arena_dev, ldr, z_dev, alpha_dev, bias_dev,
-                                     noise_dev, scratch_dev, S(stream)));
+                                     noise_dev, scratch_dev, S(stream), cov));
 }
 
-int cimrgp_layer_predict(int dtype, const void* x_dev, const int64_t* starts_dev, int64_t n, int d, const void* xs_dev,
-                         const int64_t* t_starts_dev, int64_t ns, int batch, double ell, double sf2, const void* l_arena_dev,
-                         int64_t ldl, int64_t l_stride, const void* ws_arena_dev, size_t ws_stride_bytes, const void* z_dev, int q,
-                         const void* bias_dev, const void* noise_dev, void* w_arena_dev, int64_t ldw, int64_t w_stride,
-                         void* mean_dev, void* var_dev, void* stream)
+static int layer_predict_impl(const char* fn, int dtype, int cov, const void* x_dev, const int64_t* starts_dev, int64_t n, int d,
+                              const void* xs_dev, const int64_t* t_starts_dev, int64_t ns, int batch, double ell, double sf2,
+                              const void* l_arena_dev, int64_t ldl, int64_t l_stride, const void* ws_arena_dev,
+                              size_t ws_stride_bytes, const void* z_dev, int q, const void* bias_dev, const void* noise_dev,
+                              void* w_arena_dev, int64_t ldw, int64_t w_stride, void* mean_dev, void* var_dev, void* stream)
 {
-    const char* fn = "cimrgp_layer_predict";
     CIMRGP_REQUIRE(x_dev && starts_dev && xs_dev && t_starts_dev && l_arena_dev && ws_arena_dev && z_dev && w_arena_dev &&
                    mean_dev && var_dev, fn, "null pointer");
     CIMRGP_REQUIRE(dtype == CIMRGP_F32 || dtype == CIMRGP_F64, fn, "unknown dtype");
@@ -738,10 +813,64 @@ int cimrgp_layer_predict(int dtype, const void* x_dev, const int64_t* starts_dev
     DISPATCH(dtype, fn,
              layer_predict_typed<float>(x_dev, starts_dev, n, d, xs_dev, t_starts_dev, ns, batch, ell, sf2, l_arena_dev, ldl,
                                         l_stride, ws_arena_dev, ws_stride_bytes, z_dev, q, bias_dev, noise_dev, w_arena_dev, ldw,
-                                        w_stride, mean_dev, var_dev, S(stream)),
+                                        w_stride, mean_dev, var_dev, S(stream), cov),
              layer_predict_typed<double>(x_dev, starts_dev, n, d, xs_dev, t_starts_dev, ns, batch, ell, sf2, l_arena_dev, ldl,
                                          l_stride, ws_arena_dev, ws_stride_bytes, z_dev, q, bias_dev, noise_dev, w_arena_dev, ldw,
-                                         w_stride, mean_dev, var_dev, S(stream)));
+                                         w_stride, mean_dev, var_dev, S(stream), cov));
+}
+
+int cimrgp_layer_fit(int dtype, const void* x_dev, const void* y_dev, const void* fbar_dev, void* train_out_dev,
+                     const int64_t* starts_dev, int batch, int64_t n, int d, int q, double ell, double sf2, double noise_fixed,
+                     double noise_frac, double noise_floor, const void* shared_bias_dev, const void* shared_noise_dev,
+                     void* k_arena_dev, int64_t ldk, int64_t k_stride, void* ws_arena_dev, size_t ws_stride_bytes,
+                     int32_t* info_dev, void* rows_arena_dev, int64_t ldr, void* z_dev, void* alpha_dev, void* bias_dev,
+                     void* noise_dev, void* scratch_dev, void* stream)
+{
+    const char* fn = "cimrgp_layer_fit";
+    return layer_fit_impl(fn, dtype, CIMRGP_COV_RBF, x_dev, y_dev, fbar_dev, train_out_dev, starts_dev, batch, n, d, q, ell, sf2,
+                          noise_fixed, noise_frac, noise_floor, shared_bias_dev, shared_noise_dev, k_arena_dev, ldk, k_stride,
+                          ws_arena_dev, ws_stride_bytes, info_dev, rows_arena_dev, ldr, z_dev, alpha_dev, bias_dev, noise_dev,
+                          scratch_dev, stream);
+}
+
+int cimrgp_layer_fit_cov(int dtype, int cov, const void* x_dev, const void* y_dev, const void* fbar_dev, void* train_out_dev,
+                         const int64_t* starts_dev, int batch, int64_t n, int d, int q, double ell, double sf2, double noise_fixed,
+                         double noise_frac, double noise_floor, const void* shared_bias_dev, const void* shared_noise_dev,
+                         void* k_arena_dev, int64_t ldk, int64_t k_stride, void* ws_arena_dev, size_t ws_stride_bytes,
+                         int32_t* info_dev, void* rows_arena_dev, int64_t ldr, void* z_dev, void* alpha_dev, void* bias_dev,
+                         void* noise_dev, void* scratch_dev, void* stream)
+{
+    const char* fn = "cimrgp_layer_fit_cov";
+    CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
+    return layer_fit_impl(fn, dtype, cov, x_dev, y_dev, fbar_dev, train_out_dev, starts_dev, batch, n, d, q, ell, sf2,
+                          noise_fixed, noise_frac, noise_floor, shared_bias_dev, shared_noise_dev, k_arena_dev, ldk, k_stride,
+                          ws_arena_dev, ws_stride_bytes, info_dev, rows_arena_dev, ldr, z_dev, alpha_dev, bias_dev, noise_dev,
+                          scratch_dev, stream);
+}
+
+int cimrgp_layer_predict(int dtype, const void* x_dev, const int64_t* starts_dev, int64_t n, int d, const void* xs_dev,
+                         const int64_t* t_starts_dev, int64_t ns, int batch, double ell, double sf2, const void* l_arena_dev,
+                         int64_t ldl, int64_t l_stride, const void* ws_arena_dev, size_t ws_stride_bytes, const void* z_dev, int q,
+                         const void* bias_dev, const void* noise_dev, void* w_arena_dev, int64_t ldw, int64_t w_stride,
+                         void* mean_dev, void* var_dev, void* stream)
+{
+    const char* fn = "cimrgp_layer_predict";
+    return layer_predict_impl(fn, dtype, CIMRGP_COV_RBF, x_dev, starts_dev, n, d, xs_dev, t_starts_dev, ns, batch, ell, sf2,
+                              l_arena_dev, ldl, l_stride, ws_arena_dev, ws_stride_bytes, z_dev, q, bias_dev, noise_dev, w_arena_dev,
+                              ldw, w_stride, mean_dev, var_dev, stream);
+}
+
+int cimrgp_layer_predict_cov(int dtype, int cov, const void* x_dev, const int64_t* starts_dev, int64_t n, int d,
+                             const void* xs_dev, const int64_t* t_starts_dev, int64_t ns, int batch, double ell, double sf2,
+                             const void* l_arena_dev, int64_t ldl, int64_t l_stride, const void* ws_arena_dev,
+                             size_t ws_stride_bytes, const void* z_dev, int q, const void* bias_dev, const void* noise_dev,
+                             void* w_arena_dev, int64_t ldw, int64_t w_stride, void* mean_dev, void* var_dev, void* stream)
+{
+    const char* fn = "cimrgp_layer_predict_cov";
+    CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
+    return layer_predict_impl(fn, dtype, cov, x_dev, starts_dev, n, d, xs_dev, t_starts_dev, ns, batch, ell, sf2, l_arena_dev, ldl,
+                              l_stride, ws_arena_dev, ws_stride_bytes, z_dev, q, bias_dev, noise_dev, w_arena_dev, ldw, w_stride,
+                              mean_dev, var_dev, stream);
 }
 
 int cimrgp_set_rows_queues(int queues)

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <type_traits>
 
 #include "../../include/cimrgp.h"
 
@@ -240,14 +241,88 @@ int gemm_pers_head_tiles(int64_t m, int k, int elem_bytes);
 template <typename T> int gemm_nt_sub(T* c, int64_t ldc, const T* a, int64_t lda, const T* b, int64_t ldb,
                                       int64_t m, int64_t n, int k, bool lower, hipStream_t st, GemmBatch bt = GemmBatch());
 
-// gram.hip
+// ------------------------------------------------------ covariance policies ----
+// The stationary covariances of the dense path (CIMRGP_COV_*, include/cimrgp.h), as functions of the squared distance
+// d2 = sum_k (x_k - x'_k)^2.  `c` is the policy's scale, fixed on the host by cov_scale(): RBF -1 / (2 l^2) (the
+// expression the RBF kernels always used, so that their results stay bit-identical), Matern sqrt(2 nu) / l, so that
+// t = c r.  r = |df| for one input dimension, sqrt(d2) otherwise: d2 is a sum of squares, so it is exactly 0 on the
+// diagonal and never negative.
+static inline bool cov_known(int cov) { return cov >= CIMRGP_COV_RBF && cov <= CIMRGP_COV_MATERN52; }
+
+static inline double cov_scale(int cov, double ell)
+{
+    switch (cov) {
+        case CIMRGP_COV_MATERN12: return 1.0 / ell;
+        case CIMRGP_COV_MATERN32: return sqrt(3.0) / ell;
+        case CIMRGP_COV_MATERN52: return sqrt(5.0) / ell;
+        default: return -0.5 / (ell * ell);
+    }
+}
+
+// The one run-time -> compile-time dispatch over the policies: f(std::integral_constant<int, COV>) for the id `cov`
+// (validated by the entry points; anything else takes the RBF).
+template <typename F> static inline int with_cov(int cov, F&& f)
+{
+    switch (cov) {
+        case CIMRGP_COV_MATERN12: return f(std::integral_constant<int, CIMRGP_COV_MATERN12>());
+        case CIMRGP_COV_MATERN32: return f(std::integral_constant<int, CIMRGP_COV_MATERN32>());
+        case CIMRGP_COV_MATERN52: return f(std::integral_constant<int, CIMRGP_COV_MATERN52>());
+        default: return f(std::integral_constant<int, CIMRGP_COV_RBF>());
+    }
+}
+
+template <int COV> struct Cov;
+
+template <> struct Cov<CIMRGP_COV_RBF> {
+    template <typename T, int D> static __device__ __forceinline__ T value(T d2, T, T c, T sf2) { return sf2 * exp(d2 * c); }
+};
+
+// Matern policies: value(d2) and, for the gradient of the log marginal likelihood w.r.t. log l,
+//   dlogl = -r dk/dr  (isotropic: d k / d log l)
+//   ard   = -(dk/dr) / r  (per dimension with pre-scaled inputs: d k / d log l_k = ard * (x_k - x'_k)^2)
+// both finite at r = 0 except ard for nu = 1/2, which is defined as 0 there (every (x_k - x'_k)^2 is 0 too).
+template <int COV> struct MaternCov {
+    template <typename T> static __device__ __forceinline__ T poly(T t)
+    {
+        if (COV == CIMRGP_COV_MATERN12) return (T)1;
+        if (COV == CIMRGP_COV_MATERN32) return (T)1 + t;
+        return (T)1 + t + t * t * (T)(1.0 / 3.0);
+    }
+    template <typename T, int D> static __device__ __forceinline__ T radius(T d2, T df0) { return D == 1 ? fabs(df0) : sqrt(d2); }
+    template <typename T, int D> static __device__ __forceinline__ T value(T d2, T df0, T c, T sf2)
+    {
+        const T t = c * radius<T, D>(d2, df0);
+        return sf2 * poly(t) * exp(-t);
+    }
+    // t = c r, v = exp(-t)
+    template <typename T> static __device__ __forceinline__ T dlogl(T t, T v, T sf2)
+    {
+        if (COV == CIMRGP_COV_MATERN12) return sf2 * t * v;
+        if (COV == CIMRGP_COV_MATERN32) return sf2 * t * t * v;
+        return sf2 * t * t * ((T)1 + t) * v * (T)(1.0 / 3.0);
+    }
+    template <typename T> static __device__ __forceinline__ T ard(T t, T r, T v, T c, T sf2)
+    {
+        if (COV == CIMRGP_COV_MATERN12) return r > (T)0 ? sf2 * c * v / r : (T)0;
+        if (COV == CIMRGP_COV_MATERN32) return c * c * sf2 * v;
+        return c * c * sf2 * ((T)1 + t) * v * (T)(1.0 / 3.0);
+    }
+};
+template <> struct Cov<CIMRGP_COV_MATERN12> : MaternCov<CIMRGP_COV_MATERN12> {};
+template <> struct Cov<CIMRGP_COV_MATERN32> : MaternCov<CIMRGP_COV_MATERN32> {};
+template <> struct Cov<CIMRGP_COV_MATERN52> : MaternCov<CIMRGP_COV_MATERN52> {};
+
+// gram.hip.  cov: CIMRGP_COV_* (validated by the caller); fn: the entry point named in error messages (NULL: the RBF
+// entry point's name)
 template <typename T> int rbf_gram_run(const T* xa, int64_t na, const T* xb, int64_t nb, int d, double ell, double sf2,
-                                       double diag_add, T* k, int64_t ld, bool symm, bool lower_only, hipStream_t st);
+                                       double diag_add, T* k, int64_t ld, bool symm, bool lower_only, hipStream_t st,
+                                       int cov = CIMRGP_COV_RBF, const char* fn = nullptr);
 template <typename T> int rbf_gram_batched_run(const T* xa, const int64_t* a_starts, int64_t na, const T* xb, const int64_t* b_starts,
                                                int64_t nb, int d, double ell, double sf2, const T* diag_dev, T* k, int64_t ld,
-                                               int64_t kstride, int batch, bool symm, hipStream_t st);
+                                               int64_t kstride, int batch, bool symm, hipStream_t st, int cov = CIMRGP_COV_RBF);
 template <typename T> int predict_mean_run(const T* x, int64_t n, int d, const T* alpha, int q, const T* xs, int64_t ns,
-                                           double ell, double sf2, const T* bias, T* mean, int accumulate, hipStream_t st);
+                                           double ell, double sf2, const T* bias, T* mean, int accumulate, hipStream_t st,
+                                           int cov = CIMRGP_COV_RBF, const char* fn = nullptr);
 // solve.hip
 template <typename T> int potrs_run(const T* l, int64_t n, int64_t ld, const T* ws, T* rhs, int q, T* z_out, T* scratch,
                                     bool backward_only, hipStream_t st, PotrfBatch bt = PotrfBatch(), bool work_ready = false);
@@ -264,13 +339,14 @@ template <typename T> int misc_noise_from_stats(const T* stats, int q, double fr
 template <typename T> int misc_logdet_half(const T* l, int64_t n, int64_t ld, double* out, hipStream_t st);
 template <typename T> int lml_grad_run(const T* x, int64_t n, int d, const T* kinv, int64_t ld, const T* alpha, int q,
                                        double ell, double sf2, double noise, double* out3, double* scratch, hipStream_t st,
-                                       bool ard = false);
+                                       bool ard = false, int cov = CIMRGP_COV_RBF, const char* fn = nullptr);
 
 // layer.hip: one call per layer for a batch of equal-sized blocks (strides in elements)
 template <typename T> struct LayerFit {
     const T* x; const T* y; const T* fbar; T* train_out; const int64_t* starts;
     int batch; int64_t n; int d; int q;
     double ell, sf2, noise_fixed, noise_frac, noise_floor;
+    int cov = CIMRGP_COV_RBF;
     const T* shared_bias; const T* shared_noise;
     T* k; int64_t ldk, sk; T* ws; int64_t sws; int32_t* info;
     T* rows; int64_t ldr, srows;
@@ -281,6 +357,7 @@ template <typename T> struct LayerPredict {
     const T* x; const int64_t* starts; int64_t n; int d;
     const T* xs; const int64_t* t_starts; int64_t ns; int batch;
     double ell, sf2;
+    int cov = CIMRGP_COV_RBF;
     const T* l; int64_t ldl, sl; const T* ws; int64_t sws;
     const T* z; int q; const T* bias; const T* noise;
     T* w; int64_t ldw, sw;

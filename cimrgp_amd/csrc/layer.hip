@@ -7,6 +7,8 @@
 //   fit      statistics -> bias, noise | residual rows | Gram + noise | factorisation with the residual
 //            rows carried (z = L^-1 r) | backward solve (alpha) | training-point prediction
 //   predict  cross-Gram | row-wise solve W = K* L^-T | mean = W z + bias, var = sf - sum W^2 (+ noise)
+// The Gram and cross-Gram take the layer's covariance policy (a.cov, CIMRGP_COV_*); k(0) = sf for every policy, so
+// the variance is the same expression for all of them.
 //
 // Round 2 issued five launches per block from a Python loop for the front end and one row-wise solve
 // per block for the prediction: a layer of 128 blocks of 2048 points was launch-bound (22 ms for 0.37
@@ -141,7 +143,7 @@ int layer_fit_run(const LayerFit<T>& a, hipStream_t st)
                        (const T*)a.bias, a.rows, a.ldr, a.srows);
     CIMRGP_LAUNCH_CHECK(fn);
     int rc = rbf_gram_batched_run<T>(a.x, a.starts, a.n, a.x, a.starts, a.n, a.d, a.ell, a.sf2, (const T*)a.noise, a.k, a.ldk,
-                                     a.sk, a.batch, true, st);
+                                     a.sk, a.batch, true, st, a.cov);
     if (rc) return rc;
     PotrfBatch bt;
     bt.count = a.batch;
@@ -171,7 +173,7 @@ int layer_predict_run(const LayerPredict<T>& a, hipStream_t st)
     CIMRGP_REQUIRE(a.ldw >= a.n, fn, "leading dimension of W smaller than n");
     // W_b = K(xs_b, x_b)
     int rc = rbf_gram_batched_run<T>(a.xs, a.t_starts, a.ns, a.x, a.starts, a.n, a.d, a.ell, a.sf2, (const T*)nullptr, a.w, a.ldw,
-                                     a.sw, a.batch, false, st);
+                                     a.sw, a.batch, false, st, a.cov);
     if (rc) return rc;
     // W_b <- W_b L_b^-T
     PotrfBatch bt;

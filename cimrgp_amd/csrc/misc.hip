@@ -188,6 +188,8 @@ CIMRGP_INST(float)
 // One pass over the LOWER triangle of K^-1 (off-diagonal entries count twice); the kernel
 // matrix is re-evaluated on the fly from X, nothing n x n besides K^-1 is read.  Per-tile
 // partial sums, then a fixed-order final reduction (deterministic).
+// The Matern policies (common.hpp) replace sf E_ij by k_ij and sf E_ij d2_ij / l^2 by their
+// d k / d log l (k_cov_lml_grad_tiles<T, COV, ARD>; the RBF instance keeps its name).
 // ---------------------------------------------------------------------------
 namespace cimrgp {
 namespace {
@@ -283,6 +285,110 @@ void k_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict
     }
 }
 
+// The Matern policies' tile: k_lml_grad_tiles' staging and reductions with k_ij and d k_ij / d log l of policy COV.
+// (The RBF kernel above keeps its own body, so that its code -- and its FP32 contraction of d2 -- stays as it was.)
+// c = cov_scale(COV, l); inv_l2 is not read.
+template <typename T, int COV, bool ARD>
+static __device__ __forceinline__ void lml_grad_tile(const T* __restrict__ x, int n, int d, const T* __restrict__ kinv, int64_t ld,
+                                                     const T* __restrict__ alpha, int q, T c, T sf2, T inv_l2,
+                                                     double* __restrict__ partial)
+{
+    static_assert(COV != CIMRGP_COV_RBF, "the RBF gradient is k_lml_grad_tiles");
+    (void)inv_l2;
+    __shared__ T sa[LG_T * LG_MAXD], sb[LG_T * LG_MAXD];
+    __shared__ T aa[LG_T * 8], ab[LG_T * 8];
+    __shared__ double red[ARD ? LG_NP : 3][4];
+    const int id = blockIdx.x;
+    int ti = (int)((sqrtf(8.0f * (float)id + 1.0f) - 1.0f) * 0.5f);
+    while (ti * (ti + 1) / 2 > id) --ti;
+    while ((ti + 1) * (ti + 2) / 2 <= id) ++ti;
+    const int tj = id - ti * (ti + 1) / 2;
+    const int row0 = ti * LG_T, col0 = tj * LG_T;
+    const int tid = threadIdx.x;
+    for (int e = tid; e < LG_T * LG_MAXD; e += 256) {
+        const int r = e / LG_MAXD, k = e - r * LG_MAXD;
+        sa[e] = (k < d && row0 + r < n) ? x[(int64_t)(row0 + r) * d + k] : (T)0;
+        sb[e] = (k < d && col0 + r < n) ? x[(int64_t)(col0 + r) * d + k] : (T)0;
+        aa[e] = (k < q && row0 + r < n) ? alpha[(int64_t)(row0 + r) * q + k] : (T)0;
+        ab[e] = (k < q && col0 + r < n) ? alpha[(int64_t)(col0 + r) * q + k] : (T)0;
+    }
+    __syncthreads();
+    const int tx = tid & 63, ty = tid >> 6;
+    double s_sf = 0.0, s_l = 0.0, s_tr = 0.0;
+    double s_lk[ARD ? LG_MAXD : 1];
+#pragma unroll
+    for (int k = 0; k < (ARD ? LG_MAXD : 1); ++k) s_lk[k] = 0.0;
+    const int gc = col0 + tx;
+    for (int rr = ty; rr < LG_T; rr += 4) {
+        const int gr = row0 + rr;
+        if (gr < n && gc < n && gc <= gr) {
+            T d2 = (T)0;
+            T dk2[LG_MAXD];
+#pragma unroll
+            for (int k = 0; k < LG_MAXD; ++k) {
+                const T df = sa[rr * LG_MAXD + k] - sb[tx * LG_MAXD + k];
+                dk2[k] = df * df;
+                d2 += dk2[k];
+            }
+            T aat = (T)0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) aat += aa[rr * 8 + k] * ab[tx * 8 + k];
+            const T g = aat - (T)q * kinv[(int64_t)gr * ld + gc];
+            const double wgt = (gr == gc) ? 1.0 : 2.0;
+            // r from d2 (a sum of squares: exactly 0 on the diagonal); d = 1 takes |df| as the Gram kernels do
+            const T r = d == 1 ? fabs(sa[rr * LG_MAXD] - sb[tx * LG_MAXD]) : sqrt(d2);
+            const T t = c * r, v = exp(-t);
+            const T kf = sf2 * Cov<COV>::poly(t) * v;
+            s_sf += wgt * (double)(g * kf);
+            if (ARD) {
+                const T gk = g * Cov<COV>::ard(t, r, v, c, sf2);
+#pragma unroll
+                for (int k = 0; k < LG_MAXD; ++k) s_lk[k] += wgt * (double)(gk * dk2[k]);
+            } else {
+                s_l  += wgt * (double)(g * Cov<COV>::dlogl(t, v, sf2));
+            }
+            if (gr == gc) s_tr += (double)g;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s_sf += __shfl_xor(s_sf, off, 64);
+        s_l  += __shfl_xor(s_l, off, 64);
+        s_tr += __shfl_xor(s_tr, off, 64);
+        if (ARD) {
+#pragma unroll
+            for (int k = 0; k < LG_MAXD; ++k) s_lk[k] += __shfl_xor(s_lk[k], off, 64);
+        }
+    }
+    if (ARD) {
+        if (tx == 0) {
+            red[0][ty] = s_sf;
+#pragma unroll
+            for (int k = 0; k < LG_MAXD; ++k) red[1 + k][ty] = s_lk[k];
+            red[LG_NP - 1][ty] = s_tr;
+        }
+        __syncthreads();
+        if (tid < LG_NP) partial[(int64_t)id * LG_NP + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+    } else {
+        if (tx == 0) { red[0][ty] = s_sf; red[1][ty] = s_l; red[2][ty] = s_tr; }
+        __syncthreads();
+        if (tid < 3) partial[(int64_t)id * 3 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+    }
+}
+
+template <typename T, int COV, bool ARD>
+__global__ __launch_bounds__(256)
+void k_cov_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict__ kinv, int64_t ld,
+                          const T* __restrict__ alpha, int q, T c, T sf2, T inv_l2, double* __restrict__ partial)
+{
+    lml_grad_tile<T, COV, ARD>(x, n, d, kinv, ld, alpha, q, c, sf2, inv_l2, partial);
+}
+
+template <typename T, int COV, bool ARD> static auto lml_grad_kernel()
+{
+    if constexpr (COV == CIMRGP_COV_RBF) return k_lml_grad_tiles<T, ARD>; else return k_cov_lml_grad_tiles<T, COV, ARD>;
+}
+
 __global__ __launch_bounds__(1024)
 void k_lml_grad_final(const double* __restrict__ partial, int64_t ntiles, double noise, double* __restrict__ out,
                       int np, int nout)
@@ -301,11 +407,11 @@ void k_lml_grad_final(const double* __restrict__ partial, int64_t ntiles, double
 
 }  // namespace
 
-template <typename T>
-int lml_grad_run(const T* x, int64_t n, int d, const T* kinv, int64_t ld, const T* alpha, int q,
-                 double ell, double sf2, double noise, double* out3, double* scratch, hipStream_t st, bool ard)
+template <typename T, int COV>
+static int lml_grad_run_cov(const T* x, int64_t n, int d, const T* kinv, int64_t ld, const T* alpha, int q,
+                            double ell, double sf2, double noise, double* out3, double* scratch, hipStream_t st, bool ard,
+                            const char* fn)
 {
-    const char* fn = "cimrgp_lml_grad";
     CIMRGP_REQUIRE(n > 0 && n < (1ll << 30), fn, "bad size");
     CIMRGP_REQUIRE(d >= 1 && d <= LG_MAXD, fn, "input dimension must be in [1, 8]");
     CIMRGP_REQUIRE(q >= 1 && q <= 8, fn, "number of outputs must be in [1, 8]");
@@ -313,13 +419,13 @@ int lml_grad_run(const T* x, int64_t n, int d, const T* kinv, int64_t ld, const 
     CIMRGP_REQUIRE(tiles < (1ll << 31), fn, "grid too large");
     if (ard) {
         // inputs are pre-scaled by the length-scales: unit length-scale here; out = [sf | l_1..l_d | noise]
-        hipLaunchKernelGGL((k_lml_grad_tiles<T, true>), dim3((unsigned)tiles), dim3(256), 0, st, x, (int)n, d, kinv, ld, alpha, q,
-                           (T)(-0.5), (T)sf2, (T)1, scratch);
+        hipLaunchKernelGGL((lml_grad_kernel<T, COV, true>()), dim3((unsigned)tiles), dim3(256), 0, st, x, (int)n, d, kinv, ld, alpha, q,
+                           (T)cov_scale(COV, 1.0), (T)sf2, (T)1, scratch);
         CIMRGP_LAUNCH_CHECK(fn);
         hipLaunchKernelGGL(k_lml_grad_final, dim3(1), dim3(1024), 0, st, (const double*)scratch, tiles, noise, out3, LG_NP, d + 2);
     } else {
-        hipLaunchKernelGGL((k_lml_grad_tiles<T, false>), dim3((unsigned)tiles), dim3(256), 0, st, x, (int)n, d, kinv, ld, alpha, q,
-                           (T)(-0.5 / (ell * ell)), (T)sf2, (T)(1.0 / (ell * ell)), scratch);
+        hipLaunchKernelGGL((lml_grad_kernel<T, COV, false>()), dim3((unsigned)tiles), dim3(256), 0, st, x, (int)n, d, kinv, ld, alpha, q,
+                           (T)cov_scale(COV, ell), (T)sf2, (T)(1.0 / (ell * ell)), scratch);
         CIMRGP_LAUNCH_CHECK(fn);
         hipLaunchKernelGGL(k_lml_grad_final, dim3(1), dim3(1024), 0, st, (const double*)scratch, tiles, noise, out3, 3, 3);
     }
@@ -327,9 +433,19 @@ int lml_grad_run(const T* x, int64_t n, int d, const T* kinv, int64_t ld, const 
     return 0;
 }
 
+template <typename T>
+int lml_grad_run(const T* x, int64_t n, int d, const T* kinv, int64_t ld, const T* alpha, int q,
+                 double ell, double sf2, double noise, double* out3, double* scratch, hipStream_t st, bool ard, int cov, const char* fn)
+{
+    if (!fn) fn = "cimrgp_lml_grad";
+    return with_cov(cov, [&](auto c) {
+        return lml_grad_run_cov<T, decltype(c)::value>(x, n, d, kinv, ld, alpha, q, ell, sf2, noise, out3, scratch, st, ard, fn);
+    });
+}
+
 template int lml_grad_run<double>(const double*, int64_t, int, const double*, int64_t, const double*, int, double, double,
-                                  double, double*, double*, hipStream_t, bool);
+                                  double, double*, double*, hipStream_t, bool, int, const char*);
 template int lml_grad_run<float>(const float*, int64_t, int, const float*, int64_t, const float*, int, double, double,
-                                 double, double*, double*, hipStream_t, bool);
+                                 double, double*, double*, hipStream_t, bool, int, const char*);
 
 }  // namespace cimrgp

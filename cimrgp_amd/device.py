@@ -68,24 +68,43 @@ def to_device(a, dtype, device):
     return t.to(device=device, dtype=dtype).contiguous()
 
 
-def rbf_gram(x, ell, sf2, diag_add=0.0, lower_only=False, out=None):
-    """D1.  x: (n x d) device tensor.  Returns the (n x ld) buffer; [:, :n] is K."""
+def _cov_id(cov):
+    cov = int(cov)
+    if cov not in (_lib.COV_RBF, _lib.COV_MATERN12, _lib.COV_MATERN32, _lib.COV_MATERN52):
+        raise ValueError("unknown covariance id %d (include/cimrgp.h CIMRGP_COV_*)" % cov)
+    return cov
+
+
+def rbf_gram(x, ell, sf2, diag_add=0.0, lower_only=False, out=None, cov=_lib.COV_RBF):
+    """D1.  x: (n x d) device tensor.  Returns the (n x ld) buffer; [:, :n] is K.
+    ``cov``: covariance id (``_lib.COV_*``, a kernel object's ``.cov``); the RBF goes through the
+    original entry point (cimrgp_rbf_gram), the Matern ones through cimrgp_cov_gram."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
     n, d = x.shape
     if out is None:
         out = alloc_matrix(n, n, x.dtype, x.device)
     lib = _lib.load()
+    if cov != _lib.COV_RBF:
+        _lib.check(lib.cimrgp_cov_gram(_DT[x.dtype], cov, _p(x), n, d, float(ell), float(sf2), float(diag_add),
+                                       _p(out), out.stride(0), int(bool(lower_only)), _stream()), "cimrgp_cov_gram")
+        return out
     _lib.check(lib.cimrgp_rbf_gram(_DT[x.dtype], _p(x), n, d, float(ell), float(sf2), float(diag_add),
                                    _p(out), out.stride(0), int(bool(lower_only)), _stream()), "cimrgp_rbf_gram")
     return out
 
 
-def rbf_cross(xa, xb, ell, sf2, out=None):
-    """Cross-Gram (na x nb) into a padded buffer."""
+def rbf_cross(xa, xb, ell, sf2, out=None, cov=_lib.COV_RBF):
+    """Cross-Gram (na x nb) into a padded buffer; ``cov`` as for :func:`rbf_gram`."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
     na, d = xa.shape
     nb = xb.shape[0]
     if out is None:
         out = alloc_matrix(na, nb, xa.dtype, xa.device)
     lib = _lib.load()
+    if cov != _lib.COV_RBF:
+        _lib.check(lib.cimrgp_cov_cross(_DT[xa.dtype], cov, _p(xa), na, _p(xb), nb, d, float(ell), float(sf2),
+                                        _p(out), out.stride(0), _stream()), "cimrgp_cov_cross")
+        return out
     _lib.check(lib.cimrgp_rbf_cross(_DT[xa.dtype], _p(xa), na, _p(xb), nb, d, float(ell), float(sf2),
                                     _p(out), out.stride(0), _stream()), "cimrgp_rbf_cross")
     return out
@@ -226,17 +245,26 @@ def _layer_work_areas(batch, q, n, ldr, dtype, device):
 
 
 def layer_fit(x, y, fbar, train_out, starts, n, ell, sf2, noise_fixed, noise_frac, noise_floor, shared_bias, shared_noise,
-              karena, ws_arena, info, bias, noise, z, alpha):
-    """The fit of ``batch`` equal-sized blocks of one layer in ONE call (cimrgp_layer_fit, include/cimrgp.h).
+              karena, ws_arena, info, bias, noise, z, alpha, cov=_lib.COV_RBF):
+    """The fit of ``batch`` equal-sized blocks of one layer in ONE call (cimrgp_layer_fit, include/cimrgp.h;
+    cimrgp_layer_fit_cov for a Matern ``cov``).
     x, y, fbar, train_out: the LAYER's arrays (N x d / N x q); starts: device int64 (batch,) row offsets.
     karena (batch, n, ld), ws_arena (batch, ws_bytes) uint8, info (batch,) int32, bias (batch, q), noise (batch,),
     z / alpha (batch, n, q) are filled.  noise_fixed < 0: from the statistics (or ``shared_noise``)."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
     lib = _lib.load()
     batch = int(karena.shape[0])
     q = int(y.shape[1])
     d = int(x.shape[1])
     ldr = padded_ld(n)
     rows, scratch = _layer_work_areas(batch, q, int(n), ldr, y.dtype, y.device)
+    if cov != _lib.COV_RBF:
+        _lib.check(lib.cimrgp_layer_fit_cov(_DT[y.dtype], cov, _p(x), _p(y), _p(fbar), _p(train_out), _p(starts), batch, int(n), d,
+                                            q, float(ell), float(sf2), float(noise_fixed), float(noise_frac), float(noise_floor),
+                                            _p(shared_bias), _p(shared_noise), _p(karena), karena.stride(1), karena.stride(0),
+                                            _p(ws_arena), ws_arena.stride(0), _p(info), _p(rows), ldr, _p(z), _p(alpha), _p(bias),
+                                            _p(noise), _p(scratch), _stream()), "cimrgp_layer_fit_cov")
+        return
     _lib.check(lib.cimrgp_layer_fit(_DT[y.dtype], _p(x), _p(y), _p(fbar), _p(train_out), _p(starts), batch, int(n), d, q,
                                     float(ell), float(sf2), float(noise_fixed), float(noise_frac), float(noise_floor),
                                     _p(shared_bias), _p(shared_noise), _p(karena), karena.stride(1), karena.stride(0),
@@ -244,14 +272,22 @@ def layer_fit(x, y, fbar, train_out, starts, n, ell, sf2, noise_fixed, noise_fra
                                     _p(noise), _p(scratch), _stream()), "cimrgp_layer_fit")
 
 
-def layer_predict(x, starts, n, xs, t_starts, ns, ell, sf2, larena, ws_arena, z, bias, noise, mean, var):
+def layer_predict(x, starts, n, xs, t_starts, ns, ell, sf2, larena, ws_arena, z, bias, noise, mean, var, cov=_lib.COV_RBF):
     """Predictive mean and variance of ``batch`` equal-sized blocks at ``ns`` test points each in ONE call
     (cimrgp_layer_predict): accumulates into mean (N* x q) / var (N*,) at rows t_starts[b] ...; ``noise``
     (batch,) or None is added to the variance."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
     lib = _lib.load()
     batch = int(larena.shape[0])
     ldw = padded_ld(n)
     w = torch.empty((batch, max(int(ns), 1), ldw), dtype=x.dtype, device=x.device)
+    if cov != _lib.COV_RBF:
+        _lib.check(lib.cimrgp_layer_predict_cov(_DT[x.dtype], cov, _p(x), _p(starts), int(n), int(x.shape[1]), _p(xs), _p(t_starts),
+                                                int(ns), batch, float(ell), float(sf2), _p(larena), larena.stride(1),
+                                                larena.stride(0), _p(ws_arena), ws_arena.stride(0), _p(z), int(z.shape[2]), _p(bias),
+                                                _p(noise), _p(w), ldw, w.stride(0), _p(mean), _p(var), _stream()),
+                   "cimrgp_layer_predict_cov")
+        return
     _lib.check(lib.cimrgp_layer_predict(_DT[x.dtype], _p(x), _p(starts), int(n), int(x.shape[1]), _p(xs), _p(t_starts), int(ns),
                                         batch, float(ell), float(sf2), _p(larena), larena.stride(1), larena.stride(0),
                                         _p(ws_arena), ws_arena.stride(0), _p(z), int(z.shape[2]), _p(bias), _p(noise),
@@ -308,8 +344,9 @@ def trsm_rows(lbuf, n, ws, bbuf, m):
     return bbuf
 
 
-def predict_mean(x, alpha, xs, ell, sf2, bias=None, out=None, accumulate=False):
-    """D4 fused mean: out (ns x q) (+)= bias + K(xs, x) alpha."""
+def predict_mean(x, alpha, xs, ell, sf2, bias=None, out=None, accumulate=False, cov=_lib.COV_RBF):
+    """D4 fused mean: out (ns x q) (+)= bias + K(xs, x) alpha; ``cov`` as for :func:`rbf_gram`."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
     lib = _lib.load()
     n, d = x.shape
     ns = xs.shape[0]
@@ -317,6 +354,11 @@ def predict_mean(x, alpha, xs, ell, sf2, bias=None, out=None, accumulate=False):
     if out is None:
         out = torch.empty((ns, q), dtype=x.dtype, device=x.device)
         accumulate = False
+    if cov != _lib.COV_RBF:
+        _lib.check(lib.cimrgp_cov_predict_mean(_DT[x.dtype], cov, _p(x), n, d, _p(alpha), q, _p(xs), ns, float(ell),
+                                               float(sf2), _p(bias), _p(out), int(bool(accumulate)), _stream()),
+                   "cimrgp_cov_predict_mean")
+        return out
     _lib.check(lib.cimrgp_predict_mean(_DT[x.dtype], _p(x), n, d, _p(alpha), q, _p(xs), ns, float(ell),
                                        float(sf2), _p(bias), _p(out), int(bool(accumulate)), _stream()),
                "cimrgp_predict_mean")
@@ -392,23 +434,35 @@ def syrk_lower(cbuf, abuf, n, k):
     return cbuf
 
 
-def lml_grad(x, kinv, n, alpha, ell, sf2, noise):
+def lml_grad(x, kinv, n, alpha, ell, sf2, noise, cov=_lib.COV_RBF):
     """Gradient of the log marginal likelihood w.r.t. (log sf, log l, log noise): device float64[3]."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
     lib = _lib.load()
     out = torch.empty(3, dtype=torch.float64, device=x.device)
     scratch = torch.empty(max(lib.cimrgp_lml_grad_scratch_bytes(int(n)), 8) // 8, dtype=torch.float64, device=x.device)
+    if cov != _lib.COV_RBF:
+        _lib.check(lib.cimrgp_cov_lml_grad(_DT[x.dtype], cov, _p(x), int(n), x.shape[1], _p(kinv), kinv.stride(0), _p(alpha),
+                                           alpha.shape[1], float(ell), float(sf2), float(noise), _p(out), _p(scratch), _stream()),
+                   "cimrgp_cov_lml_grad")
+        return out
     _lib.check(lib.cimrgp_lml_grad(_DT[x.dtype], _p(x), int(n), x.shape[1], _p(kinv), kinv.stride(0), _p(alpha),
                                    alpha.shape[1], float(ell), float(sf2), float(noise), _p(out), _p(scratch), _stream()),
                "cimrgp_lml_grad")
     return out
 
 
-def lml_grad_ard(x_scaled, kinv, n, alpha, sf2, noise):
+def lml_grad_ard(x_scaled, kinv, n, alpha, sf2, noise, cov=_lib.COV_RBF):
     """ARD gradient w.r.t. (log sf, log l_1..l_d, log noise); ``x_scaled`` = inputs / length-scales."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
     lib = _lib.load()
     d = x_scaled.shape[1]
     out = torch.empty(d + 2, dtype=torch.float64, device=x_scaled.device)
     scratch = torch.empty(max(lib.cimrgp_lml_grad_scratch_bytes(int(n)), 8) // 8, dtype=torch.float64, device=x_scaled.device)
+    if cov != _lib.COV_RBF:
+        _lib.check(lib.cimrgp_cov_lml_grad_ard(_DT[x_scaled.dtype], cov, _p(x_scaled), int(n), d, _p(kinv), kinv.stride(0),
+                                               _p(alpha), alpha.shape[1], float(sf2), float(noise), _p(out), _p(scratch),
+                                               _stream()), "cimrgp_cov_lml_grad_ard")
+        return out
     _lib.check(lib.cimrgp_lml_grad_ard(_DT[x_scaled.dtype], _p(x_scaled), int(n), d, _p(kinv), kinv.stride(0), _p(alpha),
                                        alpha.shape[1], float(sf2), float(noise), _p(out), _p(scratch), _stream()),
                "cimrgp_lml_grad_ard")

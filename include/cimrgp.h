@@ -36,6 +36,17 @@ extern "C" {
 
 enum { CIMRGP_F32 = 0, CIMRGP_F64 = 1 };
 
+/* Covariance of the cimrgp_cov_* / cimrgp_layer_*_cov entry points, with r = |x - x'| and t = sqrt(2 nu) r / ell:
+ *   RBF        sf2 exp(-r^2 / (2 ell^2))     (the covariance of every other entry point)
+ *   MATERN12   sf2 exp(-t)                   (nu = 1/2, the exponential covariance)
+ *   MATERN32   sf2 (1 + t) exp(-t)           (nu = 3/2)
+ *   MATERN52   sf2 (1 + t + t^2 / 3) exp(-t) (nu = 5/2)
+ * sf2 is the signal variance (k(0) = sf2 for all four). */
+#define CIMRGP_COV_RBF      0
+#define CIMRGP_COV_MATERN12 1
+#define CIMRGP_COV_MATERN32 2
+#define CIMRGP_COV_MATERN52 3
+
 /* *info_dev values other than LAPACK's: CIMRGP_INFO_WATCHDOG = the factorisation's internal schedule
  * gave up waiting for one of its own kernels (a bounded device-side wait of 2 s expired: the panel chain
  * waits for tiles of the trailing update through a device counter).  It says nothing about the matrix;
@@ -66,6 +77,17 @@ int cimrgp_rbf_gram(int dtype, const void* x_dev, int64_t n, int d,
 /* Cross-Gram  Kab[a][b] = k(xa_a, xb_b),  (na x nb) row-major, ld >= nb.
  * Replaces kern.K(X*, X) inside GPy's predict (RegressionInput.py:66-67). */
 int cimrgp_rbf_cross(int dtype, const void* xa_dev, int64_t na,
+                     const void* xb_dev, int64_t nb, int d,
+                     double ell, double sf2,
+                     void* kab_dev, int64_t ld, void* stream);
+
+/* The Gram and cross-Gram of covariance `cov` (CIMRGP_COV_*): the arguments of cimrgp_rbf_gram /
+ * cimrgp_rbf_cross with `cov` after dtype.  cov = CIMRGP_COV_RBF gives bit-identical results to those;
+ * an unknown cov is rejected before any device work ("unknown covariance"). */
+int cimrgp_cov_gram(int dtype, int cov, const void* x_dev, int64_t n, int d,
+                    double ell, double sf2, double diag_add,
+                    void* k_dev, int64_t ldk, int lower_only, void* stream);
+int cimrgp_cov_cross(int dtype, int cov, const void* xa_dev, int64_t na,
                      const void* xb_dev, int64_t nb, int d,
                      double ell, double sf2,
                      void* kab_dev, int64_t ld, void* stream);
@@ -200,6 +222,12 @@ int cimrgp_predict_mean(int dtype, const void* x_dev, int64_t n, int d,
                         const void* xs_dev, int64_t ns,
                         double ell, double sf2, const void* bias_dev,
                         void* mean_dev, int accumulate, void* stream);
+/* The same with covariance `cov` (CIMRGP_COV_*). */
+int cimrgp_cov_predict_mean(int dtype, int cov, const void* x_dev, int64_t n, int d,
+                            const void* alpha_dev, int q,
+                            const void* xs_dev, int64_t ns,
+                            double ell, double sf2, const void* bias_dev,
+                            void* mean_dev, int accumulate, void* stream);
 
 /* ---- D5 tail: from W = K(X*,X) L^-T  (ns x n, after cimrgp_trsm_rows) ------
  *   var[i]     (+)= sf2 + extra_var + extra_var_dev[0] - sum_j W[i][j]^2
@@ -268,6 +296,18 @@ int cimrgp_lml_grad_ard(int dtype, const void* xs_dev, int64_t n, int d,
                         const void* kinv_dev, int64_t ldk, const void* alpha_dev, int q,
                         double sf2, double noise, double* out_dev,
                         double* scratch_dev, void* stream);
+/* Both gradients for covariance `cov` (CIMRGP_COV_*): sf E_ij above becomes k_ij and the length-scale term
+ * d k_ij / d log l, which for the Matern covariances is, with t = sqrt(2 nu) r / l and v = exp(-t),
+ *   nu = 1/2: sf2 t v    nu = 3/2: sf2 t^2 v    nu = 5/2: sf2 t^2 (1 + t) v / 3
+ * and per dimension (ARD, pre-scaled inputs, l = 1) -(dk/dr) / r * (x_k - x'_k)^2, taken as 0 at r = 0. */
+int cimrgp_cov_lml_grad(int dtype, int cov, const void* x_dev, int64_t n, int d,
+                        const void* kinv_dev, int64_t ldk, const void* alpha_dev, int q,
+                        double ell, double sf2, double noise, double* out_dev,
+                        double* scratch_dev, void* stream);
+int cimrgp_cov_lml_grad_ard(int dtype, int cov, const void* xs_dev, int64_t n, int d,
+                            const void* kinv_dev, int64_t ldk, const void* alpha_dev, int q,
+                            double sf2, double noise, double* out_dev,
+                            double* scratch_dev, void* stream);
 
 /* ---- reduced-rank (Laplacian basis) block path of the reference, SURVEY.md 8f rank 2 ----
  * Phi (n x m row-major, ld = m):  phi_i(x) = prod_k L_k^-1/2 sin(pi i (x_k + L_k)/(2 L_k)),
@@ -338,6 +378,25 @@ int cimrgp_layer_predict(int dtype, const void* x_dev, const int64_t* starts_dev
                          const void* bias_dev, const void* noise_dev, void* w_arena_dev,
                          int64_t ldw, int64_t w_stride, void* mean_dev, void* var_dev,
                          void* stream);
+/* The same two calls with covariance `cov` (CIMRGP_COV_*) for K_b and K(xs_b, x_b); k(0) = sf2 for every
+ * covariance, so the variance is unchanged in form. */
+int cimrgp_layer_fit_cov(int dtype, int cov, const void* x_dev, const void* y_dev,
+                         const void* fbar_dev, void* train_out_dev, const int64_t* starts_dev,
+                         int batch, int64_t n, int d, int q, double ell, double sf2,
+                         double noise_fixed, double noise_frac, double noise_floor,
+                         const void* shared_bias_dev, const void* shared_noise_dev,
+                         void* k_arena_dev, int64_t ldk, int64_t k_stride, void* ws_arena_dev,
+                         size_t ws_stride_bytes, int32_t* info_dev, void* rows_arena_dev,
+                         int64_t ldr, void* z_dev, void* alpha_dev, void* bias_dev,
+                         void* noise_dev, void* scratch_dev, void* stream);
+int cimrgp_layer_predict_cov(int dtype, int cov, const void* x_dev, const int64_t* starts_dev,
+                             int64_t n, int d, const void* xs_dev, const int64_t* t_starts_dev,
+                             int64_t ns, int batch, double ell, double sf2,
+                             const void* l_arena_dev, int64_t ldl, int64_t l_stride,
+                             const void* ws_arena_dev, size_t ws_stride_bytes, const void* z_dev,
+                             int q, const void* bias_dev, const void* noise_dev,
+                             void* w_arena_dev, int64_t ldw, int64_t w_stride, void* mean_dev,
+                             void* var_dev, void* stream);
 
 /* ---- the path's collective ------------------------------------
  * The blocks of a resolution are independent and shard over the GPUs of a node, one process per GPU; what is
