@@ -67,6 +67,8 @@ class MultiResolutionGaussianProcess(object):
         if cls is MultiResolutionGaussianProcess:
             basis = kwargs.get('basis_function_obj', args[3] if len(args) > 3 else None)
             if basis is not None:
+                if kwargs.get('optimize_hyperparameters', args[24] if len(args) > 24 else False):
+                    raise TypeError('not yet supported')
                 from .ReducedRank import ReducedRankMRGP
                 return object.__new__(ReducedRankMRGP)
         return object.__new__(cls)
@@ -93,7 +95,20 @@ class MultiResolutionGaussianProcess(object):
                  dtype='f64',
                  device=None,
                  process_group=None,
-                 keep_factors=True):
+                 keep_factors=True,
+                 optimize_hyperparameters=False,
+                 max_iters=1000):
+        """``optimize_hyperparameters=True``: before each layer is fitted, its (variance, length-scale, noise) are learned
+        by L-BFGS-B on the sum over its regions of the log marginal likelihood of the layer's residual targets (see
+        :meth:`_learn_layer`); at most ``max_iters`` iterations per layer.  Only for the dense blocks (no
+        ``basis_function_obj``)."""
+        if optimize_hyperparameters and basis_function_obj is not None:
+            raise TypeError('not yet supported')
+        if int(max_iters) < 1:
+            raise ValueError('max_iters must be at least 1')
+        self.optimize_hyperparameters = bool(optimize_hyperparameters)
+        self.max_iters = int(max_iters)
+        self.optimizer_results = [None] * (index_set_obj.get_n_resolutions() + 1 if index_set_obj is not None else 0)
         self.verbose = verbose
         self.forced_independence = forced_independence
         if forced_independence is not True and (axis_resolution_specific or ard_resolution_specific):
@@ -201,8 +216,67 @@ class MultiResolutionGaussianProcess(object):
     def fit(self, n_iter=1, tol=1e-3, min_iter=10):
         self._fit()
 
+    # ------------------------------------------------- per-layer hyper-parameters
+    def layer_log_marginal_likelihood(self, layer, ell, sf, noise):
+        """(lml, grad) of layer ``layer`` at (ell, sf = variance, noise) on the residual targets of the last fit
+        (y - f_bar of that layer, the layer's bias rule), summed over all regions and ranks; grad is w.r.t.
+        (log sf, log ell, log noise).  Collective: every rank calls it.  Raises LinAlgError if a block is not PD."""
+        if not self._fitted:
+            raise RuntimeError('call fit() before evaluating a layer objective')
+        lml, grad, failure = self._layer_objective(layer, self._f_bar_layers[layer], ell, sf, noise)
+        if failure != 0.0:
+            raise np.linalg.LinAlgError('Matrix is not positive definite (a block of layer %d)' % layer)
+        return lml, grad
+
+    def _layer_objective(self, j, f_bar, ell, sf, noise):
+        """Sum over this rank's blocks of layer j, then ONE all-reduce of [lml | grad | failure] over the ranks, so that
+        every rank sees the same objective.  A watchdog code raises RuntimeError on every rank."""
+        post = self.posterior_obj[j]
+        lml, grad, failure = post.layer_objective(ell, sf, noise, self._slices(self._y, j), self.x[j], self._slices(f_bar, j),
+                                                  self._owned(j))
+        if self.world_size > 1:
+            buf = torch.tensor([lml] + list(grad) + [failure], dtype=torch.float64, device=self.device)
+            dist.allreduce_sum_(buf, self.group)
+            vals = buf.cpu().numpy()
+            lml, grad, failure = float(vals[0]), vals[1:4], float(vals[4])
+        if dev.is_watchdog(failure):
+            raise RuntimeError('cimrgp_potrf: schedule watchdog while evaluating the objective of layer %d' % j)
+        return lml, np.asarray(grad, dtype=np.float64), failure
+
+    def _learn_layer(self, j, f_bar):
+        """L-BFGS-B (SciPy) on -sum_l LML_l over theta = (log sf, log l, log noise) of layer j, from the constructor's
+        kernel (noise: its own, else NOISE_FRACTION * sf); the layer is then fitted with a NEW kernel object of the
+        same class holding the learned values (the noise fixed and shared by the layer's regions).  A non-PD trial
+        point scores (1e100, 0), as in GP_RBF.  With several ranks every evaluation costs one small all-reduce."""
+        from scipy.optimize import minimize
+        from .Posteriors import NOISE_FRACTION
+        k0 = self.spectral_density_obj[j]
+        noise0 = k0.noise if k0.noise is not None else NOISE_FRACTION * k0.sf
+        theta0 = np.log([k0.sf, k0.l, noise0])
+
+        def objective(theta):
+            sf, ell, noise = np.exp(theta)
+            lml, grad, failure = self._layer_objective(j, f_bar, ell, sf, noise)
+            if failure != 0.0:
+                return 1e100, np.zeros(3)
+            return -lml, -grad
+
+        res = minimize(objective, theta0, jac=True, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
+        sf, ell, noise = (float(v) for v in np.exp(res.x))
+        if isinstance(k0, DenseMaternKernel):
+            kernel = DenseMaternKernel(nu=k0.nu, l=ell, sf=sf, noise=noise)
+        else:
+            kernel = RBFKernel(l=ell, sf=sf, noise=noise)
+        self.optimizer_results[j] = res
+        self.posterior_obj[j].kernel = kernel
+
     def _fit(self):
         n, q = self._y.shape
+        if self.optimize_hyperparameters:
+            # a re-fit starts again from the constructor's kernels
+            for j in range(self.n_layers):
+                self.posterior_obj[j].kernel = self.spectral_density_obj[j]
+            self.optimizer_results = [None] * self.n_layers
         f_bar = torch.zeros_like(self._y)
         self._layer_events = [torch.cuda.Event(enable_timing=True) for _ in range(self.n_layers + 1)]
         failed = torch.zeros(self.n_layers, dtype=self.dtype, device=self.device)
@@ -234,6 +308,8 @@ class MultiResolutionGaussianProcess(object):
                 buf = torch.zeros(n * q + 1, dtype=self.dtype, device=self.device)
                 layer_pred, flag = buf[:n * q].view(n, q), buf[n * q:]
             owned = self._owned(j)
+            if self.optimize_hyperparameters:
+                self._learn_layer(j, f_bar)
             self.posterior_obj[j].update_scale_given_axis(
                 y_mean=self._slices(self._y, j), x=self.x[j], f_bar=self._slices(f_bar, j),
                 train_out=self._slices(layer_pred, j), owned=owned, keep_factors=self.keep_factors)

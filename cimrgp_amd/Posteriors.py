@@ -313,6 +313,86 @@ class DensePosterior(object):
                     blk.batch, blk.batch_index = batch, i
                 self.blocks[l] = blk
 
+    def layer_objective(self, ell, sf2, noise, y_mean, x, f_bar, owned=None):
+        """Log marginal likelihood of the layer's residual targets ``y_mean - f_bar`` (lists indexed by region of device
+        views, as for :meth:`update_scale_given_axis`) under the covariance of ``self.kernel``'s class with
+        (ell, sf2, noise), summed over the ``owned`` regions, and its gradient w.r.t. (log sf2, log ell, log noise).
+        Each block's bias is its column means, or the whole layer's when ``bias_region_specific`` is False.
+        Returns (lml, grad (3,), failure): failure = the largest LAPACK ``info`` of the blocks (0: all PD); lml and
+        grad are meaningless when it is not 0.  Equal-sized blocks whose views are slices of one layer array go
+        through ONE C call per sub-batch (cimrgp_layer_lml_grad_cov, one host read-back of its results); the others
+        (larger than BATCH_MAX_N, or not slices) through the single-block composition
+        (RegressionInput.log_marginal_likelihood)."""
+        from .RegressionInput import log_marginal_likelihood
+        regions = list(range(self.n_regions) if owned is None else owned)
+        q = self.dy
+        cov = self.kernel.cov
+        shared_bias = None
+        if not self.bias_region_specific:
+            shared_bias = dev.block_stats(self._whole_layer(y_mean), self._whole_layer(f_bar))[:q]
+        lml, grad, failure = 0.0, np.zeros(3), 0.0
+        by_size = {}
+        for l in regions:
+            by_size.setdefault(int(x[l].shape[0]), []).append(l)
+        for n_l, group in by_size.items():
+            sliced = all(_layer_array(v, group) is not None for v in (y_mean, x, f_bar)) and _same_rows((y_mean, x, f_bar), group)
+            if n_l <= BATCH_MAX_N and sliced:
+                a, g, f = self._objective_batched(group, ell, sf2, noise, y_mean, x, f_bar, shared_bias)
+                lml, grad, failure = lml + a, grad + g, max(failure, f)
+                continue
+            for l in group:
+                bias = shared_bias if shared_bias is not None else dev.block_stats(y_mean[l], f_bar[l])[:q]
+                r = dev.residual(y_mean[l], f_bar[l], bias)
+                try:
+                    a, g = log_marginal_likelihood(x[l], r, ell, sf2, noise, cov)
+                except np.linalg.LinAlgError:
+                    failure = max(failure, 1.0)
+                    continue
+                except RuntimeError as e:
+                    if 'schedule watchdog' not in str(e):
+                        raise
+                    failure = max(failure, float(dev.INFO_WATCHDOG))
+                    continue
+                lml, grad = lml + a, grad + g
+        return lml, grad, failure
+
+    def _objective_batched(self, group, ell, sf2, noise, y_mean, x, f_bar, shared_bias):
+        """:meth:`layer_objective` of ``group`` (regions of equal size): sub-batches sized by the free memory as in
+        :meth:`_fit_batched` (the K^-1 arena and the carried identity rows on top of the factor)."""
+        n = int(x[group[0]].shape[0])
+        q = self.dy
+        device, dtype = y_mean[group[0]].device, y_mean[group[0]].dtype
+        ld = dev.padded_ld(n)
+        ws_bytes = max((dev.potrf_workspace_bytes(n, dtype) + 15) // 16 * 16, 16)
+        esz = torch.empty((), dtype=dtype).element_size()
+        per_block = 2 * n * ld * esz + ws_bytes + dev.layer_lml_scratch_bytes(n, q, 1, dtype)
+        free_bytes = torch.cuda.mem_get_info(device)[0]
+        cached = torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+        per_call = int(max(1, min(len(group), (free_bytes + cached) * 0.8 // per_block)))
+        y_all, x_all, f_all = _layer_array(y_mean, group), _layer_array(x, group), _layer_array(f_bar, group)
+        lml, grad, failure = 0.0, np.zeros(3), 0.0
+        for c0 in range(0, len(group), per_call):
+            sub = group[c0:c0 + per_call]
+            nb = len(sub)
+            rows = [y_mean[l].storage_offset() // y_mean[l].stride(0) for l in sub]
+            starts = torch.tensor(rows, dtype=torch.int64).to(device, non_blocking=True)
+            karena = torch.empty((nb, n, ld), dtype=dtype, device=device)
+            kinv = torch.empty((nb, n, ld), dtype=dtype, device=device)
+            ws_arena = torch.empty((nb, ws_bytes), dtype=torch.uint8, device=device)
+            info = torch.zeros(nb, dtype=torch.int32, device=device)
+            out = torch.empty((nb, 4), dtype=torch.float64, device=device)
+            dev.layer_lml_grad(x_all, y_all, f_all, starts, n, ell, sf2, noise, shared_bias, karena, kinv, ws_arena, info, out,
+                               cov=self.kernel.cov)
+            del karena, kinv, ws_arena
+            res = torch.cat([out.reshape(-1), info.to(torch.float64)]).cpu().numpy()     # one read-back per call
+            vals, infos = res[:4 * nb].reshape(nb, 4), res[4 * nb:]
+            if np.any(infos != 0):
+                failure = max(failure, float(infos.max()))
+                continue
+            lml += float(vals[:, 0].sum())
+            grad += vals[:, 1:].sum(axis=0)
+        return lml, grad, failure
+
     def predict_layer(self, x_all, xs, test_bounds, owned, mean, var, add_noise, fan_factory):
         """Accumulate the layer's predictive mean and variance at the test points: test block l =
         rows test_bounds[l] of ``xs``, served by training block l (MRGP.py:782-803).  Blocks that were fitted

@@ -24,8 +24,39 @@ import numpy as np
 import torch
 
 from . import device as dev
+from ._lib import COV_RBF
 from .KernelClass import RBFKernel, DenseMaternKernel
 from .Posteriors import DenseBlock, NOISE_FRACTION
+
+
+def log_marginal_likelihood(x, y, ell, sf, noise, cov=COV_RBF, want_grad=True):
+    """One block's LML of targets y (device, n x q) under K = k_cov(x, x) (length-scale ell, variance sf) + noise I, and
+    its gradient w.r.t. (log sf, log ell, log noise) as a NumPy (3,) array: Gram, factorisation, solve, log-determinant,
+    K^-1 = L^-T L^-1 (row-wise solve of the identity, SYRK) and the fused gradient reduction.  Raises LinAlgError if K
+    is not PD.  ``GP_RBF.log_marginal_likelihood`` and the MRGP layer objective for blocks the batched call
+    (cimrgp_layer_lml_grad_cov) cannot take both run this."""
+    n, q = y.shape
+    kbuf = dev.rbf_gram(x, ell, sf, noise, lower_only=True, cov=cov)
+    ws, info = dev.potrf(kbuf, n)
+    alpha = y.clone()
+    dev.potrs(kbuf, n, ws, alpha)
+    dev.raise_if_not_pd(info)
+    half_logdet = float(dev.logdet_half(kbuf, n).item())
+    fit = float((y * alpha).sum().item())
+    lml = -0.5 * fit - q * half_logdet - 0.5 * n * q * np.log(2 * np.pi)
+    if not want_grad:
+        return lml, None
+    # K^-1 = U U^T with U = L^-T: the identity carried through the row-wise solve, then a SYRK
+    u = dev.alloc_matrix(n, n, x.dtype, x.device)
+    u.zero_()
+    u[:n, :n].fill_diagonal_(1.0)
+    dev.trsm_rows(kbuf, n, ws, u, n)
+    kinv = dev.alloc_matrix(n, n, x.dtype, x.device)
+    kinv.zero_()
+    dev.syrk_lower(kinv, u, n, n)            # lower(kinv) = -K^-1
+    kinv.neg_()
+    grad = dev.lml_grad(x, kinv, n, alpha, ell, sf, noise, cov=cov).cpu().numpy()
+    return lml, grad
 
 
 class RegressionMethod(object):
@@ -105,29 +136,7 @@ class GP_RBF(RegressionMethod):
     def log_marginal_likelihood(self, x, y, ell, sf, noise, want_grad=True):
         """LML of targets y (device, n x q) under K = sf E(ell) + noise I, and its gradient
         w.r.t. (log sf, log ell, log noise).  Raises LinAlgError if K is not PD."""
-        n, q = y.shape
-        cov = self.kernel.cov
-        kbuf = dev.rbf_gram(x, ell, sf, noise, lower_only=True, cov=cov)
-        ws, info = dev.potrf(kbuf, n)
-        alpha = y.clone()
-        dev.potrs(kbuf, n, ws, alpha)
-        dev.raise_if_not_pd(info)
-        half_logdet = float(dev.logdet_half(kbuf, n).item())
-        fit = float((y * alpha).sum().item())
-        lml = -0.5 * fit - q * half_logdet - 0.5 * n * q * np.log(2 * np.pi)
-        if not want_grad:
-            return lml, None
-        # K^-1 = U U^T with U = L^-T: the identity carried through the row-wise solve, then a SYRK
-        u = dev.alloc_matrix(n, n, x.dtype, x.device)
-        u.zero_()
-        u[:n, :n].fill_diagonal_(1.0)
-        dev.trsm_rows(kbuf, n, ws, u, n)
-        kinv = dev.alloc_matrix(n, n, x.dtype, x.device)
-        kinv.zero_()
-        dev.syrk_lower(kinv, u, n, n)            # lower(kinv) = -K^-1
-        kinv.neg_()
-        grad = dev.lml_grad(x, kinv, n, alpha, ell, sf, noise, cov=cov).cpu().numpy()
-        return lml, grad
+        return log_marginal_likelihood(x, y, ell, sf, noise, self.kernel.cov, want_grad)
 
     def log_marginal_likelihood_ard(self, x, y, ells, sf, noise):
         """ARD twin of :meth:`log_marginal_likelihood`: ``ells`` (d,) length-scales; gradient w.r.t.

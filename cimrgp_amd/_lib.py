@@ -81,6 +81,13 @@ SIGNATURES = {
     "cimrgp_profile_collect_bytes": (_i32, [C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_i64)]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/cimrgp_objective.h (the layer objective)
+OBJECTIVE_SIGNATURES = {
+    "cimrgp_layer_lml_grad_scratch_bytes": (_sz, [_i32, _i64, _i32, _i32]),
+    "cimrgp_layer_lml_grad_cov": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _dbl, _dbl, _dbl, _vp, _vp, _i64,
+                                         _i64, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -100,7 +107,7 @@ def load():
             "`bash cimrgp_amd/csrc/build.sh` (needs hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if a symbol is missing
         fn.restype = res
         fn.argtypes = args

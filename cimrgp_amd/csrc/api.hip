@@ -873,6 +873,49 @@ int cimrgp_layer_predict_cov(int dtype, int cov, const void* x_dev, const int64_
                               mean_dev, var_dev, stream);
 }
 
+size_t cimrgp_layer_lml_grad_scratch_bytes(int dtype, int64_t n, int q, int batch)
+{
+    if ((dtype != CIMRGP_F32 && dtype != CIMRGP_F64) || n <= 0 || q < 1 || batch < 1) return 0;
+    return lml_scratch_layout(esize(dtype), n, q, batch).total;
+}
+
+int cimrgp_layer_lml_grad_cov(int dtype, int cov, const void* x_dev, const void* y_dev, const void* fbar_dev,
+                              const int64_t* starts_dev, int batch, int64_t n, int d, int q, double ell, double sf2,
+                              double noise, const void* shared_bias_dev, void* k_arena_dev, int64_t ldk, int64_t k_stride,
+                              void* kinv_arena_dev, void* ws_arena_dev, size_t ws_stride_bytes, int32_t* info_dev,
+                              void* scratch_dev, double* out_dev, void* stream)
+{
+    const char* fn = "cimrgp_layer_lml_grad_cov";
+    CIMRGP_REQUIRE(x_dev && y_dev && starts_dev && k_arena_dev && kinv_arena_dev && ws_arena_dev && info_dev && scratch_dev && out_dev,
+                   fn, "null pointer");
+    CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
+    CIMRGP_REQUIRE(dtype == CIMRGP_F32 || dtype == CIMRGP_F64, fn, "unknown dtype");
+    CIMRGP_REQUIRE(batch >= 1 && batch < 65536 && n >= 1 && n < (1ll << 30) && ldk >= n, fn, "bad dimensions");
+    CIMRGP_REQUIRE(d >= 1 && d <= 8, fn, "input dimension must be in [1, 8]");
+    CIMRGP_REQUIRE(q >= 1 && q <= 8, fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(ld_ok(dtype, ldk) && ld_ok(dtype, k_stride), fn, "leading dimensions and strides must be multiples of 16 bytes");
+    CIMRGP_REQUIRE(k_stride >= n * ldk - (ldk - n), fn, "matrix stride too small");
+    CIMRGP_REQUIRE(aligned16(k_arena_dev) && aligned16(kinv_arena_dev) && aligned16(ws_arena_dev) && aligned16(scratch_dev), fn,
+                   "pointers must be 16-byte aligned");
+    CIMRGP_REQUIRE(ws_stride_bytes >= cimrgp_potrf_workspace_bytes(dtype, n) && ws_stride_bytes % 16 == 0, fn,
+                   "workspace stride too small or misaligned");
+    CIMRGP_REQUIRE(ell > 0.0 && sf2 > 0.0 && noise >= 0.0, fn, "kernel parameters must be positive (noise non-negative)");
+    auto run = [&](auto tag) {
+        using T = decltype(tag);
+        LayerLml<T> a;
+        a.cov = cov;
+        a.x = (const T*)x_dev; a.y = (const T*)y_dev; a.fbar = (const T*)fbar_dev; a.starts = starts_dev;
+        a.batch = batch; a.n = n; a.d = d; a.q = q;
+        a.ell = ell; a.sf2 = sf2; a.noise = noise;
+        a.shared_bias = (const T*)shared_bias_dev;
+        a.k = (T*)k_arena_dev; a.ldk = ldk; a.sk = k_stride; a.kinv = (T*)kinv_arena_dev;
+        a.ws = (T*)ws_arena_dev; a.sws = (int64_t)(ws_stride_bytes / sizeof(T)); a.info = info_dev;
+        a.scratch = scratch_dev; a.out = out_dev;
+        return layer_lml_grad_run<T>(a, S(stream));
+    };
+    DISPATCH(dtype, fn, run(float()), run(double()));
+}
+
 int cimrgp_set_rows_queues(int queues)
 {
     if (queues != 1 && queues != 2) return fail("cimrgp_set_rows_queues", "queues must be 1 or 2");

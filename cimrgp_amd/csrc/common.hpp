@@ -340,6 +340,14 @@ template <typename T> int misc_logdet_half(const T* l, int64_t n, int64_t ld, do
 template <typename T> int lml_grad_run(const T* x, int64_t n, int d, const T* kinv, int64_t ld, const T* alpha, int q,
                                        double ell, double sf2, double noise, double* out3, double* scratch, hipStream_t st,
                                        bool ard = false, int cov = CIMRGP_COV_RBF, const char* fn = nullptr);
+// the gradient of `batch` blocks (K^-1 lower triangles at ks apart, inputs from rows starts[b]) and each block's log
+// marginal likelihood from its factor l (same layout as kinv) and z = L^-1 r (batch x n x q): out[4 b + 0 .. 3];
+// partial: batch x lml_grad_tiles_count(n) x 3 doubles
+int64_t lml_grad_tiles_count(int64_t n);
+template <typename T> int lml_grad_batched_run(const T* x, const int64_t* starts, int batch, int64_t n, int d, const T* kinv,
+                                               int64_t ld, int64_t ks, const T* l, const T* alpha, const T* z, int q, double ell,
+                                               double sf2, double noise, double* out, double* partial, hipStream_t st, int cov,
+                                               const char* fn);
 
 // layer.hip: one call per layer for a batch of equal-sized blocks (strides in elements)
 template <typename T> struct LayerFit {
@@ -364,6 +372,21 @@ template <typename T> struct LayerPredict {
     T* mean; T* var;
 };
 template <typename T> int layer_predict_run(const LayerPredict<T>& a, hipStream_t st);
+// log marginal likelihood + gradient of a batch of blocks (cimrgp_layer_lml_grad_cov); the scratch holds the carried
+// rows (q residual rows + the identity, per block), z, alpha, the backward solve's work area, bias, noise and the
+// gradient's tile records, at the byte offsets of lml_scratch_layout
+struct LmlScratch { int64_t ldr = 0, srows = 0; size_t rows = 0, z = 0, alpha = 0, work = 0, bias = 0, noise = 0, partial = 0, total = 0; };
+LmlScratch lml_scratch_layout(size_t esz, int64_t n, int q, int batch);
+template <typename T> struct LayerLml {
+    const T* x; const T* y; const T* fbar; const int64_t* starts;
+    int batch; int64_t n; int d; int q;
+    double ell, sf2, noise;
+    int cov = CIMRGP_COV_RBF;
+    const T* shared_bias;
+    T* k; int64_t ldk, sk; T* kinv; T* ws; int64_t sws; int32_t* info;
+    void* scratch; double* out;
+};
+template <typename T> int layer_lml_grad_run(const LayerLml<T>& a, hipStream_t st);
 
 // reduced.hip
 template <typename T> int laplace_basis_run(const T* x, int64_t n, int d, const double* interval, int m, T* phi, hipStream_t st);

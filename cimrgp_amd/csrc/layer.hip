@@ -188,6 +188,113 @@ int layer_predict_run(const LayerPredict<T>& a, hipStream_t st)
                                  a.batch, a.t_starts, a.sw);
 }
 
+// ---- log marginal likelihood and its gradient for a batch of blocks (cimrgp_layer_lml_grad_cov) ----
+//   statistics -> bias | residual rows r^T and the identity as q + n carried rows | Gram + noise | factorisation with
+//   the rows carried: z^T = r^T L^-T and U = L^-T come out of the same panel sweep | backward solve (alpha) |
+//   lower(K^-1) = U U^T (batched SYRK on the matrix cores) | gradient tiles + per-block finish (misc.hip)
+// K^-1 method: the identity rides through potrf_rows_batched as carried rows, then one batched SYRK: about
+// n^3 + n^3 flops per block on top of the factorisation, all in kernels the factorisation already uses.
+
+// rows[b][q + i][j] = (i == j): the identity below the q residual rows
+template <typename T>
+__global__ void k_layer_eye(T* __restrict__ rows, int64_t ldr, int64_t srows, int64_t n, int q)
+{
+    const int64_t b = blockIdx.y;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * n) return;
+    const int64_t i = e / n, j = e - i * n;
+    rows[b * srows + (q + i) * ldr + j] = (i == j) ? (T)1 : (T)0;
+}
+
+// lower(k_b) = -lower(k_b): the SYRK subtracts (C -= A A^T)
+template <typename T>
+__global__ void k_layer_neg_lower(T* __restrict__ k, int64_t ld, int64_t ks, int64_t n)
+{
+    const int64_t b = blockIdx.y;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * n) return;
+    const int64_t i = e / n, j = e - i * n;
+    if (j <= i) k[b * ks + i * ld + j] = -k[b * ks + i * ld + j];
+}
+
+LmlScratch lml_scratch_layout(size_t esz, int64_t n, int q, int batch)
+{
+    LmlScratch s;
+    s.ldr = (n + 15) / 16 * 16;
+    if (s.ldr % 512 == 0) s.ldr += 16;       // device.padded_ld's rule
+    s.srows = (int64_t)(q + n) * s.ldr;
+    auto seg = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
+    const size_t nb = (size_t)batch;
+    size_t off = 0;
+    s.rows = off;    off += seg(nb * (size_t)s.srows * esz);
+    s.z = off;       off += seg(nb * (size_t)(n * q) * esz);
+    s.alpha = off;   off += seg(nb * (size_t)(n * q) * esz);
+    s.work = off;    off += seg(nb * (size_t)(2 * n * q) * esz);
+    s.bias = off;    off += seg(nb * (size_t)q * esz);
+    s.noise = off;   off += seg(nb * esz);
+    s.partial = off; off += seg(nb * (size_t)lml_grad_tiles_count(n) * 3 * sizeof(double));
+    s.total = off;
+    return s;
+}
+
+template <typename T>
+int layer_lml_grad_run(const LayerLml<T>& a, hipStream_t st)
+{
+    const char* fn = "cimrgp_layer_lml_grad_cov";
+    CIMRGP_REQUIRE(a.batch >= 1 && a.batch < 65536, fn, "batch count out of range");
+    CIMRGP_REQUIRE(a.n > 0 && a.n < (1ll << 30), fn, "bad dimensions");
+    CIMRGP_REQUIRE(a.q >= 1 && a.q <= LY_MAXQ, fn, "number of outputs must be in [1, 8]");
+    const LmlScratch sl = lml_scratch_layout(sizeof(T), a.n, a.q, a.batch);
+    char* base = (char*)a.scratch;
+    T* rows = (T*)(base + sl.rows);
+    T* z = (T*)(base + sl.z);
+    T* alpha = (T*)(base + sl.alpha);
+    T* work = (T*)(base + sl.work);
+    T* bias = (T*)(base + sl.bias);
+    T* noise = (T*)(base + sl.noise);
+    double* partial = (double*)(base + sl.partial);
+    const unsigned nb = (unsigned)a.batch;
+    const unsigned ge = (unsigned)((a.n * a.q + 255) / 256);
+    const unsigned gn = (unsigned)((a.n * a.n + 255) / 256);
+    hipLaunchKernelGGL((k_layer_stats<T>), dim3(nb), dim3(1024), 0, st, a.y, a.fbar, a.starts, a.n, a.q, (T)a.noise, (T)0, (T)0,
+                       a.shared_bias, (const T*)nullptr, bias, noise);
+    CIMRGP_LAUNCH_CHECK(fn);
+    hipLaunchKernelGGL((k_layer_rows<T>), dim3(ge, nb), dim3(256), 0, st, a.y, a.fbar, a.starts, a.n, a.q, (const T*)bias, rows,
+                       sl.ldr, sl.srows);
+    CIMRGP_LAUNCH_CHECK(fn);
+    hipLaunchKernelGGL((k_layer_eye<T>), dim3(gn, nb), dim3(256), 0, st, rows, sl.ldr, sl.srows, a.n, a.q);
+    CIMRGP_LAUNCH_CHECK(fn);
+    int rc = rbf_gram_batched_run<T>(a.x, a.starts, a.n, a.x, a.starts, a.n, a.d, a.ell, a.sf2, (const T*)noise, a.k, a.ldk, a.sk,
+                                     a.batch, true, st, a.cov);
+    if (rc) return rc;
+    PotrfBatch bt;
+    bt.count = a.batch;
+    bt.sk = a.sk;
+    bt.sws = a.sws;
+    bt.sb = sl.srows;
+    rc = potrf_batched_run<T>(a.k, a.n, a.ldk, a.ws, a.info, rows, a.q + a.n, sl.ldr, bt, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_layer_z<T>), dim3(ge, nb), dim3(256), 0, st, (const T*)rows, sl.ldr, sl.srows, a.n, a.q, z, alpha, work,
+                       2 * (int64_t)a.q * a.n);
+    CIMRGP_LAUNCH_CHECK(fn);
+    rc = potrs_run<T>(a.k, a.n, a.ldk, a.ws, alpha, a.q, nullptr, work, true, st, bt, true);
+    if (rc) return rc;
+    const size_t kinv_elems = (size_t)((int64_t)(a.batch - 1) * a.sk + (a.n - 1) * a.ldk + a.n);
+    rc = check_hip(hipMemsetAsync(a.kinv, 0, kinv_elems * sizeof(T), st), fn, "hipMemsetAsync");
+    if (rc) return rc;
+    GemmBatch gb;
+    gb.count = a.batch;
+    gb.sc = a.sk;
+    gb.sa = gb.sb = sl.srows;
+    const T* u = rows + (int64_t)a.q * sl.ldr;
+    rc = gemm_nt_sub<T>(a.kinv, a.ldk, u, sl.ldr, u, sl.ldr, a.n, a.n, (int)a.n, true, st, gb);
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_layer_neg_lower<T>), dim3(gn, nb), dim3(256), 0, st, a.kinv, a.ldk, a.sk, a.n);
+    CIMRGP_LAUNCH_CHECK(fn);
+    return lml_grad_batched_run<T>(a.x, a.starts, a.batch, a.n, a.d, (const T*)a.kinv, a.ldk, a.sk, (const T*)a.k, (const T*)alpha,
+                                   (const T*)z, a.q, a.ell, a.sf2, a.noise, a.out, partial, st, a.cov, fn);
+}
+
 // The targets of ONE block as carried rows and back (cimrgp_block_posterior).
 template <typename T>
 __global__ void k_rhs_rows(const T* __restrict__ y, int64_t n, int q, T* __restrict__ rows, int64_t ldr)
@@ -226,5 +333,7 @@ template int layer_fit_run<double>(const LayerFit<double>&, hipStream_t);
 template int layer_fit_run<float>(const LayerFit<float>&, hipStream_t);
 template int layer_predict_run<double>(const LayerPredict<double>&, hipStream_t);
 template int layer_predict_run<float>(const LayerPredict<float>&, hipStream_t);
+template int layer_lml_grad_run<double>(const LayerLml<double>&, hipStream_t);
+template int layer_lml_grad_run<float>(const LayerLml<float>&, hipStream_t);
 
 }  // namespace cimrgp

@@ -202,12 +202,25 @@ constexpr int LG_MAXD = 8;
 // dimension: partial record = [sf | l_1 .. l_8 | trace] (LG_NP entries) instead of [sf | l | trace].
 constexpr int LG_NP = LG_MAXD + 2;
 
-template <typename T, bool ARD>
+// BATCHED: blockIdx.y = block b of a layer (cimrgp_layer_lml_grad_cov): x from row starts[b], K^-1 at b * ks, alpha at
+// b * n * q, the partial records at b * gridDim.x.  The single-block instance (BATCHED = false) reads none of these.
+struct LgBatch { const int64_t* starts; int64_t ks; };
+#define CIMRGP_LG_BLOCK(NP)                                 \
+    if (BATCHED) {                                          \
+        const int64_t b_ = blockIdx.y;                      \
+        x += bb.starts[b_] * d;                             \
+        kinv += b_ * bb.ks;                                 \
+        alpha += b_ * (int64_t)n * q;                       \
+        partial += b_ * (int64_t)gridDim.x * (NP);          \
+    }
+
+template <typename T, bool ARD, bool BATCHED = false>
 __global__ __launch_bounds__(256)
 void k_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict__ kinv, int64_t ld,
                       const T* __restrict__ alpha, int q, T neg_half_inv_l2, T sf2, T inv_l2,
-                      double* __restrict__ partial)
+                      double* __restrict__ partial, LgBatch bb)
 {
+    CIMRGP_LG_BLOCK(ARD ? LG_NP : 3)
     __shared__ T sa[LG_T * LG_MAXD], sb[LG_T * LG_MAXD];
     __shared__ T aa[LG_T * 8], ab[LG_T * 8];
     __shared__ double red[ARD ? LG_NP : 3][4];
@@ -288,13 +301,14 @@ void k_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict
 // The Matern policies' tile: k_lml_grad_tiles' staging and reductions with k_ij and d k_ij / d log l of policy COV.
 // (The RBF kernel above keeps its own body, so that its code -- and its FP32 contraction of d2 -- stays as it was.)
 // c = cov_scale(COV, l); inv_l2 is not read.
-template <typename T, int COV, bool ARD>
+template <typename T, int COV, bool ARD, bool BATCHED>
 static __device__ __forceinline__ void lml_grad_tile(const T* __restrict__ x, int n, int d, const T* __restrict__ kinv, int64_t ld,
                                                      const T* __restrict__ alpha, int q, T c, T sf2, T inv_l2,
-                                                     double* __restrict__ partial)
+                                                     double* __restrict__ partial, const LgBatch& bb)
 {
     static_assert(COV != CIMRGP_COV_RBF, "the RBF gradient is k_lml_grad_tiles");
     (void)inv_l2;
+    CIMRGP_LG_BLOCK(ARD ? LG_NP : 3)
     __shared__ T sa[LG_T * LG_MAXD], sb[LG_T * LG_MAXD];
     __shared__ T aa[LG_T * 8], ab[LG_T * 8];
     __shared__ double red[ARD ? LG_NP : 3][4];
@@ -376,17 +390,17 @@ static __device__ __forceinline__ void lml_grad_tile(const T* __restrict__ x, in
     }
 }
 
-template <typename T, int COV, bool ARD>
+template <typename T, int COV, bool ARD, bool BATCHED = false>
 __global__ __launch_bounds__(256)
 void k_cov_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict__ kinv, int64_t ld,
-                          const T* __restrict__ alpha, int q, T c, T sf2, T inv_l2, double* __restrict__ partial)
+                          const T* __restrict__ alpha, int q, T c, T sf2, T inv_l2, double* __restrict__ partial, LgBatch bb)
 {
-    lml_grad_tile<T, COV, ARD>(x, n, d, kinv, ld, alpha, q, c, sf2, inv_l2, partial);
+    lml_grad_tile<T, COV, ARD, BATCHED>(x, n, d, kinv, ld, alpha, q, c, sf2, inv_l2, partial, bb);
 }
 
-template <typename T, int COV, bool ARD> static auto lml_grad_kernel()
+template <typename T, int COV, bool ARD, bool BATCHED = false> static auto lml_grad_kernel()
 {
-    if constexpr (COV == CIMRGP_COV_RBF) return k_lml_grad_tiles<T, ARD>; else return k_cov_lml_grad_tiles<T, COV, ARD>;
+    if constexpr (COV == CIMRGP_COV_RBF) return k_lml_grad_tiles<T, ARD, BATCHED>; else return k_cov_lml_grad_tiles<T, COV, ARD, BATCHED>;
 }
 
 __global__ __launch_bounds__(1024)
@@ -420,12 +434,12 @@ static int lml_grad_run_cov(const T* x, int64_t n, int d, const T* kinv, int64_t
     if (ard) {
         // inputs are pre-scaled by the length-scales: unit length-scale here; out = [sf | l_1..l_d | noise]
         hipLaunchKernelGGL((lml_grad_kernel<T, COV, true>()), dim3((unsigned)tiles), dim3(256), 0, st, x, (int)n, d, kinv, ld, alpha, q,
-                           (T)cov_scale(COV, 1.0), (T)sf2, (T)1, scratch);
+                           (T)cov_scale(COV, 1.0), (T)sf2, (T)1, scratch, LgBatch{nullptr, 0});
         CIMRGP_LAUNCH_CHECK(fn);
         hipLaunchKernelGGL(k_lml_grad_final, dim3(1), dim3(1024), 0, st, (const double*)scratch, tiles, noise, out3, LG_NP, d + 2);
     } else {
         hipLaunchKernelGGL((lml_grad_kernel<T, COV, false>()), dim3((unsigned)tiles), dim3(256), 0, st, x, (int)n, d, kinv, ld, alpha, q,
-                           (T)cov_scale(COV, ell), (T)sf2, (T)(1.0 / (ell * ell)), scratch);
+                           (T)cov_scale(COV, ell), (T)sf2, (T)(1.0 / (ell * ell)), scratch, LgBatch{nullptr, 0});
         CIMRGP_LAUNCH_CHECK(fn);
         hipLaunchKernelGGL(k_lml_grad_final, dim3(1), dim3(1024), 0, st, (const double*)scratch, tiles, noise, out3, 3, 3);
     }
@@ -447,5 +461,83 @@ template int lml_grad_run<double>(const double*, int64_t, int, const double*, in
                                   double, double*, double*, hipStream_t, bool, int, const char*);
 template int lml_grad_run<float>(const float*, int64_t, int, const float*, int64_t, const float*, int, double, double,
                                  double, double*, double*, hipStream_t, bool, int, const char*);
+
+// ---- a layer's blocks at once (cimrgp_layer_lml_grad_cov) ----
+// The tile kernels above with grid.y = block, then per block one workgroup that finishes it: the gradient from its
+// tile records (k_lml_grad_final's order), the data fit sum_c z_c^T z_c = sum_c r_c^T K^-1 r_c from z = L^-1 r, and
+// sum_i log L_ii from the factor's diagonal:
+//   out[4b + 0] = -1/2 fit - q sum log L_ii - 1/2 n q log 2 pi,  out[4b + 1 .. 3] = the gradient.
+namespace {
+
+template <typename T>
+__global__ __launch_bounds__(1024)
+void k_layer_lml_final(const double* __restrict__ partial, int64_t ntiles, double noise, const T* __restrict__ l, int64_t ld,
+                       int64_t ls, const T* __restrict__ z, int64_t n, int q, double* __restrict__ out)
+{
+    __shared__ double red[16];
+    const int64_t b = blockIdx.x;
+    partial += b * ntiles * 3;
+    l += b * ls;
+    z += b * n * q;
+    double g[3];
+    for (int c = 0; c < 3; ++c) {
+        double s = 0.0;
+        for (int64_t t = threadIdx.x; t < ntiles; t += blockDim.x) s += partial[t * 3 + c];
+        g[c] = block_sum_1024(s, red);
+    }
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) s += log((double)l[i * ld + i]);
+    const double half_logdet = block_sum_1024(s, red);
+    s = 0.0;
+    for (int64_t e = threadIdx.x; e < n * q; e += blockDim.x) s += (double)z[e] * (double)z[e];
+    const double fit = block_sum_1024(s, red);
+    if (threadIdx.x == 0) {
+        out[4 * b + 0] = -0.5 * fit - (double)q * half_logdet - 0.5 * (double)(n * q) * log(2.0 * M_PI);
+        out[4 * b + 1] = 0.5 * g[0];
+        out[4 * b + 2] = 0.5 * g[1];
+        out[4 * b + 3] = 0.5 * g[2] * noise;
+    }
+}
+
+}  // namespace
+
+int64_t lml_grad_tiles_count(int64_t n)
+{
+    const int64_t tm = (n + LG_T - 1) / LG_T;
+    return tm * (tm + 1) / 2;
+}
+
+template <typename T>
+int lml_grad_batched_run(const T* x, const int64_t* starts, int batch, int64_t n, int d, const T* kinv, int64_t ld, int64_t ks,
+                         const T* l, const T* alpha, const T* z, int q, double ell, double sf2, double noise, double* out,
+                         double* partial, hipStream_t st, int cov, const char* fn)
+{
+    CIMRGP_REQUIRE(n > 0 && n < (1ll << 30), fn, "bad size");
+    CIMRGP_REQUIRE(d >= 1 && d <= LG_MAXD, fn, "input dimension must be in [1, 8]");
+    CIMRGP_REQUIRE(q >= 1 && q <= 8, fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(batch >= 1 && batch < 65536, fn, "batch count out of range");
+    const int64_t tiles = lml_grad_tiles_count(n);
+    CIMRGP_REQUIRE(tiles < (1ll << 31), fn, "grid too large");
+    const LgBatch bb{starts, ks};
+    const int rc = with_cov(cov, [&](auto c) {
+        constexpr int COV = decltype(c)::value;
+        hipLaunchKernelGGL((lml_grad_kernel<T, COV, false, true>()), dim3((unsigned)tiles, (unsigned)batch), dim3(256), 0, st, x, (int)n,
+                           d, kinv, ld, alpha, q, (T)cov_scale(COV, ell), (T)sf2, (T)(1.0 / (ell * ell)), partial, bb);
+        CIMRGP_LAUNCH_CHECK(fn);
+        return 0;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_layer_lml_final<T>), dim3((unsigned)batch), dim3(1024), 0, st, (const double*)partial, tiles, noise, l, ld, ks,
+                       z, n, q, out);
+    CIMRGP_LAUNCH_CHECK(fn);
+    return 0;
+}
+
+template int lml_grad_batched_run<double>(const double*, const int64_t*, int, int64_t, int, const double*, int64_t, int64_t,
+                                          const double*, const double*, const double*, int, double, double, double, double*,
+                                          double*, hipStream_t, int, const char*);
+template int lml_grad_batched_run<float>(const float*, const int64_t*, int, int64_t, int, const float*, int64_t, int64_t,
+                                         const float*, const float*, const float*, int, double, double, double, double*,
+                                         double*, hipStream_t, int, const char*);
 
 }  // namespace cimrgp

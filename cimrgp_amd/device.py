@@ -294,6 +294,29 @@ def layer_predict(x, starts, n, xs, t_starts, ns, ell, sf2, larena, ws_arena, z,
                                         _p(w), ldw, w.stride(0), _p(mean), _p(var), _stream()), "cimrgp_layer_predict")
 
 
+def layer_lml_scratch_bytes(n, q, batch, dtype):
+    return int(_lib.load().cimrgp_layer_lml_grad_scratch_bytes(_DT[dtype], int(n), int(q), int(batch)))
+
+
+def layer_lml_grad(x, y, fbar, starts, n, ell, sf2, noise, shared_bias, karena, kinv_arena, ws_arena, info, out,
+                   cov=_lib.COV_RBF):
+    """Log marginal likelihood and its gradient w.r.t. (log sf, log l, log noise) of ``batch`` equal-sized blocks of
+    one layer in ONE call (cimrgp_layer_lml_grad_cov, include/cimrgp.h), addressed as for :func:`layer_fit`.
+    Targets: y - fbar - bias, bias = ``shared_bias`` (q,) or each block's column means.  karena / kinv_arena
+    (batch, n, ld) receive L and the lower triangle of K^-1, ws_arena (batch, ws_bytes) uint8, info (batch,) int32;
+    out (batch, 4) float64 = [LML | gradient] per block (undefined where info != 0)."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
+    lib = _lib.load()
+    batch = int(karena.shape[0])
+    q = int(y.shape[1])
+    scratch = torch.empty(max(layer_lml_scratch_bytes(n, q, batch, y.dtype), 16), dtype=torch.uint8, device=y.device)
+    _lib.check(lib.cimrgp_layer_lml_grad_cov(_DT[y.dtype], cov, _p(x), _p(y), _p(fbar), _p(starts), batch, int(n), int(x.shape[1]),
+                                             q, float(ell), float(sf2), float(noise), _p(shared_bias), _p(karena), karena.stride(1),
+                                             karena.stride(0), _p(kinv_arena), _p(ws_arena), ws_arena.stride(0), _p(info),
+                                             _p(scratch), _p(out), _stream()), "cimrgp_layer_lml_grad_cov")
+    return out
+
+
 def solve_lt(lbuf, n, ws, z):
     """Backward half of D3: z (n x q) = L^-1 R is overwritten with alpha = L^-T z."""
     lib = _lib.load()

@@ -455,4 +455,8 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
 #ifdef __cplusplus
 }
 #endif
+
+/* The hyper-parameter objective of a layer's blocks (cimrgp_layer_lml_grad_cov): include/cimrgp_objective.h. */
+#include "cimrgp_objective.h"
+
 #endif /* CIMRGP_H */
