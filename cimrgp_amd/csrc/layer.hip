@@ -206,6 +206,17 @@ __global__ void k_layer_eye(T* __restrict__ rows, int64_t ldr, int64_t srows, in
     rows[b * srows + (q + i) * ldr + j] = (i == j) ? (T)1 : (T)0;
 }
 
+// k_b[0:n, 0:n] = 0 (the SYRK's C): the padding columns [n, ld) and the gaps between the blocks belong to the caller
+template <typename T>
+__global__ void k_layer_zero(T* __restrict__ k, int64_t ld, int64_t ks, int64_t n)
+{
+    const int64_t b = blockIdx.y;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * n) return;
+    const int64_t i = e / n, j = e - i * n;
+    k[b * ks + i * ld + j] = (T)0;
+}
+
 // lower(k_b) = -lower(k_b): the SYRK subtracts (C -= A A^T)
 template <typename T>
 __global__ void k_layer_neg_lower(T* __restrict__ k, int64_t ld, int64_t ks, int64_t n)
@@ -279,9 +290,8 @@ int layer_lml_grad_run(const LayerLml<T>& a, hipStream_t st)
     CIMRGP_LAUNCH_CHECK(fn);
     rc = potrs_run<T>(a.k, a.n, a.ldk, a.ws, alpha, a.q, nullptr, work, true, st, bt, true);
     if (rc) return rc;
-    const size_t kinv_elems = (size_t)((int64_t)(a.batch - 1) * a.sk + (a.n - 1) * a.ldk + a.n);
-    rc = check_hip(hipMemsetAsync(a.kinv, 0, kinv_elems * sizeof(T), st), fn, "hipMemsetAsync");
-    if (rc) return rc;
+    hipLaunchKernelGGL((k_layer_zero<T>), dim3(gn, nb), dim3(256), 0, st, a.kinv, a.ldk, a.sk, a.n);
+    CIMRGP_LAUNCH_CHECK(fn);
     GemmBatch gb;
     gb.count = a.batch;
     gb.sc = a.sk;

@@ -148,7 +148,10 @@ int cimrgp_block_posterior(int dtype, const void* x_dev, int64_t n, int d, const
  * and device; passing ANY buffer of a set whose solve stage may still be running -- one set where two are needed, or a
  * plain cimrgp_block_posterior on the same set right behind a staged call -- is detected: the front end then waits for
  * that solve stage; correct, without overlap.  Results: k_dev is final on stream, alpha / z / mean / var on stream_solve.  Bit-identical to
- * cimrgp_block_posterior; equal streams give exactly that call. */
+ * cimrgp_block_posterior, except when the call factors early panels on a cimrgp_front_queue (FP64, the previous factorisation
+ * on `stream` still in flight): those panels update the trailing matrix one panel at a time, the look-ahead schedule groups
+ * the updates differently, so the results then agree with cimrgp_block_posterior to rounding, not bit for bit.  Equal
+ * streams give exactly that call. */
 int cimrgp_block_posterior_staged(int dtype, const void* x_dev, int64_t n, int d, const void* y_dev, int q,
                                   const void* xs_dev, int64_t ns, double ell, double sf2, double noise,
                                   void* k_dev, int64_t ldk, void* workspace_dev, size_t workspace_bytes,
@@ -274,7 +277,9 @@ int cimrgp_logdet_half(int dtype, const void* l_dev, int64_t n, int64_t ldl,
 
 /* ---- hyper-parameter optimisation step (RegressionInput.py:63, `.optimize()`) ----
  * C <- C - A A^T on the lower triangle (C: n x n, A: n x k, row-major).  With C = 0 and
- * A = L^-T (cimrgp_trsm_rows applied to the identity) this gives -K^-1. */
+ * A = L^-T (cimrgp_trsm_rows applied to the identity) this gives -K^-1.  The strict upper triangle
+ * is never read; inside the 128 x 128 diagonal blocks (rows and columns [128 t, 128 t + 128)) it may
+ * be overwritten (the persistent update stores diagonal tiles whole); outside them it is not written. */
 int cimrgp_syrk_lower(int dtype, void* c_dev, int64_t ldc, const void* a_dev,
                       int64_t lda, int64_t n, int64_t k, void* stream);
 /* Gradient of the log marginal likelihood w.r.t. (log sf, log l, log noise) for

@@ -22,7 +22,8 @@ extern "C" {
  *   out_dev[4b + 0] = LML_b = -1/2 sum_c r_c^T K_b^-1 r_c - q sum_i log L_ii - 1/2 n q log 2 pi,
  *   out_dev[4b + 1 .. 3] = d LML_b / d (log sf2, log ell, log noise) = 1/2 tr((alpha alpha^T - q K_b^-1) dK_b/dtheta),
  * doubles.  k_arena_dev (batch blocks of n x ldk, k_stride apart) receives L_b, kinv_arena_dev (same layout) the lower
- * triangle of K_b^-1; ws_arena_dev as for cimrgp_layer_fit; info_dev[b] as for cimrgp_potrf (CIMRGP_INFO_WATCHDOG
+ * triangle of K_b^-1 (the strict upper triangle of each n x n block holds junk; the columns [n, ldk) and the gaps
+ * between the blocks of either arena are not written); ws_arena_dev as for cimrgp_layer_fit; info_dev[b] as for cimrgp_potrf (CIMRGP_INFO_WATCHDOG
  * included): a block with info != 0 has undefined outputs, the other blocks' outputs are not affected.
  * scratch_dev: cimrgp_layer_lml_grad_scratch_bytes(dtype, n, q, batch) bytes, 16-byte aligned (0 for invalid sizes).
  * Enqueue-only.  Every argument is checked before any device work (errors name cimrgp_layer_lml_grad_cov). */
