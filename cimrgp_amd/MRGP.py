@@ -179,6 +179,7 @@ class MultiResolutionGaussianProcess(object):
         self.stats_obj = [DenseStats(self, j) for j in range(self.n_layers)]
         self._f_bar_layers = [None] * self.n_layers
         self._fitted = False
+        self.last_joint_jitter = [0.0] * self.n_layers
         self.lower_bound = []
         self.lower_bound_layer = [[] for _ in range(self.n_layers)]
 
@@ -438,6 +439,94 @@ class MultiResolutionGaussianProcess(object):
         if index_set_obj is not None:
             self._check_index_set(index_set_obj, number_of_regions)
         return self._predict(test_x, index_set_obj, want_var=True, include_noise=include_noise)
+
+    # ------------------------------------------------------- joint distribution
+    def _joint_layers(self, index_set, ns, include_noise):
+        """(layer, test bounds, add noise) of every layer that contributes, by the rule of :meth:`_predict`: without an
+        index set the single root region of layer 0 serves every test point and no noise is added."""
+        if index_set is None:
+            if self.n_regions[0] != 1:
+                raise ValueError('index_set_obj is required when the first layer has more than one region')
+            return [(0, [(0, ns)], False)]
+        n_layers = index_set.get_n_resolutions() + 1
+        return [(j, index_set.bounds[j], include_noise and j == n_layers - 1) for j in range(n_layers)]
+
+    def _joint(self, xs, index_set, include_noise, cov_out=None, samples=None, seed=0, jitter=1e-6):
+        """Every owned block's share, then ONE sum over the ranks of [buffer | failure flag]."""
+        ns = xs.shape[0]
+        buf = cov_out if cov_out is not None else samples
+        flag = torch.zeros(2, dtype=self.dtype, device=self.device)      # [not positive definite | any other failure]
+        self.last_joint_jitter = [0.0] * self.n_layers
+        failure = None
+        for j, bounds, add_noise in self._joint_layers(index_set, ns, include_noise):
+            owned = self._owned(j)
+            if not owned:
+                continue
+            try:
+                self.last_joint_jitter[j] = self.posterior_obj[j].joint_layer(j, self._x_dev, xs, bounds, set(owned), add_noise,
+                                                                              cov_out, samples, seed, jitter)
+            except Exception as e:
+                # LinAlgError, the factorisation's schedule watchdog (RuntimeError), a failed C call ...: the other
+                # ranks wait in the collective, so join it with the flag set, then raise
+                if self.world_size == 1:
+                    raise
+                failure = e
+                flag[0 if isinstance(e, np.linalg.LinAlgError) else 1] = 1.0
+                break
+        if self.world_size > 1:
+            flat = torch.cat([buf.reshape(-1), flag])
+            dist.allreduce_sum_(flat, self.group)
+            buf.copy_(flat[:-2].view_as(buf))
+            if failure is not None:
+                raise failure
+            flags = flat[-2:].cpu().numpy()
+            if flags[1] != 0.0:
+                raise RuntimeError('joint predictive distribution failed on another rank (see its exception)')
+            if flags[0] != 0.0:
+                raise np.linalg.LinAlgError('joint predictive covariance not positive definite (a block owned by another rank)')
+        return buf
+
+    def get_predicted_covariance(self, test_x, index_set_obj=None, number_of_regions=None, include_noise=True):
+        """Joint predictive covariance (N* x N*, a symmetric NumPy array) of the latent function at ``test_x``, shared
+        by all outputs: the sum over the layers of each region's K(X*, X*) - W W^T, W = K(X*, X) L^-T, entries between
+        test points of different regions of a layer being 0.  ``include_noise``: the finest layer's block
+        noise on the diagonal, as in :meth:`get_predicted_mean_and_var`, whose variance is this matrix's diagonal.
+        Assembled on the device from the blocks' lower triangles: memory is N*^2 elements."""
+        if index_set_obj is not None:
+            self._check_index_set(index_set_obj, number_of_regions)
+        if not self._fitted:
+            raise RuntimeError('call fit() before predicting')
+        xs = self._prepare_test(test_x)
+        ns = xs.shape[0]
+        cov = torch.zeros((ns, ns), dtype=self.dtype, device=self.device)
+        self._joint(xs, index_set_obj, include_noise, cov_out=cov)
+        cov = torch.tril(cov) + torch.tril(cov, -1).t()
+        return cov.double().cpu().numpy()
+
+    def posterior_samples(self, test_x, size=1, index_set_obj=None, number_of_regions=None, seed=0, include_noise=True,
+                          jitter=1e-6):
+        """``size`` draws (size, N*, dy) from the joint predictive distribution at ``test_x``: the predictive mean plus,
+        per layer j and region l, chol(Sigma_jl + jitter sf2_j I) Z_jl with Z_jl[c][i] = phi(seed, j 2^32 + l, c, i),
+        c = sample * dy + output (include/cimrgp_joint.h).  Outputs are independent; a request for fewer samples gives a
+        prefix of a longer one, whatever the rank count.  A block whose factorisation fails is retried with 10x the
+        jitter (at most 4 times), then numpy.linalg.LinAlgError names the layer and region;
+        ``self.last_joint_jitter[j]``: the largest relative jitter the owned blocks of layer j needed."""
+        if index_set_obj is not None:
+            self._check_index_set(index_set_obj, number_of_regions)
+        if int(size) < 1:
+            raise ValueError('size must be at least 1')
+        if not (float(jitter) >= 0.0):
+            raise ValueError('jitter must be non-negative')
+        if not self._fitted:
+            raise RuntimeError('call fit() before predicting')
+        size = int(size)
+        mean = self._predict(test_x, index_set_obj, want_var=False)[0]
+        xs = self._prepare_test(test_x)
+        ns = xs.shape[0]
+        out = torch.zeros((size * self.dy, ns), dtype=self.dtype, device=self.device)
+        self._joint(xs, index_set_obj, include_noise, samples=out, seed=int(seed), jitter=float(jitter))
+        dev_part = out.double().cpu().numpy().reshape(size, self.dy, ns).transpose(0, 2, 1)
+        return mean[None, :, :] + dev_part
 
     def get_test_likelihood(self, test, index_set_obj=None, number_of_regions=None):
         test_x, test_y = test[0], test[1]

@@ -195,6 +195,95 @@ class _FittedBatch(object):
         self.karena, self.ws_arena, self.z, self.bias, self.noise = karena, ws_arena, z, bias, noise
 
 
+#: escalations of a block's relative jitter (x 10 each) before a joint factorisation is given up
+JOINT_RETRIES = 4
+#: a retry starts from max(jitter, this) x 10: a zero jitter escalates to 1e-6 (GPy's jitchol starting value), ... 1e-3
+JOINT_JITTER_FLOOR = 1e-7
+#: bytes of standard normals one joint sampling call may hold
+JOINT_Z_BYTES = 256 << 20
+
+
+class _JointCall(object):
+    """Blocks of one layer that go through one cimrgp_layer_joint_cov call: the training side (layer arrays, starts,
+    factor and workspace arenas), the test side (t_starts, ns) and the blocks' noise (nb,) on the device."""
+
+    def __init__(self, regions, x, starts, n, t_starts, ns, larena, ws_arena, noise):
+        self.regions, self.x, self.starts, self.n = list(regions), x, starts, int(n)
+        self.t_starts, self.ns, self.larena, self.ws_arena, self.noise = t_starts, int(ns), larena, ws_arena, noise
+
+    def part(self, i):
+        """Block i alone (batch = 1): for a factorisation retried with more jitter."""
+        return _JointCall([self.regions[i]], self.x, self.starts[i:i + 1], self.n, self.t_starts[i:i + 1], self.ns,
+                          self.larena[i:i + 1], self.ws_arena[i:i + 1], self.noise[i:i + 1])
+
+
+def single_joint_call(blk, region, xs_device, a, b):
+    """A fitted :class:`DenseBlock` as a batch of one: its own inputs with start 0, its factor buffer as the arena."""
+    if blk.lbuf is None:
+        raise RuntimeError('the joint covariance needs the Cholesky factor: fit with keep_factors=True')
+    starts = torch.zeros(1, dtype=torch.int64, device=xs_device)
+    t_starts = torch.full((1,), int(a), dtype=torch.int64, device=xs_device)
+    return _JointCall([region], blk.x, starts, blk.n, t_starts, int(b) - int(a), blk.lbuf.unsqueeze(0), blk.ws.unsqueeze(0),
+                      blk.noise.reshape(1))
+
+
+def joint_run(call, kernel, xs, layer, add_noise, cov_out=None, samples=None, seed=0, jitter=1e-6):
+    """One call's share of the joint distribution ("Joint predictive covariance and posterior samples").
+    ``cov_out`` (N* x N*): the blocks' Sigma (+ noise) is added to its lower triangle, no jitter.  ``samples`` (cols x
+    N*): each block is factored with (jitter sf2 + noise) on its diagonal -- a block whose factorisation fails is
+    retried alone with 10x the jitter (from JOINT_JITTER_FLOOR when it is smaller), at most JOINT_RETRIES times, then LinAlgError names the layer and region --
+    and chol(.) Z is added, Z_b[c][i] = phi(seed, layer 2^32 + region, c, i).  Returns the largest relative jitter
+    used (0.0 without samples)."""
+    nb, ns, n = len(call.regions), call.ns, call.n
+    if ns <= 0 or nb == 0:
+        return 0.0
+    dtype, device = xs.dtype, xs.device
+    sf2 = float(kernel.sf)
+    ldc = dev.joint_ld(ns, dtype)
+    carena = torch.empty((nb, ns, ldc), dtype=dtype, device=device)
+    extra = call.noise.to(dtype) if add_noise else torch.zeros(nb, dtype=dtype, device=device)
+    if samples is None:
+        dev.layer_joint_cov(call.x, call.starts, n, xs, call.t_starts, ns, kernel.l, sf2, call.larena, call.ws_arena, extra,
+                            carena, cov=kernel.cov)
+        for i, a in enumerate(call.t_starts.cpu().tolist()):
+            cov_out[a:a + ns, a:a + ns] += torch.tril(carena[i, :, :ns])
+        return 0.0
+    cws_bytes = max((dev.potrf_workspace_bytes(ns, dtype) + 15) // 16 * 16, 16)
+    cws = torch.empty((nb, cws_bytes), dtype=torch.uint8, device=device)
+    info = torch.zeros(nb, dtype=torch.int32, device=device)
+    diag = extra + jitter * sf2
+    dev.layer_joint_cov(call.x, call.starts, n, xs, call.t_starts, ns, kernel.l, sf2, call.larena, call.ws_arena, diag, carena,
+                        cws, info, cov=kernel.cov)
+    used = float(jitter)
+    for i in np.flatnonzero(info.cpu().numpy() != 0):          # info read once per call
+        one, rel = call.part(int(i)), max(float(jitter), JOINT_JITTER_FLOOR)
+        for _ in range(JOINT_RETRIES):
+            rel *= 10.0
+            dev.layer_joint_cov(one.x, one.starts, n, xs, one.t_starts, ns, kernel.l, sf2, one.larena, one.ws_arena,
+                                extra[i:i + 1] + rel * sf2, carena[i:i + 1], cws[i:i + 1], info[i:i + 1], cov=kernel.cov)
+            code = int(info[i].item())
+            if code == 0:
+                break
+        if code != 0:
+            if dev.is_watchdog(code):
+                raise RuntimeError('cimrgp_potrf: schedule watchdog (joint factor of layer %d, region %d)'
+                                   % (layer, call.regions[i]))
+            raise np.linalg.LinAlgError('joint predictive covariance of layer %d, region %d is not positive definite '
+                                        'with a relative jitter of %g (leading minor of order %d)'
+                                        % (layer, call.regions[i], rel, code))
+        used = max(used, rel)
+    keys = torch.tensor([(int(layer) << 32) + int(l) for l in call.regions], dtype=torch.int64).to(device)
+    cols = int(samples.shape[0])
+    ldz = dev.joint_ld(ns, dtype)
+    chunk = int(max(1, min(cols, JOINT_Z_BYTES // (nb * ldz * xs.element_size()))))
+    z = torch.empty((nb, chunk, ldz), dtype=dtype, device=device)
+    for c0 in range(0, cols, chunk):
+        cc = min(chunk, cols - c0)
+        dev.normal_fill(seed, keys, c0, cc, ns, z)
+        dev.layer_sample(carena, ns, z, cc, call.t_starts, samples[c0:c0 + cc])
+    return used
+
+
 class DensePosterior(object):
     """One resolution: a list of :class:`DenseBlock`, updated in place."""
 
@@ -432,6 +521,46 @@ class DensePosterior(object):
             with torch.cuda.stream(fan.stream()):
                 self.blocks[l].predict(xs[a:b], mean[a:b], var[a:b], add_noise=add_noise)
         fan.join()
+
+    def joint_layer(self, layer, x_all, xs, test_bounds, owned, add_noise, cov_out=None, samples=None, seed=0, jitter=1e-6):
+        """This layer's share of the joint predictive distribution at the test points (test block l = rows
+        test_bounds[l] of ``xs``, served by training block l), through :func:`joint_run`: blocks that were fitted
+        together and have equally many test points in ONE cimrgp_layer_joint_cov call per memory-bounded sub-batch (as
+        :meth:`predict_layer` groups them), the others as batches of one.  Returns the largest relative jitter used."""
+        calls, done = [], set()
+        esz = xs.element_size()
+        for bt in self.batches:
+            by_ns = {}
+            for i, l in enumerate(bt.regions):
+                if l in owned:
+                    a, b = (int(v) for v in test_bounds[l])
+                    by_ns.setdefault(b - a, []).append((i, a))
+            for ns, items in by_ns.items():
+                idx = [i for i, _ in items]
+                contiguous = idx == list(range(idx[0], idx[0] + len(idx)))
+                if ns <= 0 or len(items) < 2 or not contiguous:
+                    continue
+                ldc, ldw = dev.joint_ld(ns, xs.dtype), dev.joint_ld(bt.n, xs.dtype)
+                per_block = ns * (ldc + ldw) * esz + dev.potrf_workspace_bytes(ns, xs.dtype) + 16
+                free_bytes = torch.cuda.mem_get_info(xs.device)[0] + torch.cuda.memory_reserved(xs.device) \
+                    - torch.cuda.memory_allocated(xs.device)
+                per_call = int(max(1, min(len(items), (0.4 * free_bytes) // per_block)))
+                for c0 in range(0, len(items), per_call):
+                    part = items[c0:c0 + per_call]
+                    i0, nb = part[0][0], len(part)
+                    t_starts = torch.tensor([a for _, a in part], dtype=torch.int64).to(xs.device, non_blocking=True)
+                    calls.append(_JointCall([bt.regions[i] for i, _ in part], x_all, bt.starts[i0:i0 + nb], bt.n, t_starts, ns,
+                                            bt.karena[i0:i0 + nb], bt.ws_arena[i0:i0 + nb], bt.noise[i0:i0 + nb]))
+                done.update(bt.regions[i] for i, _ in items)
+        for l in sorted(owned):
+            if l not in done:
+                a, b = (int(v) for v in test_bounds[l])
+                if b > a:
+                    calls.append(single_joint_call(self.blocks[l], l, xs.device, a, b))
+        used = 0.0
+        for call in calls:
+            used = max(used, joint_run(call, self.kernel, xs, layer, add_noise, cov_out, samples, seed, jitter))
+        return used
 
     @staticmethod
     def _whole_layer(views):

@@ -26,7 +26,7 @@ import torch
 from . import device as dev
 from ._lib import COV_RBF
 from .KernelClass import RBFKernel, DenseMaternKernel
-from .Posteriors import DenseBlock, NOISE_FRACTION
+from .Posteriors import DenseBlock, NOISE_FRACTION, joint_run, single_joint_call
 
 
 def log_marginal_likelihood(x, y, ell, sf, noise, cov=COV_RBF, want_grad=True):
@@ -248,6 +248,47 @@ class GP_RBF(RegressionMethod):
         if self.preprocess:
             mean = self._reverse_trans_labels(mean)
         return mean, var
+
+
+    def _joint(self, test_data, cov_out=None, samples=None, seed=0):
+        blk = self.block
+        xs = dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, blk.x.device)
+        if self.ARD:
+            xs = (xs * self._scale).contiguous()
+        call = single_joint_call(blk, 0, xs.device, 0, xs.shape[0])
+        joint_run(call, blk.kernel, xs, 0, False, cov_out, samples, seed)
+        return xs.shape[0]
+
+    def predict_with_covariance(self, test_data):
+        """Mean (un-z-scored) and the latent joint predictive covariance (N* x N*, z-scored label units like
+        ``predict_with_variance``'s variance, which is its diagonal)."""
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        mean, _ = self._predict_mean_var(test_data, want_var=False)
+        ns = np.atleast_2d(np.asarray(test_data)).shape[0]
+        cov = torch.zeros((ns, ns), dtype=self.dtype, device=self.block.x.device)
+        self._joint(test_data, cov_out=cov)
+        cov = torch.tril(cov) + torch.tril(cov, -1).t()
+        if self.preprocess:
+            mean = self._reverse_trans_labels(mean)
+        return mean, cov.double().cpu().numpy()
+
+    def posterior_samples_f(self, test_data, size=1, seed=0):
+        """``size`` draws (size, N*, q) of the latent function in the original label units: the z-scored draw
+        mean + chol(Sigma + 1e-6 sf2 I) Z (Z_c = phi(seed, 0, c, .), c = sample * q + output; include/cimrgp_joint.h)
+        times labels_std, plus labels_mean, per output."""
+        if int(size) < 1:
+            raise ValueError('size must be at least 1')
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        mean, _ = self._predict_mean_var(test_data, want_var=False)
+        ns, q = mean.shape
+        out = torch.zeros((int(size) * q, ns), dtype=self.dtype, device=self.block.x.device)
+        self._joint(test_data, samples=out, seed=int(seed))
+        f = mean[None, :, :] + out.double().cpu().numpy().reshape(int(size), q, ns).transpose(0, 2, 1)
+        if self.preprocess:
+            f = f * self.labels_std + self.labels_mean
+        return f
 
 
 class GP_Matern(GP_RBF):

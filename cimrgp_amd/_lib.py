@@ -88,6 +88,14 @@ OBJECTIVE_SIGNATURES = {
                                          _i64, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/cimrgp_joint.h (joint covariance and samples)
+JOINT_SIGNATURES = {
+    "cimrgp_normal_fill": (_i32, [_i32, C.c_uint64, _vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp]),
+    "cimrgp_layer_joint_cov": (_i32, [_i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _dbl, _dbl, _vp, _i64, _i64, _vp,
+                                      _sz, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _sz, _vp, _vp]),
+    "cimrgp_layer_sample": (_i32, [_i32, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+}
+
 _lib = None
 
 
@@ -107,7 +115,8 @@ def load():
             "`bash cimrgp_amd/csrc/build.sh` (needs hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + \
+            list(JOINT_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if a symbol is missing
         fn.restype = res
         fn.argtypes = args

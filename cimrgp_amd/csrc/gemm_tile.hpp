@@ -16,7 +16,10 @@ constexpr int LROW     = KT_BYTES + 16;  // LDS row stride
 // EDGE = false: M, N multiples of 128 and K a multiple of the stage depth -- no bounds logic
 // at all (every select on a prefetched register makes hipcc wait for it right behind the
 // load).  EDGE = true: ragged sizes, zero-fill and predicated stores.
-template <typename T, bool LOWER, bool EDGE, int W>
+// ADD = true: C + A B^T instead (the joint sampler, joint.hip).  TRI_B = true: B is read as lower
+// triangular -- B[r][k] is taken as 0 for k > r whatever the strict upper triangle holds.  Both are
+// compile-time: with the defaults every existing instance compiles to the instructions it had before.
+template <typename T, bool LOWER, bool EDGE, int W, bool ADD = false, bool TRI_B = false>
 static __device__ __forceinline__ void gemm_tile(unsigned char* smem, T* __restrict__ C, int64_t ldc,
                                                   const T* __restrict__ A, int64_t lda,
                                                   const T* __restrict__ B, int64_t ldb,
@@ -85,6 +88,7 @@ static __device__ __forceinline__ void gemm_tile(unsigned char* smem, T* __restr
                 if (!(b_ok[p] && kin)) vb = zero4;                               \
                 if (!kfull) { va = mask_chunk<T>(va, kcol, K); vb = mask_chunk<T>(vb, kcol, K); } \
             }                                                                    \
+            if constexpr (TRI_B) vb = mask_chunk<T>(vb, kcol, col0 + sr + 32 * p + 1); \
             *reinterpret_cast<uint4*>(as_ + (sr + 32 * p) * LROW + sc * 16) = va; \
             *reinterpret_cast<uint4*>(bs_ + (sr + 32 * p) * LROW + sc * 16) = vb; \
         }                                                                        \
@@ -147,7 +151,10 @@ static __device__ __forceinline__ void gemm_tile(unsigned char* smem, T* __restr
 #pragma unroll
             for (int mi = 0; mi < W; ++mi)
 #pragma unroll
-                for (int ni = 0; ni < W; ++ni) acc[mi][ni] = X::mma_neg(a[mi], b[ni], acc[mi][ni]);
+                for (int ni = 0; ni < W; ++ni) {
+                    if constexpr (ADD) acc[mi][ni] = X::mma(a[mi], b[ni], acc[mi][ni]);
+                    else acc[mi][ni] = X::mma_neg(a[mi], b[ni], acc[mi][ni]);
+                }
         }
         if (more) CIMRGP_SWRITE((kt + 1) & 1, kt + 1);
         __syncthreads();

@@ -294,6 +294,52 @@ def layer_predict(x, starts, n, xs, t_starts, ns, ell, sf2, larena, ws_arena, z,
                                         _p(w), ldw, w.stride(0), _p(mean), _p(var), _stream()), "cimrgp_layer_predict")
 
 
+def joint_ld(cols, dtype):
+    """padded_ld, and at least 128 bytes: the row pitch of the joint calls' matrix-core operands."""
+    return max(padded_ld(cols), 128 // torch.empty((), dtype=dtype).element_size())
+
+
+def normal_fill(seed, keys, col0, cols, ns, z):
+    """Standard normals phi(seed, keys[b], col0 + c, i) into z (batch, >= cols, ldz): row c of block b holds sample
+    column col0 + c at points i < ns (cimrgp_normal_fill, include/cimrgp_joint.h).  keys: device int64 (batch,)."""
+    lib = _lib.load()
+    batch = int(z.shape[0])
+    _lib.check(lib.cimrgp_normal_fill(_DT[z.dtype], int(seed) & 0xFFFFFFFFFFFFFFFF, _p(keys), batch, int(col0), int(cols), int(ns),
+                                      _p(z), z.stride(1), z.stride(0), _stream()), "cimrgp_normal_fill")
+    return z
+
+
+def layer_joint_cov(x, starts, n, xs, t_starts, ns, ell, sf2, larena, ws_arena, diag, carena, cws_arena=None, info=None,
+                    cov=_lib.COV_RBF):
+    """Predictive covariance blocks of ``batch`` equal-sized blocks in ONE call (cimrgp_layer_joint_cov): lower(carena[b])
+    = K(xs_b, xs_b) + diag[b] I - W_b W_b^T, addressed as for :func:`layer_predict`; with ``cws_arena`` (batch, ws_bytes)
+    uint8 and ``info`` (batch,) int32 each block is factored in place and its strict upper triangle zeroed.  diag:
+    device (batch,) of the dtype, or None.  The W work area is allocated for this call only."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
+    lib = _lib.load()
+    batch = int(larena.shape[0])
+    ldw = joint_ld(n, x.dtype)
+    w = torch.empty((batch, max(int(ns), 1), ldw), dtype=x.dtype, device=x.device)
+    _lib.check(lib.cimrgp_layer_joint_cov(_DT[x.dtype], cov, _p(x), _p(starts), int(n), int(x.shape[1]), _p(xs), _p(t_starts),
+                                          int(ns), batch, float(ell), float(sf2), _p(larena), larena.stride(1), larena.stride(0),
+                                          _p(ws_arena), ws_arena.stride(0), _p(diag), _p(w), ldw, w.stride(0), _p(carena),
+                                          carena.stride(1), carena.stride(0), _p(cws_arena),
+                                          0 if cws_arena is None else cws_arena.stride(0), _p(info), _stream()),
+               "cimrgp_layer_joint_cov")
+    return carena
+
+
+def layer_sample(larena, ns, z, cols, t_starts, out):
+    """out[c, t_starts[b] + i] += sum_{k <= i} L_b[i, k] z[b, c, k] for c < cols (cimrgp_layer_sample): larena
+    (batch, >= ns, ldl) factors, z (batch, >= cols, ldz) normals, out (cols, ld_out) shared by the blocks."""
+    lib = _lib.load()
+    batch = int(larena.shape[0])
+    _lib.check(lib.cimrgp_layer_sample(_DT[larena.dtype], _p(larena), larena.stride(1), larena.stride(0), int(ns), batch, _p(z),
+                                       z.stride(1), z.stride(0), int(cols), _p(t_starts), _p(out), out.stride(0), _stream()),
+               "cimrgp_layer_sample")
+    return out
+
+
 def layer_lml_scratch_bytes(n, q, batch, dtype):
     return int(_lib.load().cimrgp_layer_lml_grad_scratch_bytes(_DT[dtype], int(n), int(q), int(batch)))
 

@@ -464,4 +464,7 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
 /* The hyper-parameter objective of a layer's blocks (cimrgp_layer_lml_grad_cov): include/cimrgp_objective.h. */
 #include "cimrgp_objective.h"
 
+/* The joint predictive covariance of a layer's blocks and posterior samples: include/cimrgp_joint.h. */
+#include "cimrgp_joint.h"
+
 #endif /* CIMRGP_H */
