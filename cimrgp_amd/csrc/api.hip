@@ -32,36 +32,21 @@ const Knobs& knobs()
         Knobs v;
 #ifdef CIMRGP_TUNING
         auto num = [](const char* name, int64_t dflt) { const char* e = getenv(name); return e ? (int64_t)atoll(e) : dflt; };
-        const char* c = getenv("CIMRGP_CHAIN");
-        v.chain_mode = !c ? 0 : (c[0] == 's' ? 1 : c[0] == 'w' ? 2 : c[0] == 'q' ? 3 : 0);
         v.tail_below = num("CIMRGP_TAIL_BELOW", v.tail_below);
         v.rows_start_below = num("CIMRGP_ROWS_START", v.rows_start_below);
         v.rows_start_below_early = num("CIMRGP_ROWS_START_EARLY", v.rows_start_below_early);
-        v.head_first_above = num("CIMRGP_HEAD_FIRST", v.head_first_above);
         v.far_pair_above = num("CIMRGP_FAR_PAIR", v.far_pair_above);
-        v.fused_head0 = (int)num("CIMRGP_HEAD0", v.fused_head0);
         v.gemm_pers = (int)num("CIMRGP_GEMM_PERS", v.gemm_pers);
-        v.gemm_pers_f32 = (int)num("CIMRGP_GEMM_PERS_F32", v.gemm_pers_f32);
         v.pers_min_tiles = (int)num("CIMRGP_PERS_MIN_TILES", v.pers_min_tiles);
         v.chain_cus = (int)num("CIMRGP_CHAIN_CUS", v.chain_cus);
         v.pers_max_chunks = (int)num("CIMRGP_PERS_CHUNKS", v.pers_max_chunks);
-        v.head_direct_max_rounds = (int)num("CIMRGP_HEAD_DIRECT", v.head_direct_max_rounds);
-        v.post_final = (int)num("CIMRGP_POST_FINAL", v.post_final);
-        v.heads_beside_rows = (int)num("CIMRGP_HEADS_ROWS", v.heads_beside_rows);
-        v.early_first_panel = (int)num("CIMRGP_EARLY_PANEL", v.early_first_panel);
         v.early_panels = (int)num("CIMRGP_EARLY_PANELS", v.early_panels);
         v.early_cus = (int)num("CIMRGP_EARLY_CUS", v.early_cus);
-        v.pers_flex_cus = (int)num("CIMRGP_PERS_FLEX", v.pers_flex_cus);
-        v.pers_flex_min_rounds = (int)num("CIMRGP_PERS_FLEX_MIN", v.pers_flex_min_rounds);
-        v.rows_fused_tail = (int)num("CIMRGP_ROWS_FUSED", v.rows_fused_tail);
         v.rows_pair_above = num("CIMRGP_ROWS_PAIR", v.rows_pair_above);
         v.fused_max_chain_wgs = num("CIMRGP_FUSED_MAX", v.fused_max_chain_wgs);
         v.batch_halves_min = (int)num("CIMRGP_BATCH_HALVES", v.batch_halves_min);
         v.rows_cus = (int)num("CIMRGP_ROWS_CUS", v.rows_cus);
-        v.rows_step = (int)num("CIMRGP_ROWS_STEP", v.rows_step);
-        v.rider_lean = (int)num("CIMRGP_RIDER_LEAN", v.rider_lean);
         v.rider_round_us = (int)num("CIMRGP_RIDER_ROUND", v.rider_round_us);
-        v.trsm_group = (int)num("CIMRGP_TRSM_GROUP", v.trsm_group);
         v.rows_beside_tail_below = num("CIMRGP_ROWS_BESIDE", v.rows_beside_tail_below);
         v.tail_far_cus = (int)num("CIMRGP_TAIL_FAR_CUS", v.tail_far_cus);
         v.tail_far_min_rows = num("CIMRGP_TAIL_FAR_MIN", v.tail_far_min_rows);

@@ -23,15 +23,6 @@ int  check_hip(hipError_t e, const char* fn, const char* what);
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-#ifdef CIMRGP_STAMP   // diagnostic builds only (tools/diag_probe.hip): phase stamps of workgroup 0
-__device__ long long g_stamp[32];
-#define STAMP(n) do { if (threadIdx.x == 0 && blockIdx.x == 0) g_stamp[n] = __builtin_amdgcn_s_memtime(); } while (0)
-#define STAMPW(n, wv) do { if (threadIdx.x == 64 * (wv) && blockIdx.x == 0) g_stamp[n] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define STAMP(n) do { } while (0)
-#define STAMPW(n, wv) do { } while (0)
-#endif
-
 // ------------------------------------------------------------ MFMA traits ----
 // 16x16x4 matrix-core tiles, one 8-byte "k-slot" per lane per operand:
 //   lane l supplies A[row = l & 15][kslot = l >> 4] and B^T[col = l & 15][kslot = l >> 4].
@@ -102,7 +93,7 @@ static __device__ __forceinline__ void lds_barrier()
 // lds_settle: a wave that has just WRITTEN words other waves will read behind the next barrier reads one of them back
 // first (the last one it wrote, or any LDS word: the LDS executes one wave's accesses in issue order, so the load's
 // data can only return once every earlier store of the wave has been performed).  Round 5: measured on gfx950 with a
-// second workgroup on the compute unit (tools/lab/race_probe.hip, HISTORY.md): the LAST one or two ds_write
+// second workgroup on the compute unit (HISTORY.md, round 5): the LAST one or two ds_write
 // instructions a wave issued ahead of `s_waitcnt lgkmcnt(0); s_barrier` were not yet in the LDS array when another
 // wave's ds_read, issued right behind the barrier, read their words -- it got, bit for bit, what the words held before
 // (1.7-3 % of panel chains beside an FP32 trailing update; 0 of 1999 with the read-back).  The wait for a STORE's
@@ -113,19 +104,6 @@ static __device__ __forceinline__ void lds_settle(const T* written)
     const volatile T* p = written;
     const T v = *p;
     asm volatile("" :: "v"(v));          // the value is "used": the wait for it stays ahead of whatever follows
-}
-
-// lds_barrier_nowait: the barrier WITHOUT the wait for this wave's LDS traffic, for the one place that needs it: a
-// buffer every wave has finished READING (each read's value has been consumed by an instruction ahead of the barrier,
-// so the read itself is complete) is rewritten behind the barrier, while reads of ANOTHER buffer may stay in flight
-// across it.  The compiler-only fences (no instruction) keep the compiler from moving or caching LDS accesses across
-// the barrier; the hardware orders the rest: a wave's LDS write issued behind s_barrier cannot overtake a read
-// another wave completed ahead of it.
-static __device__ __forceinline__ void lds_barrier_nowait()
-{
-    __atomic_signal_fence(__ATOMIC_SEQ_CST);
-    __builtin_amdgcn_s_barrier();
-    __atomic_signal_fence(__ATOMIC_SEQ_CST);
 }
 
 // Zero the elements of a 16-byte chunk whose k index is >= kvalid.
@@ -161,48 +139,30 @@ template <> __device__ __forceinline__ uint4 neg_chunk<float>(uint4 v)
 // builds behind profiles/ and tools/sweep_*.sh) each CIMRGP_* environment variable named here overrides
 // its default once, at the first use.
 struct Knobs {
-    int chain_mode = 0;                    // CIMRGP_CHAIN = split | wide | quad: 1 round-1 links / 2 nine-wave / 3 four-wave (0: by context)
     int64_t tail_below = 4864;             // CIMRGP_TAIL_BELOW: trailing matrix at or below this: finish on one queue
     int64_t rows_start_below = 6144;       // CIMRGP_ROWS_START: carried rows start once the trailing matrix is smaller
     int64_t rows_start_below_early = 5632; // CIMRGP_ROWS_START_EARLY: ... in a factorisation that started with early panels (round 5, one box: 6144 / 5632 -> 144.1 / 145.4, 144.5 / 145.1, 144.3 / 145.2; a lone factorisation: 136.8 / 134.4 the other way)
-    int64_t head_first_above = 1ll << 30;  // CIMRGP_HEAD_FIRST: bulk update waits for the head above this (off)
     int64_t far_pair_above = 8192;         // CIMRGP_FAR_PAIR: far part updated once per group of panels above this
-    int fused_head0 = 1;                   // CIMRGP_HEAD0: first diagonal block of a panel takes its head update itself
     int gemm_pers = 256;                   // CIMRGP_GEMM_PERS: persistent trailing update on at most this many compute units (0: off)
-    int gemm_pers_f32 = 0;                 // CIMRGP_GEMM_PERS_F32: the persistent update for FP32 too (8-stage passes; built and bit-checked in round 4, not faster than the tile kernel: 3.85 against 3.64 ms for potrf n = 8192, 16.5 against 16.3 at 16 384)
     int pers_min_tiles = 512;              // CIMRGP_PERS_MIN_TILES: 128-tiles below which the tile-per-workgroup kernel is used
-    int rows_fused_tail = 0;               // CIMRGP_ROWS_FUSED: carried rows catch up at the tail switch, then ride in the chain's launches
     int64_t rows_pair_above = 8192;        // CIMRGP_ROWS_PAIR: the carried rows' far updates take two panels at a time (K = 512) while more columns remain
     int64_t fused_max_chain_wgs = 768;     // CIMRGP_FUSED_MAX: one-queue sweeps ride their updates in the chain's launches while batch x n / 32 is at most this
     int batch_halves_min = 8;              // CIMRGP_BATCH_HALVES: a batched factorisation of at least this many blocks (that does not ride) runs as two halves on two queues
-    int rows_step = 1;                     // CIMRGP_ROWS_STEP: carried rows' chain as one launch per panel (k_rows_step: previous panel's update + 256-wide solve; 0: update and k_trsm256 as two launches)
-    int rider_lean = 1;                    // CIMRGP_RIDER_LEAN: one-queue sweeps give rounds of K = 256 riders to the links first (0: every launch starts with one round)
     int rider_round_us = 25;               // CIMRGP_RIDER_ROUND: modelled duration of one round of K = 256 rider tiles (us)
     int rows_cus = 192;                    // CIMRGP_ROWS_CUS: compute units of the carried rows' far updates (persistent kernel; 0: tile-per-workgroup kernel).
                                            // Round 5, one box (profiles/r05_knob_scan.txt): 128 / 160 / 176 / 192 / 208 / 224 / 256 -> 132.0 / 135.8 / 135.8 / 136.8 / 135.4 / 133.4 /
                                            // 130.4 posteriors/s -- two persistent workgroups fill a unit's LDS, and the chain's workgroups need units that hold at most one
-    int trsm_group = 1;                    // CIMRGP_TRSM_GROUP: batched launches solve 4 row tiles per workgroup (0: one)
     int64_t rows_beside_tail_below = 2560; // CIMRGP_ROWS_BESIDE: with carried rows, the factorisation's tail (trailing matrix at most this) is the one-queue fused sweep while the rows keep their own queues (0: look-ahead to the end)
     int tail_far_cus = 160;                // CIMRGP_TAIL_FAR_CUS: compute units of FAR(prev) on the second queue of the fused tail (0: always riders)
     int64_t tail_far_min_rows = 2048;      // CIMRGP_TAIL_FAR_MIN: ... while at least this many rows remain beyond the next panel
     int chain_cus = 32;                    // CIMRGP_CHAIN_CUS: compute units the bulk update leaves to the panel chain (look-ahead phase)
     int pers_max_chunks = 2;               // CIMRGP_PERS_CHUNKS: the persistent update takes K up to this many panels (256 columns each) in one pass per tile (1: K = 256 only, as in rounds 3-4;
                                            // round 5, one box: potrf n = 12 288 / 16 384 13.80 / 28.51 -> 13.45 / 27.79 ms with 2-3; n = 32 768, whose groups are K = 768: 191.8 -> 200.1 ms with 3 -- so 2)
-    int early_first_panel = 1;             // CIMRGP_EARLY_PANEL: a staged call whose front end ran on the context's chain queue factors its first panel there, in queue order (0: behind the factorisation's stream)
-    int early_panels = 8;                  // CIMRGP_EARLY_PANELS: ... and this many further panels (update + next panel) one-queue style on the chain queue before the
+    int early_panels = 8;                  // CIMRGP_EARLY_PANELS: a staged call whose front end ran on the context's chain queue factors its first panel there, in queue order,
+                                           // and this many further panels (update + next panel) one-queue style on the chain queue before the
                                            // look-ahead schedule takes over.  Round 5, one box (profiles/r05_early_panels.txt): 0 / 2 / 4 / 6 / 8 / 10 / 12 / 14 ->
                                            // 137.7 / 139.8 / 140.5 / 143.1 / 143.6 / 143.8 / 141.5 / 138.8 posteriors/s
     int early_cus = 256;                   // CIMRGP_EARLY_CUS: compute units of those early updates (0: the look-ahead phase's share; no chain of their own factorisation runs beside them: 224 -> 256: 144.4 -> 145.0, 145.1 -> 146.1)
-    int heads_beside_rows = 0;             // CIMRGP_HEADS_ROWS: the combined head + bulk launch also while the carried rows are running (round 5, rows on 192 units: 137.2 -> 135.4 / 134.3 posteriors/s: off)
-    int post_final = 0;                    // CIMRGP_POST_FINAL: the look-ahead's chain posts "panel final" in a device word and a gate on the update's queue waits for it
-                                           // (0: an event between the queues, rounds 1-4).  Round 5: potrf n = 8192 5.43 -> 5.38 ms, the step unchanged -- and OFF, because
-                                           // rocprofv3's counter passes serialise kernels in the order their QUEUES become ready, not in submission order: the gate, first in
-                                           // its queue the moment the previous update ends, is run before the chain's remaining kernels and k_post three deep in theirs, and
-                                           // waits out its 2-s watchdog.  (The chain's own gate never meets that: the update it waits for is ready long before it.)
-    int head_direct_max_rounds = 0;        // CIMRGP_HEAD_DIRECT: a head-first persistent update of at most this many rounds stores its head tiles at the end of their own pass (0: always streamed under the next pass)
-    int pers_flex_cus = 0;                 // CIMRGP_PERS_FLEX: a persistent update may take up to this many units beyond its share when that saves a whole round of tiles ...
-    int pers_flex_min_rounds = 7;          // CIMRGP_PERS_FLEX_MIN: ... of a launch of at least this many rounds.  OFF: measured in round 5 (profiles/r05_flex_scan.txt): the updates
-                                           // get 4-8 % shorter (5 of the 83 rounds of a look-ahead phase at n = 8192 go), the step 2-3 % LONGER -- the panel chain needs its 32 units
 };
 const Knobs& knobs();
 // Queues for the carried rows of cimrgp_potrf_rows (1 or 2): cimrgp_set_rows_queues in include/cimrgp.h.

@@ -94,7 +94,7 @@ static __device__ __forceinline__ int pers_div(int q, int d)
 }
 
 // Closed form, straight-line (round 5: the strip-by-strip search loop of rounds 3-4 was ~350 scalar instructions per
-// tile and wave, and eight waves share one scalar unit: 1800 of a tile's 72 000 clocks, tools/lab/pers_stamps.py).
+// tile and wave, and eight waves share one scalar unit: 1800 of a tile's 72 000 clocks, HISTORY.md).
 // LOWER: full strips hold 16 s + 10 tiles, so strip s starts at tile 8 s^2 + 2 s.
 template <bool LOWER>
 static __device__ __forceinline__ void pers_tile_decode(int q, int tiles_m, int tiles_n, int& ti, int& tj)
@@ -178,40 +178,9 @@ static __device__ __forceinline__ int pers_tile_number(int w, int i, int grid, i
 // flight.  (With the events inside a switch over the stage number hipcc waited for vmcnt(0) at the top
 // of every stage, and every stage then took a full HBM round trip under load: 40 against 45 TF/s for
 // the tile-per-workgroup kernel.)
-// Timing-only builds (tools/exp_variants.sh; 1-6 give WRONG results, never the shipped library):
-// -DPERS_EXP=1 no second barrier, 2 no barriers at all, 3 no C events, 4 C loads only, 5 C stores only,
-// 6 C loads always from the tile's first rows (L2 hits), 7 / 8 the C event issued in the middle / at the
-// end of the stage instead of its head (correct results).  Measured at M=7936, K=256 (DESIGN.md section 4,
-// round 3 (1); profiles/r03_pers_variants.txt): without the C events the pass is ~10 % shorter, with only the
-// loads or only the stores ~4 %, without the barriers 2-4 %, and moving the event within the stage changes
-// nothing: the cost of streaming C is the memory pipeline's share of the issue slots, not where in the stage
-// the accesses sit and not the barriers.
-#ifndef PERS_EXP
-#define PERS_EXP 0
-#endif
-#ifndef PERS_SYNC_FLAGS
-#define PERS_SYNC_FLAGS 1
-#endif
-// Round 5: the two barriers of a stage are fences + s_barrier (common.hpp), no longer inline assembly whose "memory"
-// clobber the compiler does not apply to a __shared__ array whose address never escapes (the operand ring here).
-#if PERS_EXP == 1
-#define PERS_BARRIER_A() lds_barrier()
-#define PERS_BARRIER_B() do { } while (0)
-#elif PERS_EXP == 2
-#define PERS_BARRIER_A() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local")
-#define PERS_BARRIER_B() do { } while (0)
-#else
-#define PERS_BARRIER_A() lds_barrier()              /* stage kt+1's LDS writes are done: s_waitcnt lgkmcnt(0); s_barrier */
-#define PERS_BARRIER_B() lds_barrier_nowait()       /* every wave has consumed stage kt's fragments: s_barrier alone */
-#endif
-#ifdef PERS_STAMPS          /* diagnostic build (tools/lab/pers_stamps.py): shader-clock stamps of wave 0 at every stage's first barrier, first 8 tiles of every workgroup */
-__device__ long long g_pers_stamp[256][8 * 16 + 4];
-#define PERS_STAMP(slot_) do { if (tid == 0 && it < 8) g_pers_stamp[wg & 255][slot_] = __builtin_amdgcn_s_memtime(); } while (0)
-#define PERS_STAMP_EXIT() do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if (tid == 0) { g_pers_stamp[wg & 255][129] = __builtin_amdgcn_s_memtime(); g_pers_stamp[wg & 255][131] = __builtin_amdgcn_s_memrealtime(); } } while (0)
-#else
-#define PERS_STAMP(slot_) do { } while (0)
-#define PERS_STAMP_EXIT() do { } while (0)
-#endif
+// Round 3, M = 7936, K = 256 (profiles/r03_pers_variants.txt, HISTORY.md): without the C events a pass is ~10 %
+// shorter, with only their loads or stores ~4 %, without the barriers 2-4 %; where in the stage the event sits changes
+// nothing -- streaming C costs the memory pipeline's share of the issue slots.
 // A tile of C as a raw buffer: base = the tile's first element (wave-uniform), no stride, the largest extent (a lane's
 // offsets stay below 2^31: the launcher checks 128 rows of C against it).
 static __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const void* p)
@@ -257,7 +226,7 @@ template <typename T, bool LOWER, int NKT, bool MULTI = false>
 __global__ __launch_bounds__(PERS_THREADS)
 void k_gemm_nt_pers(T* __restrict__ C, int64_t ldc, const T* __restrict__ A, int64_t lda,
                     const T* __restrict__ B, int64_t ldb, int tiles_m, int tiles_n, int ntiles, int heads, int* __restrict__ flag,
-                    int head_direct, int nkc)
+                    int nkc)
 {
     static_assert(NKT == 16 || NKT == 8, "sixteen C events per tile: one or two per K stage");
     constexpr int EVS = 16 / NKT;                            // C events per stage
@@ -306,15 +275,11 @@ void k_gemm_nt_pers(T* __restrict__ C, int64_t ldc, const T* __restrict__ A, int
             __hip_atomic_fetch_add(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     };
-#ifdef PERS_STAMPS
-    if (tid == 0) { g_pers_stamp[wg & 255][128] = __builtin_amdgcn_s_memtime(); g_pers_stamp[wg & 255][130] = __builtin_amdgcn_s_memrealtime(); }
-#endif
-#if PERS_SYNC_FLAGS
     // Stage hand-offs by FLAGS in LDS instead of s_barrier (round 5).  A wave posts its stage number in its own word
     // right behind the LDS accesses the others wait for (the LDS executes a wave's accesses in issue order, so when the
     // post is visible those accesses have been performed) and polls the eight words where it used to stop at a barrier;
-    // the poll's read is issued one multiply group ahead of its test.  Measured with the stamped builds
-    // (tools/lab/pers_stamps.py): the two barriers of a stage cost ~250 of its ~4530 clocks -- a wave that arrives at
+    // the poll's read is issued one multiply group ahead of its test.  Measured with shader-clock stamps (HISTORY.md,
+    // round 5): the two barriers of a stage cost ~250 of its ~4530 clocks -- a wave that arrives at
     // s_barrier LAST finds its SIMD partner already waiting, and the matrix core then idles for the barrier's round trip.
     __shared__ int flag_a[8], flag_b[8];           // a: my share of the next stage is written; b: my last fragment reads of this stage are issued
     if (tid < 8) { flag_a[tid] = -1; flag_b[tid] = -1; }
@@ -331,7 +296,6 @@ void k_gemm_nt_pers(T* __restrict__ C, int64_t ldc, const T* __restrict__ A, int
             while (__builtin_amdgcn_ballot_w64(v_ - (g_) < 0) != 0ull) v_ = PERS_PEEK(flag_);                    \
             __atomic_signal_fence(__ATOMIC_SEQ_CST);                                                             \
         } while (0)
-#endif
     int it = 0;                                   // this workgroup's tile counter
     int t = pers_tile_number(wg, it, grid, ntiles);
     if (t < 0) return;
@@ -342,7 +306,7 @@ void k_gemm_nt_pers(T* __restrict__ C, int64_t ldc, const T* __restrict__ A, int
     int t_nx = pers_tile_number(wg, 1, grid, ntiles), ti_nx = ti, tj_nx = tj;
     if (t_nx >= 0) decode(t_nx, ti_nx, tj_nx);
     bool prev_head = false;                       // the tile being stored during this pass is one the chain waits for
-    bool prv_stored = true;                       // nothing to store for the "previous tile" of this pass: the first pass, or a head tile stored directly already (head_direct)
+    bool prv_stored = true;                       // nothing to store for the "previous tile" of this pass: the first pass
     T* c_cur = C + (int64_t)ti * GT * ldc + (int64_t)tj * GT;
     const T* a_cur = A + (int64_t)ti * GT * lda;
     const T* b_cur = B + (int64_t)tj * GT * ldb;
@@ -431,21 +395,18 @@ void k_gemm_nt_pers(T* __restrict__ C, int64_t ldc, const T* __restrict__ A, int
     // tile, which is stored and replaced by the next tile's C as the K loop proceeds.  The ring position
     // of a stage is its number's parity (16 stages per tile).
 #define PERS_EVENT_ONE(oth_, e_)                                                                         \
-        if (PERS_EXP != 3) {                    /* event e_ (compile-time after unrolling) */                   \
+        {                                       /* event e_ (compile-time after unrolling) */                   \
                 const int mi_ = (e_) >> 2, ne_ = ((e_) >> 1) & 1, r0_ = 2 * ((e_) & 1);                         \
                 /* buffer addressing (round 5): the tile's descriptor (SGPRs, rebuilt per tile by scalar code) + this */ \
                 /* lane's constant 32-bit byte offset + a wave-uniform scalar offset for the event: NO vector     */ \
                 /* instruction per access (the 64-bit flat address took a v_lshl_add_u64 for each of the four)    */ \
                 const int so0_ = (mi_ * 16 + RS * r0_) * row_bytes + ne_ * 16 * (int)sizeof(T);                 \
                 const int so1_ = so0_ + RS * row_bytes;                                                         \
-                if (PERS_EXP != 4) {                                                                            \
-                    cbuf_store<T>(oth_[mi_][ne_][r0_], rs_prv, cbyte0, so0_);                                   \
-                    cbuf_store<T>(oth_[mi_][ne_][r0_ + 1], rs_prv, cbyte0, so1_);                               \
-                }                                                                                               \
-                if (PERS_EXP != 5) {            /* straight into the set just stored from: nobody reads it before the next pass */ \
-                    oth_[mi_][ne_][r0_] = cbuf_load<T>(rs_nxt, cbyte0, (PERS_EXP == 6) ? 0 : so0_);             \
-                    oth_[mi_][ne_][r0_ + 1] = cbuf_load<T>(rs_nxt, cbyte0, (PERS_EXP == 6) ? 0 : so1_);         \
-                }                                                                                               \
+                cbuf_store<T>(oth_[mi_][ne_][r0_], rs_prv, cbyte0, so0_);                                       \
+                cbuf_store<T>(oth_[mi_][ne_][r0_ + 1], rs_prv, cbyte0, so1_);                                   \
+                /* straight into the set just stored from: nobody reads it before the next pass */              \
+                oth_[mi_][ne_][r0_] = cbuf_load<T>(rs_nxt, cbyte0, so0_);                                       \
+                oth_[mi_][ne_][r0_ + 1] = cbuf_load<T>(rs_nxt, cbyte0, so1_);                                   \
             }
     /* the stage's events: one (NKT = 16) or two (NKT = 8) */
 #define PERS_EVENT_BLOCK(oth_)                                                                                  \
@@ -454,23 +415,13 @@ void k_gemm_nt_pers(T* __restrict__ C, int64_t ldc, const T* __restrict__ A, int
             PERS_SWRITE(((kt_) & 1) ^ 1);           /* stage kt+1, in registers since the previous stage */     \
             if ((kt_) + 2 < NKT) PERS_GLOAD(a_chk, b_chk, (kt_) + 2)    /* stage kt+2 -> registers */            \
             else                 PERS_GLOAD(a_adv, b_adv, (kt_) + 2 - NKT)   /* ... of the next chunk of K, or of the next tile */
-#if PERS_SYNC_FLAGS
 #define PERS_SYNC_TOP()      PERS_WAIT(flag_b, seen_b, gstage - 1);
 #define PERS_SYNC_WRITTEN()  PERS_POST(flag_a);
 #define PERS_SYNC_READ()     PERS_POST(flag_b); seen_a = PERS_PEEK(flag_a); __builtin_amdgcn_sched_barrier(0);
-#undef PERS_BARRIER_A
-#undef PERS_BARRIER_B
 #define PERS_BARRIER_A()     PERS_WAIT(flag_a, seen_a, gstage)
 #define PERS_BARRIER_B()     do { } while (0)
 #define PERS_SYNC_PEEK_B()   seen_b = PERS_PEEK(flag_b); __builtin_amdgcn_sched_barrier(0);
 #define PERS_SYNC_NEXT()     ++gstage;
-#else
-#define PERS_SYNC_TOP()
-#define PERS_SYNC_WRITTEN()
-#define PERS_SYNC_READ()
-#define PERS_SYNC_PEEK_B()
-#define PERS_SYNC_NEXT()
-#endif
 #define PERS_PASS(cur_, oth_)                                                                                   \
     {                                                                                                           \
         const int tn_ = t_nx;                                                                                   \
@@ -486,8 +437,6 @@ void k_gemm_nt_pers(T* __restrict__ C, int64_t ldc, const T* __restrict__ A, int
         /* the next tile's values again (the same values into the same registers).                                 */ \
         for (int kc = 0; kc < (MULTI ? nkc : 1); ++kc) {                                                        \
         const bool lastc = !MULTI || (kc + 1 == nkc);                                                           \
-        /* a head tile stored directly at the end of its own pass (head_direct) must NOT be stored again by this  */ \
-        /* pass's events -- the panel chain may be rewriting it already: no extent, the stores drop              */ \
         const __amdgpu_buffer_rsrc_t rs_prv = (prv_stored || kc > 0) ? tile_rsrc_null(c_prv) : tile_rsrc(c_prv); \
         const T* a_chk = a_cur + kc * (NKT * BKE);                                                              \
         const T* b_chk = b_cur + kc * (NKT * BKE);                                                              \
@@ -501,24 +450,21 @@ void k_gemm_nt_pers(T* __restrict__ C, int64_t ldc, const T* __restrict__ A, int
             PERS_SYNC_TOP()                          /* flags: everyone's reads of the buffer written below are issued */ \
             PERS_STAGE_OPERANDS(kt)                                                                             \
             PERS_SYNC_WRITTEN()                      /* flags: my share of stage kt+1 is behind me */            \
-            if (PERS_EXP != 7 && PERS_EXP != 8) PERS_EVENT_BLOCK(oth_)                                          \
+            PERS_EVENT_BLOCK(oth_)                                                                              \
             /* k-step s+1's fragments are requested before k-step s is multiplied (the scheduler is fenced */  \
             /* so that it cannot fold the pairs back into read -> wait -> multiply)                        */  \
             PERS_FRAGS_NF(1, kt & 1, 1);                                                                        \
             PERS_MMA_NF(cur_, 0);                                                                               \
             PERS_INTERLEAVE();                                                                                  \
             PERS_FRAGS(0, kt & 1, 2);                                                                           \
-            if (PERS_EXP == 7) { PERS_EVENT_BLOCK(oth_) PERS_MMA_NF(cur_, 1); PERS_INTERLEAVE(); }                  \
-            else PERS_MMA(cur_, 1);                                                                             \
+            PERS_MMA(cur_, 1);                                                                                  \
             PERS_FRAGS(1, kt & 1, 3);                                                                           \
             PERS_SYNC_READ()                         /* flags: my last reads of stage kt are issued; peek at the others' writes */ \
             PERS_MMA(cur_, 0);                                                                                  \
             PERS_BARRIER_A();                                                    /* stage kt+1 is in LDS */     \
-            PERS_STAMP(it * 16 + kt);                                                                                   \
             PERS_FRAGS(0, (kt & 1) ^ 1, 0);         /* first fragments of stage kt+1 */                         \
             PERS_SYNC_PEEK_B()                       /* flags: a look at the others' last reads, tested at the top of the next stage */ \
-            if (PERS_EXP == 8) { PERS_EVENT_BLOCK(oth_) PERS_MMA_NF(cur_, 1); PERS_INTERLEAVE(); }                  \
-            else PERS_MMA(cur_, 1);                                                                             \
+            PERS_MMA(cur_, 1);                                                                                  \
             PERS_BARRIER_B();                        /* everyone has read stage kt: its buffer may be rewritten */ \
             PERS_SYNC_NEXT()                                                                                    \
         }                                                                                                       \
@@ -533,28 +479,14 @@ void k_gemm_nt_pers(T* __restrict__ C, int64_t ldc, const T* __restrict__ A, int
                     _Pragma("unroll") for (int r = 0; r < 4; ++r)                                               \
                         (c_cur + ((int64_t)(mi * 16 + RS * r) * ldc + ni * 16))[coff] = cur_[mi][ni][r];        \
             if (prev_head) signal_stored();                                                                     \
-            PERS_STAMP_EXIT();                                                                                  \
             return;                                                                                             \
         }                                                                                                       \
         prv_stored = false;                                                                                     \
-        if (head_direct && prev_head) {                                                                         \
-            /* the chain waits for this tile: out with it now instead of under the next pass (its round trip is   */ \
-            /* not hidden: only launches whose chain is the longer path ask for this, gemm_nt_sub)                */ \
-            _Pragma("unroll") for (int mi = 0; mi < 4; ++mi)                                                    \
-                _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                \
-                    _Pragma("unroll") for (int r = 0; r < 4; ++r)                                               \
-                        (c_cur + ((int64_t)(mi * 16 + RS * r) * ldc + ni * 16))[coff] = cur_[mi][ni][r];        \
-            signal_stored();                                                                                    \
-            prev_head = false;                                                                                  \
-            prv_stored = true;                                                                                  \
-        }                                                                                                       \
         t = tn_; ti = ni_; tj = nj_; ++it;                                                                      \
         c_cur = const_cast<T*>(c_nxt); a_cur = a_nxt; b_cur = b_nxt;                                            \
     }
 
-#if PERS_SYNC_FLAGS
     int seen_a = -1, seen_b = -1;                  // the flags as last peeked at (re-read in the wait if not there yet)
-#endif
     for (;;) {
         PERS_PASS(acc0, acc1)
         PERS_PASS(acc1, acc0)
@@ -566,6 +498,8 @@ void k_gemm_nt_pers(T* __restrict__ C, int64_t ldc, const T* __restrict__ A, int
 #undef PERS_SYNC_READ
 #undef PERS_SYNC_PEEK_B
 #undef PERS_SYNC_NEXT
+#undef PERS_BARRIER_A
+#undef PERS_BARRIER_B
 #undef PERS_EVENT_BLOCK
 #undef PERS_EVENT_ONE
 #undef PERS_INTERLEAVE
@@ -679,9 +613,9 @@ static int gemm_launch(T* c, int64_t ldc, const T* a, int64_t lda, const T* b, i
 // head tiles it then signals.
 int gemm_pers_head_tiles(int64_t m, int k, int elem_bytes)
 {
+    if (elem_bytes != 8) return 0;                     // FP32 updates use the tile kernel (gemm_nt_sub)
     const int bke = KT_BYTES / elem_bytes;
-    const int pers_nkt = (elem_bytes == 8) ? PERS_STAGES : PERS_STAGES / 2;
-    if (knobs().gemm_pers < 8 || (elem_bytes != 8 && !knobs().gemm_pers_f32) || m % 128 != 0 || m / 128 < 3 || k % bke != 0 || k / bke != pers_nkt) return 0;
+    if (knobs().gemm_pers < 8 || m % 128 != 0 || m / 128 < 3 || k % bke != 0 || k / bke != PERS_STAGES) return 0;
     return (int)(2 * (m / 128) - 2);
 }
 
@@ -721,17 +655,15 @@ int gemm_nt_sub(T* c, int64_t ldc, const T* a, int64_t lda, const T* b, int64_t 
     // tiny updates on the factorisation's critical path (the 256 x 256 diagonal block): 32-tiles, so
     // that the K loop of a tile is 1/4 as long and ~36 compute units share it instead of 10
     const int64_t t64 = ((m + 63) / 64) * ((n + 63) / 64) / (lower ? 2 : 1) * bt.count;
-    // the persistent form: full 128-tiles only, enough of them to give every workgroup several
-    {
+    // the persistent form: full 128-tiles only, enough of them to give every workgroup several.  FP64 only: the FP32
+    // form was slower inside the factorisation (potrf n = 8192 3.83 against 3.70 ms: HISTORY.md, round 5).
+    if constexpr (sizeof(T) == 8) {
         constexpr int bke = KT_BYTES / (int)sizeof(T);
         const int want = (bt.pers >= 0) ? bt.pers : knobs().gemm_pers;
         const int nkt = (k % bke) ? 0 : k / bke;
-        // one panel in either precision: 16 stages of doubles, 8 of floats.  The FP32 form is off by default
-        // (knobs().gemm_pers_f32): stand-alone it equals the tile kernel (0.52-0.58 of the FP32 peak both), inside the
-        // factorisation it is slower (3.85 against 3.64 ms at n = 8192): HISTORY.md, round 4.
-        constexpr int pers_nkt = (sizeof(T) == 8) ? PERS_STAGES : PERS_STAGES / 2;
+        constexpr int pers_nkt = PERS_STAGES;
         const int nkc = (nkt > 0 && nkt % pers_nkt == 0) ? nkt / pers_nkt : 0;       // chunks of one panel's K (256 columns)
-        if (want >= 8 && (sizeof(T) == 8 || knobs().gemm_pers_f32) && nkc >= 1 && nkc <= knobs().pers_max_chunks && (nkc == 1 || !bt.head_first) &&
+        if (want >= 8 && nkc >= 1 && nkc <= knobs().pers_max_chunks && (nkc == 1 || !bt.head_first) &&
             bt.count == 1 && !bt.skip_first && m % 128 == 0 && n % 128 == 0 &&
             ldc < (1ll << 20) && lda < (1ll << 23) && ldb < (1ll << 23) && (t128 >= knobs().pers_min_tiles || bt.head_first || bt.pers_force)) {
             // (ldc: 128 rows of C stay below 2^31 bytes -- the C stream addresses a tile through a raw buffer with 32-bit offsets)
@@ -741,24 +673,16 @@ int gemm_nt_sub(T* c, int64_t ldc, const T* a, int64_t lda, const T* b, int64_t 
             CIMRGP_REQUIRE(!bt.head_first || heads > 0, fn, "a head-first update needs a lower update of at least 3 x 3 tiles");
             const int64_t tiles = (lower ? tm * (tm + 1) / 2 : tm * tn) - (heads ? 1 : 0);
             const int cus = (want < 256 ? want : 256) & ~7;     // one workgroup per compute unit (gfx950: 256), 8 XCDs
-            // A launch lasts a whole number of ROUNDS of tiles (one 128 x 128 tile per workgroup and round), so a few
-            // more workgroups can save a whole round: 1829 tiles take 9 rounds on 224 units and 8 on 232 (-11 %).  With
-            // knobs().pers_flex_cus > 0 the caller's share may be exceeded by that many units when it removes a round.
-            // Round 5 measured it inside the factorisation and left it OFF: what the update gains the panel chain loses.
-            int cus_max = cus + (knobs().pers_flex_cus & ~7);
-            if (cus_max > 256) cus_max = 256;
-            int64_t rounds = (tiles + cus - 1) / cus;
-            int use = cus;
-            if (rounds >= knobs().pers_flex_min_rounds && (tiles + cus_max - 1) / cus_max < rounds) { rounds = (tiles + cus_max - 1) / cus_max; use = cus_max; }
+            // A launch lasts a whole number of ROUNDS of tiles (one 128 x 128 tile per workgroup and round).  (Taking a few
+            // units beyond the caller's share to save a round: updates 4-8 % shorter, the step 2-3 % longer -- round 5,
+            // profiles/r05_flex_scan.txt, HISTORY.md.)
+            const int64_t rounds = (tiles + cus - 1) / cus;
             int64_t g8 = (tiles + rounds - 1) / rounds;         // every workgroup busy in (nearly) every round ...
             g8 = (g8 + 7) / 8 * 8;                              // ... and the same number of them on every XCD
-            if (g8 > use) g8 = use;
+            if (g8 > cus) g8 = cus;
             const dim3 grid((unsigned)g8);
-            // head tiles straight out at the end of their own pass when the launch is short enough for the panel chain --
-            // which waits for them -- to be the longer path of the panel (knobs().head_direct_max_rounds)
-            const int head_direct = (heads > 0 && rounds <= knobs().head_direct_max_rounds) ? 1 : 0;
 #define CIMRGP_PERS_LAUNCH(LOW_, MULTI_) \
-            hipLaunchKernelGGL((k_gemm_nt_pers<T, LOW_, pers_nkt, MULTI_>), grid, dim3(PERS_THREADS), 0, st, c, ldc, a, lda, b, ldb, (int)tm, (int)tn, (int)tiles, heads, bt.flag, head_direct, nkc)
+            hipLaunchKernelGGL((k_gemm_nt_pers<T, LOW_, pers_nkt, MULTI_>), grid, dim3(PERS_THREADS), 0, st, c, ldc, a, lda, b, ldb, (int)tm, (int)tn, (int)tiles, heads, bt.flag, nkc)
             if (lower) { if (nkc > 1) CIMRGP_PERS_LAUNCH(true, true); else CIMRGP_PERS_LAUNCH(true, false); }
             else       { if (nkc > 1) CIMRGP_PERS_LAUNCH(false, true); else CIMRGP_PERS_LAUNCH(false, false); }
 #undef CIMRGP_PERS_LAUNCH
@@ -775,13 +699,6 @@ int gemm_nt_sub(T* c, int64_t ldc, const T* a, int64_t lda, const T* b, int64_t 
     if (t128 < 768 || thin <= 64) return gemm_launch<T, 2>(c, ldc, a, lda, b, ldb, m, n, k, lower, st, bt);
     return gemm_launch<T, 4>(c, ldc, a, lda, b, ldb, m, n, k, lower, st, bt);
 }
-
-#ifdef PERS_STAMPS
-extern "C" int cimrgp_debug_pers_stamps(long long* out_host)
-{
-    return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_pers_stamp), sizeof(g_pers_stamp)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 template int gemm_nt_sub<double>(double*, int64_t, const double*, int64_t, const double*, int64_t,
                                  int64_t, int64_t, int, bool, hipStream_t, GemmBatch);

@@ -98,7 +98,6 @@ static __device__ __forceinline__ void gemm_tile(unsigned char* smem, T* __restr
     const unsigned a_off = (unsigned)((wr * 16 * W + frow) * LROW + fslot * 8);
     const unsigned b_off = (unsigned)((wc * 16 * W + frow) * LROW + fslot * 8);
 
-    STAMP(16);
     CIMRGP_GLOAD(0);
     // The accumulators start as the C tile and the A fragments are NEGATED, so the MFMA
     // chain itself computes C - A B^T: the 64 C loads per lane are independent and in flight
@@ -132,7 +131,6 @@ static __device__ __forceinline__ void gemm_tile(unsigned char* smem, T* __restr
 #pragma unroll
         for (int ni = 0; ni < W; ++ni) asm volatile("" : "+v"(acc[mi][ni]));
     __syncthreads();
-    STAMP(17);
 
     for (int kt = 0; kt < nkt; ++kt) {
         const bool more = (kt + 1) < nkt;
@@ -162,7 +160,6 @@ static __device__ __forceinline__ void gemm_tile(unsigned char* smem, T* __restr
 #undef CIMRGP_GLOAD
 #undef CIMRGP_SWRITE
 
-    STAMP(18);
     int Mv = M, Nv = N;
     asm volatile("" : "+s"(Mv), "+s"(Nv));      // recompute the store predicates here (not hoisted over the loop)
     // epilogue: store the tile (f64 map: 16 lanes x 8 B = one 128-byte line per row)
@@ -178,7 +175,6 @@ static __device__ __forceinline__ void gemm_tile(unsigned char* smem, T* __restr
             }
         }
     }
-    STAMP(19);
 }
 
 }  // namespace

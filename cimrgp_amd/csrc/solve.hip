@@ -13,9 +13,7 @@ namespace cimrgp {
 
 namespace {
 
-#ifndef CIMRGP_STAMP
 constexpr int SB   = 64;
-#endif
 constexpr int MAXQ = 8;
 
 // (n x q) row-major  <->  (q x n)

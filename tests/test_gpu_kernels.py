@@ -191,7 +191,7 @@ def test_potrf_f32_beside_a_running_update_is_bit_equal_to_the_undisturbed_run(d
     """Round 5: the situation of the round-4 wrong results, run ONCE.  An FP32 factorisation above
     the one-queue limit (four-wave chain kernels beside their own FP32 trailing updates) while ANOTHER stream keeps FP32
     updates of a second matrix running on every compute unit: the factor must equal, bit for bit, the one computed with
-    nothing beside it, and pass the backward-error bar.  The cause was a hand-off through LDS (tools/lab/race_probe.hip:
+    nothing beside it, and pass the backward-error bar.  The cause was a hand-off through LDS (HISTORY.md, round 5:
     the gathering wave's last ds_write instructions were not in the LDS array when the pivot wave read behind the
     barrier); a chain workgroup that shares its compute unit with an update workgroup is what exposed it."""
     n, mu, k = 5632, 6144, 256

@@ -1,10 +1,10 @@
 #!/bin/bash
 # Collect the judged profiles of the N = 8192 bench on the GPU box (run from the repo root):
-#   bash tools/collect_profiles.sh r04 [part ...]     parts: bench stats timelines pmc sweep configs rccl variants config5 chain (default: all but config5)
+#   bash tools/collect_profiles.sh r04 [part ...]     parts: bench stats timelines pmc sweep configs rccl config5 (default: all but config5)
 # -> gpurun_out/r03_*; then locally:  python3 tools/finalize_profiles.py r03   (copies what is kept into profiles/,
 # stamps the commit).  rocprofv3: counters in their own passes with --kernel-trace only; the program itself after `--`.
 tag=${1:-rXX}; shift || true
-parts=${*:-"bench stats timelines pmc sweep configs rccl variants chain"}
+parts=${*:-"bench stats timelines pmc sweep configs rccl"}
 out=gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 want() { case " $parts " in *" $1 "*) return 0;; esac; return 1; }
@@ -67,13 +67,5 @@ if want config5; then
         python3 tools/pmc_summary.py $out/${tag}_c5pmc_$dt/ > $out/${tag}_config5_mfma_counters_$dt.json
         rm -rf $out/${tag}_c5pmc_$dt
     done
-fi
-if want chain && [ -x tools/diag_probe_e0 ]; then
-    # the chain kernels stand-alone: both forms agree bit for bit, are repeatable (also beside a running FP32 update), launch rates
-    timeout -k 10 600 tools/diag_probe_e0 | grep -v "^raw\|nine waves):\|^row\|kprev 192" > $out/${tag}_chain_kernels.txt
-fi
-if want variants && [ -f cimrgp_amd/libcimrgp_tuning_e1.so ]; then
-    # timing-only builds of the persistent kernel (built beforehand: bash tools/lab/exp_variants.sh build)
-    bash tools/lab/exp_variants.sh > $out/${tag}_pers_variants.txt 2>&1
 fi
 echo collected
