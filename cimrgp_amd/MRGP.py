@@ -440,6 +440,49 @@ class MultiResolutionGaussianProcess(object):
             self._check_index_set(index_set_obj, number_of_regions)
         return self._predict(test_x, index_set_obj, want_var=True, include_noise=include_noise)
 
+    # ------------------------------------------------------ predictive gradients
+    def predictive_gradients(self, test_x, index_set_obj=None, number_of_regions=None):
+        """Derivatives of the prediction with respect to the test inputs (GPy's ``GP.predictive_gradients``):
+        ``(dmu_dx, dvar_dx)``, NumPy arrays of shape (N*, d, dy) and (N*, d), in the caller's original input units (the
+        chain rule through ``standard_normalized_inputs``) and the output units of :meth:`get_predicted_mean_and_var`.
+        Test point i is served by the blocks :meth:`_predict` gives it, so its gradient is the sum of theirs; biases and
+        the finest layer's noise are constant.  The index-set rules and errors are those of :meth:`_predict`.  With
+        several ranks every rank adds its blocks into one zero-initialised buffer, summed by ONE collective.  Not for
+        ``adaptive_inputs`` (the warp's Jacobian is not built)."""
+        if self.adaptive_inputs is True:
+            raise TypeError('not yet supported')
+        if index_set_obj is not None:
+            self._check_index_set(index_set_obj, number_of_regions)
+        if not self._fitted:
+            raise RuntimeError('call fit() before predicting')
+        xs = self._prepare_test(test_x)
+        ns, d = int(xs.shape[0]), int(xs.shape[1])
+        q = self.dy
+        fused = torch.zeros(ns * d * (q + 1), dtype=self.dtype, device=self.device)
+        mean_grad = fused[:ns * d * q].view(ns, d, q)
+        var_grad = fused[ns * d * q:].view(ns, d)
+        if index_set_obj is None:
+            if self.n_regions[0] != 1:
+                raise ValueError('index_set_obj is required when the first layer has more than one region')
+            if self.owner[0][0] == self.rank:
+                self.posterior_obj[0].blocks[0].predict_grad(xs, mean_grad, var_grad)
+        else:
+            for j in range(index_set_obj.get_n_resolutions() + 1):
+                owned = self._owned(j)
+                if not owned:
+                    continue
+                self.posterior_obj[j].predict_grad_layer(self._x_dev, xs, index_set_obj.bounds[j], set(owned), mean_grad,
+                                                         var_grad, lambda cnt, nmax: _Fanout(self.device, cnt, nmax))
+        if self.world_size > 1:
+            dist.allreduce_sum_(fused, self.group)
+        dmu = mean_grad.double().cpu().numpy()
+        dvar = var_grad.double().cpu().numpy()
+        if self.standard_normalized_inputs is True:
+            inv_std = 1.0 / np.asarray(self.std_x_train, dtype=np.float64)
+            dmu = dmu * inv_std[None, :, None]
+            dvar = dvar * inv_std[None, :]
+        return dmu, dvar
+
     # ------------------------------------------------------- joint distribution
     def _joint_layers(self, index_set, ns, include_noise):
         """(layer, test bounds, add noise) of every layer that contributes, by the rule of :meth:`_predict`: without an

@@ -156,6 +156,27 @@ class DenseBlock(object):
                                mean_out[s0:s1], var_out[s0:s1], accumulate=True,
                                extra_var_dev=self.noise if add_noise else None)
 
+    def predict_grad(self, xs, mean_grad_out, var_grad_out=None, chunk=16384):
+        """Accumulate this block's predictive gradients at ``xs`` ("Predictive gradients"):
+        ``mean_grad_out`` (ns, d, q) += d mean / d xs from alpha, ``var_grad_out`` (ns, d) += d var / d xs from the rows
+        beta = K(xs, x) K^-1 (a forward and a backward row solve per chunk of test points).  Either may be None."""
+        k = self.kernel
+        if var_grad_out is None:
+            if mean_grad_out is not None:
+                dev.cov_predict_grad(self.x, self.alpha, xs, k.l, k.sf, mean_grad=mean_grad_out, accumulate=True, cov=k.cov)
+            return
+        if self.lbuf is None:
+            raise RuntimeError('the gradient of the predictive variance needs the Cholesky factor: fit with keep_factors=True')
+        ns = xs.shape[0]
+        for s0 in range(0, ns, chunk):
+            s1 = min(ns, s0 + chunk)
+            w = dev.rbf_cross(xs[s0:s1], self.x, k.l, k.sf, cov=k.cov)
+            dev.trsm_rows(self.lbuf, self.n, self.ws, w, s1 - s0)
+            dev.trsm_rows_lt(self.lbuf, self.n, self.ws, w, s1 - s0)
+            dev.cov_predict_grad(self.x, self.alpha, xs[s0:s1], k.l, k.sf, beta=w,
+                                 mean_grad=None if mean_grad_out is None else mean_grad_out[s0:s1],
+                                 var_grad=var_grad_out[s0:s1], accumulate=True, cov=k.cov)
+
     def log_marginal_likelihood(self, r_dot_alpha):
         """-1/2 r^T alpha - sum log L_ii - n/2 log 2pi, per output column summed."""
         half_logdet = float(dev.logdet_half(self.lbuf, self.n).item())
@@ -520,6 +541,51 @@ class DensePosterior(object):
             a, b = (int(v) for v in test_bounds[l])
             with torch.cuda.stream(fan.stream()):
                 self.blocks[l].predict(xs[a:b], mean[a:b], var[a:b], add_noise=add_noise)
+        fan.join()
+
+    def predict_grad_layer(self, x_all, xs, test_bounds, owned, mean_grad, var_grad, fan_factory):
+        """Accumulate the layer's predictive gradients at the test points (test block l = rows test_bounds[l] of ``xs``,
+        served by training block l), grouped as :meth:`predict_layer` groups the blocks: ONE
+        cimrgp_layer_predict_grad_cov call per memory-bounded sub-batch of blocks fitted together with equally many test
+        points (their alpha is recomputed from a copy of z: a batch keeps z, not alpha), the others one by one on the
+        stream pool."""
+        done = set()
+        for bt in self.batches:
+            by_ns = {}
+            for i, l in enumerate(bt.regions):
+                if l in owned:
+                    a, b = (int(v) for v in test_bounds[l])
+                    by_ns.setdefault(b - a, []).append((i, a))
+            for ns, items in by_ns.items():
+                idx = [i for i, _ in items]
+                contiguous = idx == list(range(idx[0], idx[0] + len(idx)))
+                if ns <= 0 or len(items) < 2 or not contiguous:
+                    continue
+                ldw = dev.padded_ld(bt.n)
+                esz = xs.element_size()
+                free_bytes = torch.cuda.mem_get_info(xs.device)[0] + torch.cuda.memory_reserved(xs.device) \
+                    - torch.cuda.memory_allocated(xs.device)
+                per_block = (ns * ldw + 2 * bt.n * self.dy) * esz
+                per_call = int(max(1, min(len(items), (0.5 * free_bytes) // max(1, per_block))))
+                for c0 in range(0, len(items), per_call):
+                    part = items[c0:c0 + per_call]
+                    i0, nb = part[0][0], len(part)
+                    t_starts = torch.tensor([a for _, a in part], dtype=torch.int64).to(xs.device, non_blocking=True)
+                    karena, ws_arena = bt.karena[i0:i0 + nb], bt.ws_arena[i0:i0 + nb]
+                    alpha = dev.solve_lt_batched(karena, bt.n, karena.stride(1), ws_arena, bt.z[i0:i0 + nb].clone())
+                    dev.layer_predict_grad(x_all, bt.starts[i0:i0 + nb], bt.n, xs, t_starts, ns, self.kernel.l, self.kernel.sf,
+                                           karena, ws_arena, alpha, mean_grad, var_grad, cov=self.kernel.cov)
+                done.update(bt.regions[i] for i, _ in items)
+        rest = [l for l in owned if l not in done]
+        if not rest:
+            return
+        fan = fan_factory(len(rest), max(self.blocks[l].n for l in rest))
+        for l in rest:
+            a, b = (int(v) for v in test_bounds[l])
+            if b <= a:
+                continue
+            with torch.cuda.stream(fan.stream()):
+                self.blocks[l].predict_grad(xs[a:b], mean_grad[a:b], None if var_grad is None else var_grad[a:b])
         fan.join()
 
     def joint_layer(self, layer, x_all, xs, test_bounds, owned, add_noise, cov_out=None, samples=None, seed=0, jitter=1e-6):

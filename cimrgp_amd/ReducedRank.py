@@ -1030,6 +1030,11 @@ class ReducedRankMRGP(MultiResolutionGaussianProcess):
                 dist.allreduce_sum_(total, self.group)
         return mean.double().cpu().numpy(), (total.double().cpu().numpy() if want_var else None)
 
+    def predictive_gradients(self, test_x, index_set_obj=None, number_of_regions=None):
+        """Gradients of the reduced-rank prediction with respect to the test inputs are not built (only the dense
+        blocks have them: MultiResolutionGaussianProcess.predictive_gradients)."""
+        raise TypeError('not yet supported')
+
     def get_basis_contributions(self):
         """MRGP.py:973-982."""
         return [[self.stats_obj[j].scale_moment2[l] / np.sum(self.stats_obj[j].scale_moment2[l])

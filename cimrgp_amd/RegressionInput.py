@@ -250,6 +250,34 @@ class GP_RBF(RegressionMethod):
         return mean, var
 
 
+    def predictive_gradients(self, test_data):
+        """GPy's ``predictive_gradients``: ``(dmu_dX (N*, d, q), dvar_dX (N*, d))`` with respect to the original test
+        inputs (the chain rule through the input z-scoring and, with ARD, the per-dimension 1 / lengthscale scaling).  The
+        mean gradient is in the original label units, per output; the variance gradient is left in z-scored label units,
+        as ``predict_with_variance`` leaves the variance."""
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        blk = self.block
+        xs = dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, blk.x.device)
+        if self.ARD:
+            xs = (xs * self._scale).contiguous()
+        ns, d = int(xs.shape[0]), int(xs.shape[1])
+        q = blk.alpha.shape[1]
+        mean_grad = torch.zeros((ns, d, q), dtype=self.dtype, device=xs.device)
+        var_grad = torch.zeros((ns, d), dtype=self.dtype, device=xs.device)
+        blk.predict_grad(xs, mean_grad, var_grad)
+        dmu = mean_grad.double().cpu().numpy()
+        dvar = var_grad.double().cpu().numpy()
+        if self.ARD:
+            s = 1.0 / np.asarray(self.lengthscales, dtype=np.float64)
+            dmu = dmu * s[None, :, None]
+            dvar = dvar * s[None, :]
+        if self.preprocess:
+            inv_std = 1.0 / np.asarray(self.data_std, dtype=np.float64)
+            dmu = dmu * inv_std[None, :, None] * np.asarray(self.labels_std, dtype=np.float64)[None, None, :]
+            dvar = dvar * inv_std[None, :]
+        return dmu, dvar
+
     def _joint(self, test_data, cov_out=None, samples=None, seed=0):
         blk = self.block
         xs = dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, blk.x.device)

@@ -96,6 +96,16 @@ JOINT_SIGNATURES = {
     "cimrgp_layer_sample": (_i32, [_i32, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/cimrgp_grad.h (predictive gradients)
+GRAD_SIGNATURES = {
+    "cimrgp_trsm_rows_lt": (_i32, [_i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp]),
+    "cimrgp_trsm_rows_lt_batched": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _sz, _vp, _i64, _i64, _i64, _i32, _vp]),
+    "cimrgp_cov_predict_grad": (_i32, [_i32, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _dbl, _dbl, _vp, _i64, _vp, _vp, _i32,
+                                       _vp]),
+    "cimrgp_layer_predict_grad_cov": (_i32, [_i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _dbl, _dbl, _vp, _i64, _i64,
+                                             _vp, _sz, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _i32, _vp]),
+}
+
 _lib = None
 
 
@@ -116,7 +126,7 @@ def load():
             "There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + \
-            list(JOINT_SIGNATURES.items()):
+            list(JOINT_SIGNATURES.items()) + list(GRAD_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if a symbol is missing
         fn.restype = res
         fn.argtypes = args

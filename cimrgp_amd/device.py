@@ -340,6 +340,58 @@ def layer_sample(larena, ns, z, cols, t_starts, out):
     return out
 
 
+def trsm_rows_lt(lbuf, n, ws, bbuf, m):
+    """B <- B L^-1 on bbuf[:m, :n] (cimrgp_trsm_rows_lt, include/cimrgp_grad.h): after :func:`trsm_rows` the rows of
+    K(X*, X) K^-1."""
+    lib = _lib.load()
+    _lib.check(lib.cimrgp_trsm_rows_lt(_DT[lbuf.dtype], _p(lbuf), int(n), lbuf.stride(0), _p(ws), _p(bbuf), int(m),
+                                       bbuf.stride(0), _stream()), "cimrgp_trsm_rows_lt")
+    return bbuf
+
+
+def trsm_rows_lt_batched(larena, n, ws_arena, barena, m):
+    """B_b <- B_b L_b^-1 for every block b of larena (batch, >= n, ldl), ws_arena (batch, ws_bytes) uint8 and barena
+    (batch, >= m, ldb) (cimrgp_trsm_rows_lt_batched)."""
+    lib = _lib.load()
+    batch = int(larena.shape[0])
+    _lib.check(lib.cimrgp_trsm_rows_lt_batched(_DT[larena.dtype], _p(larena), int(n), larena.stride(1), larena.stride(0),
+                                               _p(ws_arena), ws_arena.stride(0), _p(barena), int(m), barena.stride(1),
+                                               barena.stride(0), batch, _stream()), "cimrgp_trsm_rows_lt_batched")
+    return barena
+
+
+def cov_predict_grad(x, alpha, xs, ell, sf2, beta=None, mean_grad=None, var_grad=None, accumulate=False, cov=_lib.COV_RBF):
+    """The fused derivative contraction of one block (cimrgp_cov_predict_grad): mean_grad (ns, d, q) (+)= d mean / d xs
+    from alpha (n x q); var_grad (ns, d) (+)= d var / d xs from beta (ns rows of K(xs, x) K^-1).  Either output may be
+    None."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
+    lib = _lib.load()
+    n, d = x.shape
+    q = int(alpha.shape[1]) if alpha is not None else int(mean_grad.shape[2]) if mean_grad is not None else 1
+    ldb = beta.stride(0) if beta is not None else 0
+    _lib.check(lib.cimrgp_cov_predict_grad(_DT[x.dtype], cov, _p(x), int(n), int(d), _p(alpha), q, _p(xs), int(xs.shape[0]),
+                                           float(ell), float(sf2), _p(beta), ldb, _p(mean_grad), _p(var_grad),
+                                           1 if accumulate else 0, _stream()), "cimrgp_cov_predict_grad")
+
+
+def layer_predict_grad(x, starts, n, xs, t_starts, ns, ell, sf2, larena, ws_arena, alpha, mean_grad, var_grad,
+                       cov=_lib.COV_RBF):
+    """Predictive gradients of ``batch`` equal-sized blocks at ``ns`` test points each in ONE call
+    (cimrgp_layer_predict_grad_cov): accumulates into mean_grad (N*, d, q) / var_grad (N*, d) at rows t_starts[b] ...;
+    alpha (batch, n, q) contiguous.  The W work area is allocated for this call only (not without var_grad)."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
+    lib = _lib.load()
+    batch = int(larena.shape[0])
+    ldw = padded_ld(n)
+    w = torch.empty((batch, max(int(ns), 1), ldw), dtype=x.dtype, device=x.device) if var_grad is not None else None
+    _lib.check(lib.cimrgp_layer_predict_grad_cov(_DT[x.dtype], cov, _p(x), _p(starts), int(n), int(x.shape[1]), _p(xs),
+                                                 _p(t_starts), int(ns), batch, float(ell), float(sf2), _p(larena),
+                                                 larena.stride(1), larena.stride(0), _p(ws_arena), ws_arena.stride(0),
+                                                 _p(alpha), int(alpha.shape[2]), _p(w), ldw, 0 if w is None else w.stride(0),
+                                                 _p(mean_grad), _p(var_grad), 1, _stream()),
+               "cimrgp_layer_predict_grad_cov")
+
+
 def layer_lml_scratch_bytes(n, q, batch, dtype):
     return int(_lib.load().cimrgp_layer_lml_grad_scratch_bytes(_DT[dtype], int(n), int(q), int(batch)))
 

@@ -467,4 +467,7 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
 /* The joint predictive covariance of a layer's blocks and posterior samples: include/cimrgp_joint.h. */
 #include "cimrgp_joint.h"
 
+/* Derivatives of the predictive mean and variance with respect to the test inputs: include/cimrgp_grad.h. */
+#include "cimrgp_grad.h"
+
 #endif /* CIMRGP_H */
