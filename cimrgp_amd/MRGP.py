@@ -571,6 +571,58 @@ class MultiResolutionGaussianProcess(object):
         dev_part = out.double().cpu().numpy().reshape(size, self.dy, ns).transpose(0, 2, 1)
         return mean[None, :, :] + dev_part
 
+    # ------------------------------------------------- leave-one-out cross-validation
+    def leave_one_out(self, layer=None):
+        """Leave-one-out prediction of every training target: ``(loo_mean (N, dy), loo_var (N,))``, NumPy arrays in the
+        output units of :meth:`get_predicted_mean_and_var` ("Leave-one-out cross-validation").  For the block
+        (``layer`` j, region l) that holds point i, with K = K_j(X, X) + noise I, alpha = K^-1 (y - f_bar_j - bias) and
+        d = diag(K^-1):  loo_mean[i] = y[i] - alpha[i] / d_i,  loo_var[i] = 1 / d_i (noise included, shared by the
+        outputs).  This is the BLOCKWISE leave-one-out of layer j conditional on the coarser layers: point i is withheld
+        from its layer-j block only; the prediction f_bar_j of layers 0 .. j - 1, the block's bias and its noise are those
+        of the fit and keep their dependence on y[i].  That is how the model is fitted and how its hyper-parameters are
+        learned (layer by layer); it is not a refit of the whole chain.  ``layer=None``: the finest layer.  Closed form
+        (Rasmussen & Williams 5.4.2): nothing is refitted, sampled or jittered.  Needs ``keep_factors=True``.  With
+        several ranks every rank adds its blocks into one zero buffer, summed by ONE collective of [mean | var | failure
+        flags]."""
+        if not self._fitted:
+            raise RuntimeError('call fit() before leave_one_out()')
+        if not self.keep_factors:
+            raise RuntimeError('leave-one-out needs the Cholesky factors: construct the model with keep_factors=True')
+        j = self.n_layers - 1 if layer is None else int(layer)
+        if not 0 <= j < self.n_layers:
+            raise ValueError('layer must be in [0, %d), got %r' % (self.n_layers, layer))
+        n, q = self._y.shape
+        fused = torch.zeros(n * q + n + 2, dtype=self.dtype, device=self.device)
+        mean, var, flag = fused[:n * q].view(n, q), fused[n * q:n * q + n], fused[n * q + n:]
+        owned = self._owned(j)
+        failure = None
+        if owned:
+            try:
+                self.posterior_obj[j].loo_layer(self._y, self._slices(self._y, j), set(owned), mean, var,
+                                                lambda cnt, nmax: _Fanout(self.device, cnt, nmax))
+            except Exception as e:
+                # the other ranks wait in the collective: join it with the flag set, then raise (as _joint does)
+                if self.world_size == 1:
+                    raise
+                failure = e
+                flag[0 if isinstance(e, np.linalg.LinAlgError) else 1] = 1.0
+        if self.world_size > 1:
+            dist.allreduce_sum_(fused, self.group)
+            if failure is not None:
+                raise failure
+        res = fused.double().cpu().numpy()
+        if res[-1] != 0.0 or res[-2] != 0.0:
+            raise RuntimeError('leave-one-out failed on another rank (see its exception)')
+        return res[:n * q].reshape(n, q).copy(), res[n * q:n * q + n].copy()
+
+    def get_loo_likelihood(self, layer=None):
+        """:meth:`get_test_likelihood`'s formula (kept as it is, so that the two numbers are comparable) applied to the
+        training targets and their leave-one-out predictions of ``layer`` (:meth:`leave_one_out`): a score that needs no
+        held-out set."""
+        mf, vf = self.leave_one_out(layer)
+        ll = -0.5 * np.log(2 * np.pi * vf) - 0.5 * (np.linalg.norm((self.observations - mf), axis=1) ** 2) / vf
+        return np.mean(ll)
+
     def get_test_likelihood(self, test, index_set_obj=None, number_of_regions=None):
         test_x, test_y = test[0], test[1]
         mf, vf = self.get_predicted_mean_and_var(test_x, index_set_obj, number_of_regions)

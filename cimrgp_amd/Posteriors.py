@@ -177,6 +177,17 @@ class DenseBlock(object):
                                  mean_grad=None if mean_grad_out is None else mean_grad_out[s0:s1],
                                  var_grad=var_grad_out[s0:s1], accumulate=True, cov=k.cov)
 
+    def loo(self, y, mean_out, var_out=None):
+        """Leave-one-out prediction of this block's own targets ("Leave-one-out cross-validation"):
+        ``mean_out`` (n x q) = y - alpha / d, ``var_out`` (n,) = 1 / d with d = diag(K^-1) from row strips of L^-T
+        (cimrgp_kinv_diag; at most LOO_SCRATCH_BYTES of scratch, which the result does not depend on).  ``y`` (n x q):
+        the block's rows of the observations.  Point i is withheld from THIS block only: the coarser layers' prediction,
+        the block's bias and its noise are those of the fit.  Either output may be None."""
+        if self.lbuf is None:
+            raise RuntimeError('leave-one-out needs the Cholesky factor: fit with keep_factors=True')
+        d = dev.kinv_diag(self.lbuf, self.n, self.ws, LOO_SCRATCH_BYTES)
+        dev.loo(y, self.alpha, d, mean_out, var_out)
+
     def log_marginal_likelihood(self, r_dot_alpha):
         """-1/2 r^T alpha - sum log L_ii - n/2 log 2pi, per output column summed."""
         half_logdet = float(dev.logdet_half(self.lbuf, self.n).item())
@@ -222,6 +233,10 @@ JOINT_RETRIES = 4
 JOINT_JITTER_FLOOR = 1e-7
 #: bytes of standard normals one joint sampling call may hold
 JOINT_Z_BYTES = 256 << 20
+
+
+#: bytes of L^-T row strips one leave-one-out call may hold (the strip height follows from it; the result does not)
+LOO_SCRATCH_BYTES = 512 << 20
 
 
 class _JointCall(object):
@@ -586,6 +601,38 @@ class DensePosterior(object):
                 continue
             with torch.cuda.stream(fan.stream()):
                 self.blocks[l].predict_grad(xs[a:b], mean_grad[a:b], None if var_grad is None else var_grad[a:b])
+        fan.join()
+
+    def loo_layer(self, y_all, y, owned, mean, var, fan_factory):
+        """Leave-one-out prediction of the layer's own targets by its ``owned`` blocks (:meth:`DenseBlock.loo`), written
+        into the rows of ``mean`` (N x q) and ``var`` (N,) that each block's region covers.  ``y_all``: the (N x q)
+        observations, ``y``: its region views (lists indexed by region, as for :meth:`update_scale_given_axis`).  Grouped
+        as :meth:`predict_grad_layer` groups the blocks: the owned blocks of a batch fitted together go through ONE
+        cimrgp_kinv_diag_batched call per sub-batch (scratch bounded by LOO_SCRATCH_BYTES; their alpha is recomputed from
+        a copy of z: a batch keeps z, not alpha), the others one by one on the stream pool."""
+        done = set()
+        for bt in self.batches:
+            idx = [i for i, l in enumerate(bt.regions) if l in owned]
+            if len(idx) < 2 or idx != list(range(idx[0], idx[0] + len(idx))):
+                continue
+            strip = dev.kinv_diag_scratch_bytes(bt.n, 256, y_all.dtype)
+            per_call = int(max(1, min(len(idx), LOO_SCRATCH_BYTES // strip)))
+            for c0 in range(0, len(idx), per_call):
+                i0, nb = idx[c0], len(idx[c0:c0 + per_call])
+                karena, ws_arena = bt.karena[i0:i0 + nb], bt.ws_arena[i0:i0 + nb]
+                alpha = dev.solve_lt_batched(karena, bt.n, karena.stride(1), ws_arena, bt.z[i0:i0 + nb].clone())
+                d = dev.kinv_diag_batched(karena, bt.n, ws_arena, LOO_SCRATCH_BYTES)
+                dev.loo(y_all, alpha, d, mean, var, starts=bt.starts[i0:i0 + nb])
+            done.update(bt.regions[i] for i in idx)
+        rest = [l for l in owned if l not in done]
+        if not rest:
+            return
+        fan = fan_factory(len(rest), max(self.blocks[l].n for l in rest))
+        for l in rest:
+            a = y[l].storage_offset() // y[l].stride(0)
+            b = a + int(y[l].shape[0])
+            with torch.cuda.stream(fan.stream()):
+                self.blocks[l].loo(y[l], mean[a:b], None if var is None else var[a:b])
         fan.join()
 
     def joint_layer(self, layer, x_all, xs, test_bounds, owned, add_noise, cov_out=None, samples=None, seed=0, jitter=1e-6):

@@ -1035,6 +1035,14 @@ class ReducedRankMRGP(MultiResolutionGaussianProcess):
         blocks have them: MultiResolutionGaussianProcess.predictive_gradients)."""
         raise TypeError('not yet supported')
 
+    def leave_one_out(self, layer=None):
+        """Leave-one-out cross-validation is built for the dense blocks only
+        (MultiResolutionGaussianProcess.leave_one_out)."""
+        raise TypeError('not yet supported')
+
+    def get_loo_likelihood(self, layer=None):
+        raise TypeError('not yet supported')
+
     def get_basis_contributions(self):
         """MRGP.py:973-982."""
         return [[self.stats_obj[j].scale_moment2[l] / np.sum(self.stats_obj[j].scale_moment2[l])

@@ -223,6 +223,7 @@ class GP_RBF(RegressionMethod):
         sink = torch.zeros_like(y)
         self.block.fit(y, None, sink, shared_bias=zero_bias)
         dev.raise_if_not_pd(self.block.info)
+        self._y_dev = y                                  # the (z-scored) labels: leave_one_out reads them
         return True
 
     def _predict(self, test_data):
@@ -277,6 +278,34 @@ class GP_RBF(RegressionMethod):
             dmu = dmu * inv_std[None, :, None] * np.asarray(self.labels_std, dtype=np.float64)[None, None, :]
             dvar = dvar * inv_std[None, :]
         return dmu, dvar
+
+    def _loo_z(self):
+        """(labels, LOO mean, LOO variance) in the (z-scored) units of the fit, NumPy."""
+        blk = self.block
+        if blk is None:
+            raise RuntimeError('call fit() before leave_one_out()')
+        y = self._y_dev
+        mean = torch.empty_like(y)
+        var = torch.empty(y.shape[0], dtype=self.dtype, device=y.device)
+        blk.loo(y, mean, var)
+        return y.double().cpu().numpy(), mean.double().cpu().numpy(), var.double().cpu().numpy()
+
+    def leave_one_out(self):
+        """Closed-form leave-one-out prediction of every training label from the other n - 1 (Rasmussen & Williams
+        5.4.2; hyper-parameters and noise as fitted): ``(mean (n, q), var (n,))``.  The mean is in the original label
+        units; the variance is left in z-scored label units, as ``predict_with_variance`` leaves it, but includes the
+        noise: it is the variance of an observation."""
+        _, mean, var = self._loo_z()
+        if self.preprocess:
+            mean = self._reverse_trans_labels(mean)
+        return mean, var
+
+    def loo_log_predictive_density(self):
+        """(n,) log densities of each training label under its leave-one-out predictive Gaussian, in z-scored label
+        units, summed over the outputs; their sum is the LOO-CV score (R&W eq. 5.11)."""
+        y, mean, var = self._loo_z()
+        q = y.shape[1]
+        return -0.5 * q * np.log(2 * np.pi * var) - 0.5 * ((y - mean) ** 2).sum(axis=1) / var
 
     def _joint(self, test_data, cov_out=None, samples=None, seed=0):
         blk = self.block

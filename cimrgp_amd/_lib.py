@@ -106,6 +106,16 @@ GRAD_SIGNATURES = {
                                              _vp, _sz, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _i32, _vp]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/cimrgp_loo.h (leave-one-out cross-validation)
+LOO_SIGNATURES = {
+    "cimrgp_trtri_rows": (_i32, [_i32, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "cimrgp_kinv_diag_scratch_bytes": (_sz, [_i32, _i64, _i64]),
+    "cimrgp_kinv_diag": (_i32, [_i32, _vp, _i64, _i64, _vp, _vp, _sz, _vp, _vp]),
+    "cimrgp_kinv_diag_batched": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _sz, _vp, _sz, _vp, _i32, _vp]),
+    "cimrgp_loo": (_i32, [_i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "cimrgp_loo_batched": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -126,7 +136,7 @@ def load():
             "There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + \
-            list(JOINT_SIGNATURES.items()) + list(GRAD_SIGNATURES.items()):
+            list(JOINT_SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(LOO_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if a symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -392,6 +392,66 @@ def layer_predict_grad(x, starts, n, xs, t_starts, ns, ell, sf2, larena, ws_aren
                "cimrgp_layer_predict_grad_cov")
 
 
+def trtri_rows(lbuf, n, ws, r0, m, out=None):
+    """Rows [r0, r0 + m) of L^-T (cimrgp_trtri_rows, include/cimrgp_loo.h) into ``out`` (>= m rows of >= n columns, columns
+    indexed as in L^-T; allocated with a padded pitch if None).  Columns left of r0 are neither read nor written."""
+    lib = _lib.load()
+    if out is None:
+        out = alloc_matrix(m, n, lbuf.dtype, lbuf.device)
+    _lib.check(lib.cimrgp_trtri_rows(_DT[lbuf.dtype], _p(lbuf), int(n), lbuf.stride(0), _p(ws), int(r0), int(m), _p(out),
+                                     out.stride(0), _stream()), "cimrgp_trtri_rows")
+    return out
+
+
+def kinv_diag_scratch_bytes(n, strip_rows, dtype):
+    return int(_lib.load().cimrgp_kinv_diag_scratch_bytes(_DT[dtype], int(n), int(strip_rows)))
+
+
+def kinv_diag(lbuf, n, ws, scratch_bytes, out=None):
+    """diag(K^-1) of one factored block (cimrgp_kinv_diag), through a scratch of at most ``scratch_bytes`` bytes (at least
+    one strip of 256 rows); the result does not depend on the scratch size."""
+    lib = _lib.load()
+    dtype = lbuf.dtype
+    nbytes = min(max(int(scratch_bytes), kinv_diag_scratch_bytes(n, 256, dtype)), kinv_diag_scratch_bytes(n, n, dtype))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=lbuf.device)
+    if out is None:
+        out = torch.empty(int(n), dtype=dtype, device=lbuf.device)
+    _lib.check(lib.cimrgp_kinv_diag(_DT[dtype], _p(lbuf), int(n), lbuf.stride(0), _p(ws), _p(scratch), nbytes, _p(out), _stream()),
+               "cimrgp_kinv_diag")
+    return out
+
+
+def kinv_diag_batched(larena, n, ws_arena, scratch_bytes, out=None):
+    """diag(K_b^-1) for every block b of larena (batch, >= n, ldl) and ws_arena (batch, ws_bytes) uint8
+    (cimrgp_kinv_diag_batched): (batch, n).  The scratch (at most ``scratch_bytes``, at least one strip of 256 rows per
+    block) is shared evenly by the blocks."""
+    lib = _lib.load()
+    dtype = larena.dtype
+    batch = int(larena.shape[0])
+    nbytes = min(max(int(scratch_bytes), batch * kinv_diag_scratch_bytes(n, 256, dtype)), batch * kinv_diag_scratch_bytes(n, n, dtype))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=larena.device)
+    if out is None:
+        out = torch.empty((batch, int(n)), dtype=dtype, device=larena.device)
+    _lib.check(lib.cimrgp_kinv_diag_batched(_DT[dtype], _p(larena), int(n), larena.stride(1), larena.stride(0), _p(ws_arena),
+                                            ws_arena.stride(0), _p(scratch), nbytes, _p(out), batch, _stream()),
+               "cimrgp_kinv_diag_batched")
+    return out
+
+
+def loo(y, alpha, diag, mean_out=None, var_out=None, starts=None):
+    """The leave-one-out tail (cimrgp_loo): mean_out = y - alpha / diag[:, None], var_out = 1 / diag; either may be None.
+    With ``starts`` (batch,) int64 the batched form (cimrgp_loo_batched): alpha (batch, n, q), diag (batch, n), block b's
+    rows of y, mean_out and var_out start at row starts[b]."""
+    lib = _lib.load()
+    q = int(alpha.shape[-1])
+    if starts is None:
+        _lib.check(lib.cimrgp_loo(_DT[diag.dtype], _p(y), _p(alpha), _p(diag), int(diag.shape[0]), q, _p(mean_out), _p(var_out),
+                                  _stream()), "cimrgp_loo")
+    else:
+        _lib.check(lib.cimrgp_loo_batched(_DT[diag.dtype], _p(y), _p(starts), _p(alpha), _p(diag), int(diag.shape[1]), q,
+                                          int(diag.shape[0]), _p(mean_out), _p(var_out), _stream()), "cimrgp_loo_batched")
+
+
 def layer_lml_scratch_bytes(n, q, batch, dtype):
     return int(_lib.load().cimrgp_layer_lml_grad_scratch_bytes(_DT[dtype], int(n), int(q), int(batch)))
 

@@ -470,4 +470,7 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
 /* Derivatives of the predictive mean and variance with respect to the test inputs: include/cimrgp_grad.h. */
 #include "cimrgp_grad.h"
 
+/* Leave-one-out cross-validation of a fitted block and the triangular inverse behind it: include/cimrgp_loo.h. */
+#include "cimrgp_loo.h"
+
 #endif /* CIMRGP_H */
