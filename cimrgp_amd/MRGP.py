@@ -29,7 +29,7 @@ from . import device as dev
 from . import dist
 from .Inputs import Inputs
 from .KernelClass import RBFKernel, DenseMaternKernel
-from .Posteriors import DensePosterior, _Fanout
+from .Posteriors import DensePosterior
 
 
 class DenseStats(object):
@@ -378,44 +378,67 @@ class MultiResolutionGaussianProcess(object):
             if len(index_set.bounds[j]) != self.n_regions[j]:
                 raise ValueError('number of regions in the training must be the same as test.')
 
-    def _predict(self, test_x, index_set, want_var, include_noise=True):
+    def _test_points(self, test_x, index_set=None, number_of_regions=None):
+        """What a prediction starts with: the test index set (if given) is checked against the training one, the model
+        must be fitted, and the test inputs go through the training inputs' transformations onto the device."""
+        if index_set is not None:
+            self._check_index_set(index_set, number_of_regions)
         if not self._fitted:
             raise RuntimeError('call fit() before predicting')
-        xs = self._prepare_test(test_x)
+        return self._prepare_test(test_x)
+
+    def _test_layers(self, index_set, ns, include_noise=True):
+        """[(layer, test bounds, add noise, owned regions)] of the layers that serve ``ns`` test points and have blocks
+        of this rank: every layer of ``index_set``, the finest adding its blocks' noise.  Without an index set every
+        prediction is taken from resolution 0 (MRGP.py:726-755), which presumes ONE root region -- it serves all the test
+        points and no noise is added; with a multi-region first layer the test points need an index set."""
+        if index_set is None:
+            if self.n_regions[0] != 1:
+                raise ValueError('index_set_obj is required when the first layer has more than one region')
+            layers = [(0, [(0, ns)], False)]
+        else:
+            n_layers = index_set.get_n_resolutions() + 1
+            layers = [(j, index_set.bounds[j], include_noise and j == n_layers - 1) for j in range(n_layers)]
+        return [(j, bounds, add_noise, self._owned(j)) for j, bounds, add_noise in layers if self._owned(j)]
+
+    def _sum_shares(self, fused, share):
+        """Run ``share()``, which adds this rank's blocks into the zero-initialised ``fused`` = [payload | not positive
+        definite | any other failure], then sum ``fused`` over the ranks in ONE collective.  An exception of ``share``
+        (LinAlgError, the factorisation's schedule watchdog, a failed C call ...) must not leave the other ranks waiting:
+        with several ranks its flag is set, the collective is joined, and then it is raised.  The caller reads the summed
+        flags with whatever else it reads back (:meth:`_failed_elsewhere`)."""
+        if self.world_size == 1:
+            return share()
+        failure = None
+        try:
+            share()
+        except Exception as e:
+            failure = e
+            fused[-2 if isinstance(e, np.linalg.LinAlgError) else -1] = 1.0
+        dist.allreduce_sum_(fused, self.group)
+        if failure is not None:
+            raise failure
+
+    @staticmethod
+    def _failed_elsewhere(flags, failed, not_pd=None):
+        """Raise for the summed failure flags of :meth:`_sum_shares` (host values) set by another rank: RuntimeError
+        ``failed``, or LinAlgError ``not_pd`` (if given) when only the not-positive-definite flag is set."""
+        if flags[1] != 0.0 or (flags[0] != 0.0 and not_pd is None):
+            raise RuntimeError(failed)
+        if flags[0] != 0.0:
+            raise np.linalg.LinAlgError(not_pd)
+
+    def _predict(self, test_x, index_set, want_var, include_noise=True):
+        xs = self._test_points(test_x)
         ns = xs.shape[0]
         # fused [mean | var] buffer: one collective for the sum over resolutions
         fused = torch.zeros((self.dy + 1, ns), dtype=self.dtype, device=self.device)
         mean = torch.zeros((ns, self.dy), dtype=self.dtype, device=self.device)
         var = fused[self.dy] if want_var else None
-        if index_set is None:
-            # every prediction is taken from resolution 0 (MRGP.py:726-755), which presumes ONE
-            # root region; with a multi-region first layer the test points need an index set
-            if self.n_regions[0] != 1:
-                raise ValueError('index_set_obj is required when the first layer has more than one region')
-            if self.owner[0][0] == self.rank:
-                self.posterior_obj[0].blocks[0].predict(xs, mean, var)
-        else:
-            n_layers = index_set.get_n_resolutions() + 1
-            for j in range(n_layers):
-                last = (j == n_layers - 1)
-                owned = self._owned(j)
-                if not owned:
-                    continue
-                # blocks of a layer write disjoint test ranges: equal-sized ones in ONE batched call, the
-                # others in flight together on the stream pool; layers accumulate into the same ranges and
-                # follow one another
-                if want_var:
-                    self.posterior_obj[j].predict_layer(self._x_dev, xs, index_set.bounds[j], set(owned), mean, var,
-                                                        include_noise and last,
-                                                        lambda cnt, nmax: _Fanout(self.device, cnt, nmax))
-                    continue
-                fan = _Fanout(self.device, len(owned), max(self.n_samps[j][l] for l in owned))
-                for l in owned:
-                    a, b = (int(v) for v in index_set.bounds[j][l])
-                    blk = self.posterior_obj[j].blocks[l]
-                    with torch.cuda.stream(fan.stream()):
-                        blk.predict(xs[a:b], mean[a:b], None)
-                fan.join()
+        # blocks of a layer write disjoint test ranges: equal-sized ones in ONE batched call, the others in flight
+        # together on the stream pool; layers accumulate into the same ranges and follow one another
+        for j, bounds, add_noise, owned in self._test_layers(index_set, ns, include_noise):
+            self.posterior_obj[j].predict_layer(self._x_dev, xs, bounds, owned, mean, var, add_noise)
         if self.world_size > 1:
             fused[:self.dy] = mean.t()
             dist.allreduce_sum_(fused, self.group)
@@ -451,28 +474,14 @@ class MultiResolutionGaussianProcess(object):
         ``adaptive_inputs`` (the warp's Jacobian is not built)."""
         if self.adaptive_inputs is True:
             raise TypeError('not yet supported')
-        if index_set_obj is not None:
-            self._check_index_set(index_set_obj, number_of_regions)
-        if not self._fitted:
-            raise RuntimeError('call fit() before predicting')
-        xs = self._prepare_test(test_x)
+        xs = self._test_points(test_x, index_set_obj, number_of_regions)
         ns, d = int(xs.shape[0]), int(xs.shape[1])
         q = self.dy
         fused = torch.zeros(ns * d * (q + 1), dtype=self.dtype, device=self.device)
         mean_grad = fused[:ns * d * q].view(ns, d, q)
         var_grad = fused[ns * d * q:].view(ns, d)
-        if index_set_obj is None:
-            if self.n_regions[0] != 1:
-                raise ValueError('index_set_obj is required when the first layer has more than one region')
-            if self.owner[0][0] == self.rank:
-                self.posterior_obj[0].blocks[0].predict_grad(xs, mean_grad, var_grad)
-        else:
-            for j in range(index_set_obj.get_n_resolutions() + 1):
-                owned = self._owned(j)
-                if not owned:
-                    continue
-                self.posterior_obj[j].predict_grad_layer(self._x_dev, xs, index_set_obj.bounds[j], set(owned), mean_grad,
-                                                         var_grad, lambda cnt, nmax: _Fanout(self.device, cnt, nmax))
+        for j, bounds, _, owned in self._test_layers(index_set_obj, ns):
+            self.posterior_obj[j].predict_grad_layer(self._x_dev, xs, bounds, owned, mean_grad, var_grad)
         if self.world_size > 1:
             dist.allreduce_sum_(fused, self.group)
         dmu = mean_grad.double().cpu().numpy()
@@ -484,49 +493,26 @@ class MultiResolutionGaussianProcess(object):
         return dmu, dvar
 
     # ------------------------------------------------------- joint distribution
-    def _joint_layers(self, index_set, ns, include_noise):
-        """(layer, test bounds, add noise) of every layer that contributes, by the rule of :meth:`_predict`: without an
-        index set the single root region of layer 0 serves every test point and no noise is added."""
-        if index_set is None:
-            if self.n_regions[0] != 1:
-                raise ValueError('index_set_obj is required when the first layer has more than one region')
-            return [(0, [(0, ns)], False)]
-        n_layers = index_set.get_n_resolutions() + 1
-        return [(j, index_set.bounds[j], include_noise and j == n_layers - 1) for j in range(n_layers)]
-
-    def _joint(self, xs, index_set, include_noise, cov_out=None, samples=None, seed=0, jitter=1e-6):
-        """Every owned block's share, then ONE sum over the ranks of [buffer | failure flag]."""
+    def _joint(self, xs, index_set, include_noise, rows, sampling, seed=0, jitter=1e-6):
+        """Every owned block's share of the (rows x N*) covariance or ``sampling`` buffer, summed over the ranks
+        (:meth:`_sum_shares`); returns the buffer."""
         ns = xs.shape[0]
-        buf = cov_out if cov_out is not None else samples
-        flag = torch.zeros(2, dtype=self.dtype, device=self.device)      # [not positive definite | any other failure]
+        fused = torch.zeros(rows * ns + 2, dtype=self.dtype, device=self.device)
+        buf = fused[:rows * ns].view(rows, ns)
         self.last_joint_jitter = [0.0] * self.n_layers
-        failure = None
-        for j, bounds, add_noise in self._joint_layers(index_set, ns, include_noise):
-            owned = self._owned(j)
-            if not owned:
-                continue
-            try:
-                self.last_joint_jitter[j] = self.posterior_obj[j].joint_layer(j, self._x_dev, xs, bounds, set(owned), add_noise,
-                                                                              cov_out, samples, seed, jitter)
-            except Exception as e:
-                # LinAlgError, the factorisation's schedule watchdog (RuntimeError), a failed C call ...: the other
-                # ranks wait in the collective, so join it with the flag set, then raise
-                if self.world_size == 1:
-                    raise
-                failure = e
-                flag[0 if isinstance(e, np.linalg.LinAlgError) else 1] = 1.0
-                break
+        layers = self._test_layers(index_set, ns, include_noise)
+
+        def share():
+            for j, bounds, add_noise, owned in layers:
+                self.last_joint_jitter[j] = self.posterior_obj[j].joint_layer(
+                    j, self._x_dev, xs, bounds, owned, add_noise, None if sampling else buf, buf if sampling else None,
+                    seed, jitter)
+
+        self._sum_shares(fused, share)
         if self.world_size > 1:
-            flat = torch.cat([buf.reshape(-1), flag])
-            dist.allreduce_sum_(flat, self.group)
-            buf.copy_(flat[:-2].view_as(buf))
-            if failure is not None:
-                raise failure
-            flags = flat[-2:].cpu().numpy()
-            if flags[1] != 0.0:
-                raise RuntimeError('joint predictive distribution failed on another rank (see its exception)')
-            if flags[0] != 0.0:
-                raise np.linalg.LinAlgError('joint predictive covariance not positive definite (a block owned by another rank)')
+            self._failed_elsewhere(fused[-2:].cpu().numpy(),
+                                   'joint predictive distribution failed on another rank (see its exception)',
+                                   'joint predictive covariance not positive definite (a block owned by another rank)')
         return buf
 
     def get_predicted_covariance(self, test_x, index_set_obj=None, number_of_regions=None, include_noise=True):
@@ -535,14 +521,8 @@ class MultiResolutionGaussianProcess(object):
         test points of different regions of a layer being 0.  ``include_noise``: the finest layer's block
         noise on the diagonal, as in :meth:`get_predicted_mean_and_var`, whose variance is this matrix's diagonal.
         Assembled on the device from the blocks' lower triangles: memory is N*^2 elements."""
-        if index_set_obj is not None:
-            self._check_index_set(index_set_obj, number_of_regions)
-        if not self._fitted:
-            raise RuntimeError('call fit() before predicting')
-        xs = self._prepare_test(test_x)
-        ns = xs.shape[0]
-        cov = torch.zeros((ns, ns), dtype=self.dtype, device=self.device)
-        self._joint(xs, index_set_obj, include_noise, cov_out=cov)
+        xs = self._test_points(test_x, index_set_obj, number_of_regions)
+        cov = self._joint(xs, index_set_obj, include_noise, xs.shape[0], sampling=False)
         cov = torch.tril(cov) + torch.tril(cov, -1).t()
         return cov.double().cpu().numpy()
 
@@ -560,14 +540,10 @@ class MultiResolutionGaussianProcess(object):
             raise ValueError('size must be at least 1')
         if not (float(jitter) >= 0.0):
             raise ValueError('jitter must be non-negative')
-        if not self._fitted:
-            raise RuntimeError('call fit() before predicting')
-        size = int(size)
         mean = self._predict(test_x, index_set_obj, want_var=False)[0]
-        xs = self._prepare_test(test_x)
-        ns = xs.shape[0]
-        out = torch.zeros((size * self.dy, ns), dtype=self.dtype, device=self.device)
-        self._joint(xs, index_set_obj, include_noise, samples=out, seed=int(seed), jitter=float(jitter))
+        xs = self._test_points(test_x)
+        size, ns = int(size), xs.shape[0]
+        out = self._joint(xs, index_set_obj, include_noise, size * self.dy, True, int(seed), float(jitter))
         dev_part = out.double().cpu().numpy().reshape(size, self.dy, ns).transpose(0, 2, 1)
         return mean[None, :, :] + dev_part
 
@@ -593,26 +569,11 @@ class MultiResolutionGaussianProcess(object):
             raise ValueError('layer must be in [0, %d), got %r' % (self.n_layers, layer))
         n, q = self._y.shape
         fused = torch.zeros(n * q + n + 2, dtype=self.dtype, device=self.device)
-        mean, var, flag = fused[:n * q].view(n, q), fused[n * q:n * q + n], fused[n * q + n:]
-        owned = self._owned(j)
-        failure = None
-        if owned:
-            try:
-                self.posterior_obj[j].loo_layer(self._y, self._slices(self._y, j), set(owned), mean, var,
-                                                lambda cnt, nmax: _Fanout(self.device, cnt, nmax))
-            except Exception as e:
-                # the other ranks wait in the collective: join it with the flag set, then raise (as _joint does)
-                if self.world_size == 1:
-                    raise
-                failure = e
-                flag[0 if isinstance(e, np.linalg.LinAlgError) else 1] = 1.0
-        if self.world_size > 1:
-            dist.allreduce_sum_(fused, self.group)
-            if failure is not None:
-                raise failure
+        mean, var = fused[:n * q].view(n, q), fused[n * q:n * q + n]
+        self._sum_shares(fused, lambda: self.posterior_obj[j].loo_layer(self._y, self._slices(self._y, j), self._owned(j),
+                                                                        mean, var))
         res = fused.double().cpu().numpy()
-        if res[-1] != 0.0 or res[-2] != 0.0:
-            raise RuntimeError('leave-one-out failed on another rank (see its exception)')
+        self._failed_elsewhere(res[-2:], 'leave-one-out failed on another rank (see its exception)')
         return res[:n * q].reshape(n, q).copy(), res[n * q:n * q + n].copy()
 
     def get_loo_likelihood(self, layer=None):

@@ -137,6 +137,30 @@ class DenseBlock(object):
             if t is not None:
                 t.record_stream(stream)
 
+    def _w_chunks(self, xs, chunk, what):
+        """(s0, s1, W) for every ``chunk`` test points of ``xs``: W = K(xs[s0:s1], x) L^-T, the cross-Gram solved
+        row-wise against the factor.  ``what`` names the caller's result in the error for a factor that was not kept."""
+        if self.lbuf is None:
+            raise RuntimeError('%s needs the Cholesky factor: fit with keep_factors=True' % what)
+        k = self.kernel
+        ns = xs.shape[0]
+        for s0 in range(0, ns, chunk):
+            s1 = min(ns, s0 + chunk)
+            w = dev.rbf_cross(xs[s0:s1], self.x, k.l, k.sf, cov=k.cov)
+            dev.trsm_rows(self.lbuf, self.n, self.ws, w, s1 - s0)
+            yield s0, s1, w
+
+    def joint_call(self, region, a, b):
+        """This block as a batch of one for :func:`joint_run` at the test rows [a, b): its own inputs with start 0, its
+        factor buffer as the arena."""
+        if self.lbuf is None:
+            raise RuntimeError('the joint covariance needs the Cholesky factor: fit with keep_factors=True')
+        starts = torch.zeros(1, dtype=torch.int64, device=self.x.device)
+        t_starts = torch.full((1,), int(a), dtype=torch.int64, device=self.x.device)
+        one = _FittedBatch([region], self.n, starts, self.lbuf.unsqueeze(0), self.ws.unsqueeze(0), self.z.unsqueeze(0),
+                           self.bias.unsqueeze(0), self.noise.reshape(1))
+        return _JointCall(one, self.x, t_starts, int(b) - int(a))
+
     def predict(self, xs, mean_out, var_out=None, extra_var=0.0, chunk=16384, add_noise=False):
         """Accumulate this block's predictive mean (and latent variance) at ``xs``
         into ``mean_out`` (ns x q) / ``var_out`` (ns,).  ``add_noise``: add the block's noise
@@ -145,13 +169,7 @@ class DenseBlock(object):
         if var_out is None:
             dev.predict_mean(self.x, self.alpha, xs, k.l, k.sf, self.bias, out=mean_out, accumulate=True, cov=k.cov)
             return
-        if self.lbuf is None:
-            raise RuntimeError('predictive variance needs the Cholesky factor: fit with keep_factors=True')
-        ns = xs.shape[0]
-        for s0 in range(0, ns, chunk):
-            s1 = min(ns, s0 + chunk)
-            w = dev.rbf_cross(xs[s0:s1], self.x, k.l, k.sf, cov=k.cov)
-            dev.trsm_rows(self.lbuf, self.n, self.ws, w, s1 - s0)
+        for s0, s1, w in self._w_chunks(xs, chunk, 'predictive variance'):
             dev.predict_from_w(w, s1 - s0, self.n, self.z, k.sf, extra_var, self.bias,
                                mean_out[s0:s1], var_out[s0:s1], accumulate=True,
                                extra_var_dev=self.noise if add_noise else None)
@@ -165,13 +183,7 @@ class DenseBlock(object):
             if mean_grad_out is not None:
                 dev.cov_predict_grad(self.x, self.alpha, xs, k.l, k.sf, mean_grad=mean_grad_out, accumulate=True, cov=k.cov)
             return
-        if self.lbuf is None:
-            raise RuntimeError('the gradient of the predictive variance needs the Cholesky factor: fit with keep_factors=True')
-        ns = xs.shape[0]
-        for s0 in range(0, ns, chunk):
-            s1 = min(ns, s0 + chunk)
-            w = dev.rbf_cross(xs[s0:s1], self.x, k.l, k.sf, cov=k.cov)
-            dev.trsm_rows(self.lbuf, self.n, self.ws, w, s1 - s0)
+        for s0, s1, w in self._w_chunks(xs, chunk, 'the gradient of the predictive variance'):
             dev.trsm_rows_lt(self.lbuf, self.n, self.ws, w, s1 - s0)
             dev.cov_predict_grad(self.x, self.alpha, xs[s0:s1], k.l, k.sf, beta=w,
                                  mean_grad=None if mean_grad_out is None else mean_grad_out[s0:s1],
@@ -218,6 +230,50 @@ def _same_rows(arrays, group):
     return all(row_of(a[l]) == row_of(arrays[0][l]) for a in arrays[1:] for l in group)
 
 
+def _groups_by_size(x, regions, arrays):
+    """[(n, regions of n rows, sliced)] over ``regions``.  sliced: a batched call may address these blocks by ONE row
+    offset into the layer's arrays -- every one of ``arrays`` (lists of region views) is a row-major 2-D array of which
+    the region views are slices, at the same rows in all of them."""
+    by_size = {}
+    for l in regions:
+        by_size.setdefault(int(x[l].shape[0]), []).append(l)
+    return [(n_l, group, all(_layer_array(v, group) is not None for v in arrays) and _same_rows(arrays, group))
+            for n_l, group in by_size.items()]
+
+
+def _row_starts(sub, device, *arrays):
+    """Device int64 tensor of the first row of every region of ``sub`` in the layer's arrays, which must be the same in
+    all of ``arrays`` (lists of region views)."""
+    def row_of(views, l):
+        return views[l].storage_offset() // views[l].stride(0)
+    rows = [row_of(arrays[0], l) for l in sub]
+    if any(row_of(v, l) != r for v in arrays[1:] for l, r in zip(sub, rows)):
+        raise ValueError('the region views of a layer must be the same row ranges of x, y, f_bar and train_out')
+    return torch.tensor(rows, dtype=torch.int64).to(device, non_blocking=True)
+
+
+def _ws_bytes(n, dtype):
+    """Bytes of one block's factorisation workspace in an arena: a multiple of 16, never 0."""
+    return max((dev.potrf_workspace_bytes(n, dtype) + 15) // 16 * 16, 16)
+
+
+def free_device_bytes(device):
+    """Bytes a new allocation on ``device`` can get: what the device reports free plus what the caching allocator holds
+    without using it.  Every memory-bounded sub-batch split takes its budget as a fraction of this."""
+    return torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+
+
+def _arena_geometry(y0, n, n_blocks, per_block_bytes, fraction):
+    """(device, dtype, ld, ws_bytes, per_call) of the arenas that hold ``n_blocks`` (n x n) factors beside targets like
+    ``y0``: padded pitch, workspace bytes per block, and how many blocks one call may take so that
+    per_block_bytes(ld, ws_bytes, esz) each fit into ``fraction`` of the free memory."""
+    device, dtype = y0.device, y0.dtype
+    ld, ws_bytes = dev.padded_ld(n), _ws_bytes(n, dtype)
+    per_block = per_block_bytes(ld, ws_bytes, y0.element_size())
+    per_call = int(max(1, min(n_blocks, fraction * free_device_bytes(device) // per_block)))
+    return device, dtype, ld, ws_bytes, per_call
+
+
 class _FittedBatch(object):
     """Equal-sized blocks fitted together: their factors share one arena, so that a prediction can
     address block i at ``base + i * stride`` (cimrgp_layer_predict)."""
@@ -225,6 +281,44 @@ class _FittedBatch(object):
     def __init__(self, regions, n, starts, karena, ws_arena, z, bias, noise):
         self.regions, self.n, self.starts = list(regions), int(n), starts
         self.karena, self.ws_arena, self.z, self.bias, self.noise = karena, ws_arena, z, bias, noise
+
+    def part(self, i0, nb):
+        """Blocks [i0, i0 + nb) of the batch: views, nothing is copied."""
+        s = slice(i0, i0 + nb)
+        return _FittedBatch(self.regions[s], self.n, self.starts[s], self.karena[s], self.ws_arena[s], self.z[s],
+                            self.bias[s], self.noise[s])
+
+    def alpha(self):
+        """(batch, n, q) weights K^-1 r, recomputed from a copy of z = L^-1 r: a batch keeps z, not alpha."""
+        return dev.solve_lt_batched(self.karena, self.n, self.karena.stride(1), self.ws_arena, self.z.clone())
+
+
+def plan_batched_calls(regions, owned, test_bounds, per_block_bytes, budget):
+    """Which blocks of one batch go through batched calls.  ``regions``: the batch's region ids in arena order; ``owned``:
+    the regions to compute; ``test_bounds[l]`` = (a, b): region l serves the test rows [a, b), or None for an operation on
+    the training rows; ``per_block_bytes(ns)``: work memory of one block at ns test points; ``budget``: bytes one call may
+    take.  Owned blocks with equally many test points form a group; a group goes through batched calls if it has test
+    points, at least 2 blocks, and its arena indices are one contiguous run, cut into sub-batches of
+    max(1, budget // per_block_bytes(ns)) blocks.  Returns (calls, covered): calls = [(i0, nb, ns, [first test row of
+    each block])] over the arena indices [i0, i0 + nb) (ns None and no rows without test bounds), covered = the regions
+    they serve.  Pure: touches no device."""
+    by_ns = {}
+    for i, l in enumerate(regions):
+        if l in owned:
+            a, b = (None, None) if test_bounds is None else (int(v) for v in test_bounds[l])
+            by_ns.setdefault(None if a is None else b - a, []).append((i, a))
+    calls, covered = [], set()
+    for ns, items in by_ns.items():
+        idx = [i for i, _ in items]
+        contiguous = idx == list(range(idx[0], idx[0] + len(idx)))
+        if (ns is not None and ns <= 0) or len(items) < 2 or not contiguous:
+            continue
+        per_call = int(max(1, min(len(items), budget // max(1, per_block_bytes(ns)))))
+        for c0 in range(0, len(items), per_call):
+            part = items[c0:c0 + per_call]
+            calls.append((part[0][0], len(part), ns, [a for _, a in part if a is not None]))
+        covered.update(regions[i] for i in idx)
+    return calls, covered
 
 
 #: escalations of a block's relative jitter (x 10 each) before a joint factorisation is given up
@@ -240,27 +334,15 @@ LOO_SCRATCH_BYTES = 512 << 20
 
 
 class _JointCall(object):
-    """Blocks of one layer that go through one cimrgp_layer_joint_cov call: the training side (layer arrays, starts,
-    factor and workspace arenas), the test side (t_starts, ns) and the blocks' noise (nb,) on the device."""
+    """Blocks of one layer that go through one cimrgp_layer_joint_cov call: the training side (a :class:`_FittedBatch`
+    slice and ``x``, the array its starts index) and the test side (t_starts, ns)."""
 
-    def __init__(self, regions, x, starts, n, t_starts, ns, larena, ws_arena, noise):
-        self.regions, self.x, self.starts, self.n = list(regions), x, starts, int(n)
-        self.t_starts, self.ns, self.larena, self.ws_arena, self.noise = t_starts, int(ns), larena, ws_arena, noise
+    def __init__(self, batch, x, t_starts, ns):
+        self.batch, self.x, self.t_starts, self.ns = batch, x, t_starts, int(ns)
 
     def part(self, i):
         """Block i alone (batch = 1): for a factorisation retried with more jitter."""
-        return _JointCall([self.regions[i]], self.x, self.starts[i:i + 1], self.n, self.t_starts[i:i + 1], self.ns,
-                          self.larena[i:i + 1], self.ws_arena[i:i + 1], self.noise[i:i + 1])
-
-
-def single_joint_call(blk, region, xs_device, a, b):
-    """A fitted :class:`DenseBlock` as a batch of one: its own inputs with start 0, its factor buffer as the arena."""
-    if blk.lbuf is None:
-        raise RuntimeError('the joint covariance needs the Cholesky factor: fit with keep_factors=True')
-    starts = torch.zeros(1, dtype=torch.int64, device=xs_device)
-    t_starts = torch.full((1,), int(a), dtype=torch.int64, device=xs_device)
-    return _JointCall([region], blk.x, starts, blk.n, t_starts, int(b) - int(a), blk.lbuf.unsqueeze(0), blk.ws.unsqueeze(0),
-                      blk.noise.reshape(1))
+        return _JointCall(self.batch.part(i, 1), self.x, self.t_starts[i:i + 1], self.ns)
 
 
 def joint_run(call, kernel, xs, layer, add_noise, cov_out=None, samples=None, seed=0, jitter=1e-6):
@@ -270,45 +352,47 @@ def joint_run(call, kernel, xs, layer, add_noise, cov_out=None, samples=None, se
     retried alone with 10x the jitter (from JOINT_JITTER_FLOOR when it is smaller), at most JOINT_RETRIES times, then LinAlgError names the layer and region --
     and chol(.) Z is added, Z_b[c][i] = phi(seed, layer 2^32 + region, c, i).  Returns the largest relative jitter
     used (0.0 without samples)."""
-    nb, ns, n = len(call.regions), call.ns, call.n
+    regions = call.batch.regions
+    nb, ns, n = len(regions), call.ns, call.batch.n
     if ns <= 0 or nb == 0:
         return 0.0
+
+    def joint_cov(c, diag, *factor_out):
+        dev.layer_joint_cov(c.x, c.batch.starts, n, xs, c.t_starts, ns, kernel.l, sf2, c.batch.karena, c.batch.ws_arena, diag,
+                            *factor_out, cov=kernel.cov)
+
     dtype, device = xs.dtype, xs.device
     sf2 = float(kernel.sf)
     ldc = dev.joint_ld(ns, dtype)
     carena = torch.empty((nb, ns, ldc), dtype=dtype, device=device)
-    extra = call.noise.to(dtype) if add_noise else torch.zeros(nb, dtype=dtype, device=device)
+    extra = call.batch.noise.to(dtype) if add_noise else torch.zeros(nb, dtype=dtype, device=device)
     if samples is None:
-        dev.layer_joint_cov(call.x, call.starts, n, xs, call.t_starts, ns, kernel.l, sf2, call.larena, call.ws_arena, extra,
-                            carena, cov=kernel.cov)
+        joint_cov(call, extra, carena)
         for i, a in enumerate(call.t_starts.cpu().tolist()):
             cov_out[a:a + ns, a:a + ns] += torch.tril(carena[i, :, :ns])
         return 0.0
-    cws_bytes = max((dev.potrf_workspace_bytes(ns, dtype) + 15) // 16 * 16, 16)
-    cws = torch.empty((nb, cws_bytes), dtype=torch.uint8, device=device)
+    cws = torch.empty((nb, _ws_bytes(ns, dtype)), dtype=torch.uint8, device=device)
     info = torch.zeros(nb, dtype=torch.int32, device=device)
     diag = extra + jitter * sf2
-    dev.layer_joint_cov(call.x, call.starts, n, xs, call.t_starts, ns, kernel.l, sf2, call.larena, call.ws_arena, diag, carena,
-                        cws, info, cov=kernel.cov)
+    joint_cov(call, diag, carena, cws, info)
     used = float(jitter)
     for i in np.flatnonzero(info.cpu().numpy() != 0):          # info read once per call
         one, rel = call.part(int(i)), max(float(jitter), JOINT_JITTER_FLOOR)
         for _ in range(JOINT_RETRIES):
             rel *= 10.0
-            dev.layer_joint_cov(one.x, one.starts, n, xs, one.t_starts, ns, kernel.l, sf2, one.larena, one.ws_arena,
-                                extra[i:i + 1] + rel * sf2, carena[i:i + 1], cws[i:i + 1], info[i:i + 1], cov=kernel.cov)
+            joint_cov(one, extra[i:i + 1] + rel * sf2, carena[i:i + 1], cws[i:i + 1], info[i:i + 1])
             code = int(info[i].item())
             if code == 0:
                 break
         if code != 0:
             if dev.is_watchdog(code):
                 raise RuntimeError('cimrgp_potrf: schedule watchdog (joint factor of layer %d, region %d)'
-                                   % (layer, call.regions[i]))
+                                   % (layer, regions[i]))
             raise np.linalg.LinAlgError('joint predictive covariance of layer %d, region %d is not positive definite '
                                         'with a relative jitter of %g (leading minor of order %d)'
-                                        % (layer, call.regions[i], rel, code))
+                                        % (layer, regions[i], rel, code))
         used = max(used, rel)
-    keys = torch.tensor([(int(layer) << 32) + int(l) for l in call.regions], dtype=torch.int64).to(device)
+    keys = torch.tensor([(int(layer) << 32) + int(l) for l in regions], dtype=torch.int64).to(device)
     cols = int(samples.shape[0])
     ldz = dev.joint_ld(ns, dtype)
     chunk = int(max(1, min(cols, JOINT_Z_BYTES // (nb * ldz * xs.element_size()))))
@@ -358,15 +442,8 @@ class DensePosterior(object):
             return
         # equal-sized small blocks: one batch per size (a uniform index set has at most two sizes per
         # layer, the last region taking the remainder, IndexSetGenerator.py:51-65)
-        by_size = {}
-        for l in regions:
-            by_size.setdefault(int(x[l].shape[0]), []).append(l)
         single = []
-        for n_l, group in by_size.items():
-            # the batched call addresses a block by ONE row offset into the layer's arrays: every array must be a
-            # row-major 2-D array of which the region views are slices, at the same rows in all four
-            sliced = all(_layer_array(v, group) is not None for v in (y_mean, x, f_bar, train_out)) \
-                and _same_rows((y_mean, x, f_bar, train_out), group)
+        for n_l, group, sliced in _groups_by_size(x, regions, (y_mean, x, f_bar, train_out)):
             if len(group) >= 2 and n_l <= BATCH_MAX_N and sliced:
                 self._fit_batched(group, y_mean, x, f_bar, train_out, shared_bias, shared_noise, keep_factors)
             else:
@@ -392,21 +469,13 @@ class DensePosterior(object):
         k = self.kernel
         n = int(x[group[0]].shape[0])
         q = self.dy
-        device, dtype = y_mean[group[0]].device, y_mean[group[0]].dtype
-        ld = dev.padded_ld(n)
-        ws_bytes = max((dev.potrf_workspace_bytes(n, dtype) + 15) // 16 * 16, 16)
-        esz = torch.empty((), dtype=dtype).element_size()
-        per_block = n * ld * esz + ws_bytes + 6 * q * ld * esz
-        free_bytes = torch.cuda.mem_get_info(device)[0]
-        cached = torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
-        budget = (free_bytes + cached) * (0.8 if keep_factors else 0.4)
-        per_call = int(max(1, min(len(group), budget // per_block)))
+        device, dtype, ld, ws_bytes, per_call = _arena_geometry(
+            y_mean[group[0]], n, len(group), lambda ld, ws, esz: n * ld * esz + ws + 6 * q * ld * esz,
+            0.8 if keep_factors else 0.4)
         # the layer's arrays: every region view is a slice of them (regions are contiguous ranges,
         # Inputs.py:57-60), so a block is a row offset into them
         y_all, x_all = _layer_array(y_mean, group), _layer_array(x, group)
         f_all, t_all = _layer_array(f_bar, group), _layer_array(train_out, group)
-        def row_of(views, l):
-            return views[l].storage_offset() // views[l].stride(0)
         for c0 in range(0, len(group), per_call):
             sub = group[c0:c0 + per_call]
             nb = len(sub)
@@ -417,10 +486,7 @@ class DensePosterior(object):
             noise = torch.empty(nb, dtype=dtype, device=device)
             z = torch.empty((nb, n, q), dtype=dtype, device=device)
             alpha = torch.empty((nb, n, q), dtype=dtype, device=device)
-            rows_y = [row_of(y_mean, l) for l in sub]
-            if any(row_of(v, l) != r for v in (x, f_bar, train_out) for l, r in zip(sub, rows_y)):
-                raise ValueError('the region views of a layer must be the same row ranges of x, y, f_bar and train_out')
-            starts = torch.tensor(rows_y, dtype=torch.int64).to(device, non_blocking=True)
+            starts = _row_starts(sub, device, y_mean, x, f_bar, train_out)
             dev.layer_fit(x_all, y_all, f_all, t_all, starts, n, k.l, k.sf, -1.0 if k.noise is None else float(k.noise),
                           NOISE_FRACTION, NOISE_FLOOR * k.sf, shared_bias, shared_noise, karena, ws_arena, info, bias, noise,
                           z, alpha, cov=k.cov)
@@ -456,11 +522,7 @@ class DensePosterior(object):
         if not self.bias_region_specific:
             shared_bias = dev.block_stats(self._whole_layer(y_mean), self._whole_layer(f_bar))[:q]
         lml, grad, failure = 0.0, np.zeros(3), 0.0
-        by_size = {}
-        for l in regions:
-            by_size.setdefault(int(x[l].shape[0]), []).append(l)
-        for n_l, group in by_size.items():
-            sliced = all(_layer_array(v, group) is not None for v in (y_mean, x, f_bar)) and _same_rows((y_mean, x, f_bar), group)
+        for n_l, group, sliced in _groups_by_size(x, regions, (y_mean, x, f_bar)):
             if n_l <= BATCH_MAX_N and sliced:
                 a, g, f = self._objective_batched(group, ell, sf2, noise, y_mean, x, f_bar, shared_bias)
                 lml, grad, failure = lml + a, grad + g, max(failure, f)
@@ -486,21 +548,15 @@ class DensePosterior(object):
         :meth:`_fit_batched` (the K^-1 arena and the carried identity rows on top of the factor)."""
         n = int(x[group[0]].shape[0])
         q = self.dy
-        device, dtype = y_mean[group[0]].device, y_mean[group[0]].dtype
-        ld = dev.padded_ld(n)
-        ws_bytes = max((dev.potrf_workspace_bytes(n, dtype) + 15) // 16 * 16, 16)
-        esz = torch.empty((), dtype=dtype).element_size()
-        per_block = 2 * n * ld * esz + ws_bytes + dev.layer_lml_scratch_bytes(n, q, 1, dtype)
-        free_bytes = torch.cuda.mem_get_info(device)[0]
-        cached = torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
-        per_call = int(max(1, min(len(group), (free_bytes + cached) * 0.8 // per_block)))
+        scratch = dev.layer_lml_scratch_bytes(n, q, 1, y_mean[group[0]].dtype)
+        device, dtype, ld, ws_bytes, per_call = _arena_geometry(
+            y_mean[group[0]], n, len(group), lambda ld, ws, esz: 2 * n * ld * esz + ws + scratch, 0.8)
         y_all, x_all, f_all = _layer_array(y_mean, group), _layer_array(x, group), _layer_array(f_bar, group)
         lml, grad, failure = 0.0, np.zeros(3), 0.0
         for c0 in range(0, len(group), per_call):
             sub = group[c0:c0 + per_call]
             nb = len(sub)
-            rows = [y_mean[l].storage_offset() // y_mean[l].stride(0) for l in sub]
-            starts = torch.tensor(rows, dtype=torch.int64).to(device, non_blocking=True)
+            starts = _row_starts(sub, device, y_mean, x, f_bar)
             karena = torch.empty((nb, n, ld), dtype=dtype, device=device)
             kinv = torch.empty((nb, n, ld), dtype=dtype, device=device)
             ws_arena = torch.empty((nb, ws_bytes), dtype=torch.uint8, device=device)
@@ -518,158 +574,102 @@ class DensePosterior(object):
             grad += vals[:, 1:].sum(axis=0)
         return lml, grad, failure
 
-    def predict_layer(self, x_all, xs, test_bounds, owned, mean, var, add_noise, fan_factory):
+    def _run_layer(self, owned, test_bounds, device, per_block_bytes, budget, batched, single, fan_out=True):
+        """Run one operation over the ``owned`` blocks of the layer.  Per batch of blocks fitted together,
+        :func:`plan_batched_calls` picks the sub-batches (``per_block_bytes(batch, ns)`` bytes of work memory per block
+        against ``budget()`` bytes, asked once per batch) and each goes to ``batched(part, t_starts, ns)``: a
+        :meth:`_FittedBatch.part`, the device tensor of its blocks' first test rows and their common number of test
+        points (both None when ``test_bounds`` is None: an operation on the training rows).  The owned blocks left over go
+        to ``single(l, a, b)`` in region order -- (a, b) = test_bounds[l]; blocks without test points are passed over --
+        dealt to the stream pool (``fan_out``), else on the caller's stream.  ``batched`` None: all one by one."""
+        own, done = set(owned), set()
+        for bt in (self.batches if batched is not None else ()):
+            calls, covered = plan_batched_calls(bt.regions, own, test_bounds, lambda ns: per_block_bytes(bt, ns), budget())
+            for i0, nb, ns, rows in calls:
+                t_starts = None if ns is None else torch.tensor(rows, dtype=torch.int64).to(device, non_blocking=True)
+                batched(bt.part(i0, nb), t_starts, ns)
+            done |= covered
+        rest = []
+        for l in sorted(own - done):
+            a, b = (None, None) if test_bounds is None else (int(v) for v in test_bounds[l])
+            if a is None or b > a:
+                rest.append((l, a, b))
+        if not rest:
+            return
+        fan = _Fanout(device, len(rest) if fan_out else 1, max(self.blocks[l].n for l, _, _ in rest))
+        for item in rest:
+            with torch.cuda.stream(fan.stream()):
+                single(*item)
+        fan.join()
+
+    def predict_layer(self, x_all, xs, test_bounds, owned, mean, var, add_noise):
         """Accumulate the layer's predictive mean and variance at the test points: test block l =
         rows test_bounds[l] of ``xs``, served by training block l (MRGP.py:782-803).  Blocks that were fitted
         together and have equally many test points go through ONE batched call per sub-batch
-        (cimrgp_layer_predict); the others one by one on the stream pool."""
-        done = set()
-        for bt in self.batches:
-            by_ns = {}
-            for i, l in enumerate(bt.regions):
-                if l in owned:
-                    a, b = (int(v) for v in test_bounds[l])
-                    by_ns.setdefault(b - a, []).append((i, a))
-            for ns, items in by_ns.items():
-                idx = [i for i, _ in items]
-                contiguous = idx == list(range(idx[0], idx[0] + len(idx)))
-                if ns <= 0 or len(items) < 2 or not contiguous:
-                    continue
-                ldw = dev.padded_ld(bt.n)
-                esz = xs.element_size()
-                free_bytes = torch.cuda.mem_get_info(xs.device)[0] + torch.cuda.memory_reserved(xs.device) \
-                    - torch.cuda.memory_allocated(xs.device)
-                per_call = int(max(1, min(len(items), (0.5 * free_bytes) // max(1, ns * ldw * esz))))
-                for c0 in range(0, len(items), per_call):
-                    part = items[c0:c0 + per_call]
-                    i0, nb = part[0][0], len(part)
-                    t_starts = torch.tensor([a for _, a in part], dtype=torch.int64).to(xs.device, non_blocking=True)
-                    dev.layer_predict(x_all, bt.starts[i0:i0 + nb], bt.n, xs, t_starts, ns, self.kernel.l, self.kernel.sf,
-                                      bt.karena[i0:i0 + nb], bt.ws_arena[i0:i0 + nb], bt.z[i0:i0 + nb], bt.bias[i0:i0 + nb],
-                                      bt.noise[i0:i0 + nb] if add_noise else None, mean, var, cov=self.kernel.cov)
-                done.update(bt.regions[i] for i, _ in items)
-        rest = [l for l in owned if l not in done]
-        if not rest:
-            return
-        fan = fan_factory(len(rest), max(self.blocks[l].n for l in rest))
-        for l in rest:
-            a, b = (int(v) for v in test_bounds[l])
-            with torch.cuda.stream(fan.stream()):
-                self.blocks[l].predict(xs[a:b], mean[a:b], var[a:b], add_noise=add_noise)
-        fan.join()
+        (cimrgp_layer_predict); the others one by one on the stream pool (:meth:`_run_layer`).  ``var`` None: the mean
+        alone, every block through the fused :func:`device.predict_mean`, which never forms W."""
+        k = self.kernel
 
-    def predict_grad_layer(self, x_all, xs, test_bounds, owned, mean_grad, var_grad, fan_factory):
+        def batched(bt, t_starts, ns):
+            dev.layer_predict(x_all, bt.starts, bt.n, xs, t_starts, ns, k.l, k.sf, bt.karena, bt.ws_arena, bt.z, bt.bias,
+                              bt.noise if add_noise else None, mean, var, cov=k.cov)
+
+        def single(l, a, b):
+            self.blocks[l].predict(xs[a:b], mean[a:b], None if var is None else var[a:b], add_noise=add_noise)
+
+        self._run_layer(owned, test_bounds, xs.device, lambda bt, ns: ns * dev.padded_ld(bt.n) * xs.element_size(),
+                        lambda: 0.5 * free_device_bytes(xs.device), batched if var is not None else None, single)
+
+    def predict_grad_layer(self, x_all, xs, test_bounds, owned, mean_grad, var_grad):
         """Accumulate the layer's predictive gradients at the test points (test block l = rows test_bounds[l] of ``xs``,
-        served by training block l), grouped as :meth:`predict_layer` groups the blocks: ONE
-        cimrgp_layer_predict_grad_cov call per memory-bounded sub-batch of blocks fitted together with equally many test
-        points (their alpha is recomputed from a copy of z: a batch keeps z, not alpha), the others one by one on the
-        stream pool."""
-        done = set()
-        for bt in self.batches:
-            by_ns = {}
-            for i, l in enumerate(bt.regions):
-                if l in owned:
-                    a, b = (int(v) for v in test_bounds[l])
-                    by_ns.setdefault(b - a, []).append((i, a))
-            for ns, items in by_ns.items():
-                idx = [i for i, _ in items]
-                contiguous = idx == list(range(idx[0], idx[0] + len(idx)))
-                if ns <= 0 or len(items) < 2 or not contiguous:
-                    continue
-                ldw = dev.padded_ld(bt.n)
-                esz = xs.element_size()
-                free_bytes = torch.cuda.mem_get_info(xs.device)[0] + torch.cuda.memory_reserved(xs.device) \
-                    - torch.cuda.memory_allocated(xs.device)
-                per_block = (ns * ldw + 2 * bt.n * self.dy) * esz
-                per_call = int(max(1, min(len(items), (0.5 * free_bytes) // max(1, per_block))))
-                for c0 in range(0, len(items), per_call):
-                    part = items[c0:c0 + per_call]
-                    i0, nb = part[0][0], len(part)
-                    t_starts = torch.tensor([a for _, a in part], dtype=torch.int64).to(xs.device, non_blocking=True)
-                    karena, ws_arena = bt.karena[i0:i0 + nb], bt.ws_arena[i0:i0 + nb]
-                    alpha = dev.solve_lt_batched(karena, bt.n, karena.stride(1), ws_arena, bt.z[i0:i0 + nb].clone())
-                    dev.layer_predict_grad(x_all, bt.starts[i0:i0 + nb], bt.n, xs, t_starts, ns, self.kernel.l, self.kernel.sf,
-                                           karena, ws_arena, alpha, mean_grad, var_grad, cov=self.kernel.cov)
-                done.update(bt.regions[i] for i, _ in items)
-        rest = [l for l in owned if l not in done]
-        if not rest:
-            return
-        fan = fan_factory(len(rest), max(self.blocks[l].n for l in rest))
-        for l in rest:
-            a, b = (int(v) for v in test_bounds[l])
-            if b <= a:
-                continue
-            with torch.cuda.stream(fan.stream()):
-                self.blocks[l].predict_grad(xs[a:b], mean_grad[a:b], None if var_grad is None else var_grad[a:b])
-        fan.join()
+        served by training block l) through :meth:`_run_layer`: ONE cimrgp_layer_predict_grad_cov call per sub-batch
+        (with :meth:`_FittedBatch.alpha`), the others one by one on the stream pool."""
+        k = self.kernel
 
-    def loo_layer(self, y_all, y, owned, mean, var, fan_factory):
+        def batched(bt, t_starts, ns):
+            dev.layer_predict_grad(x_all, bt.starts, bt.n, xs, t_starts, ns, k.l, k.sf, bt.karena, bt.ws_arena, bt.alpha(),
+                                   mean_grad, var_grad, cov=k.cov)
+
+        def single(l, a, b):
+            self.blocks[l].predict_grad(xs[a:b], mean_grad[a:b], None if var_grad is None else var_grad[a:b])
+
+        self._run_layer(owned, test_bounds, xs.device,
+                        lambda bt, ns: (ns * dev.padded_ld(bt.n) + 2 * bt.n * self.dy) * xs.element_size(),
+                        lambda: 0.5 * free_device_bytes(xs.device), batched, single)
+
+    def loo_layer(self, y_all, y, owned, mean, var):
         """Leave-one-out prediction of the layer's own targets by its ``owned`` blocks (:meth:`DenseBlock.loo`), written
         into the rows of ``mean`` (N x q) and ``var`` (N,) that each block's region covers.  ``y_all``: the (N x q)
-        observations, ``y``: its region views (lists indexed by region, as for :meth:`update_scale_given_axis`).  Grouped
-        as :meth:`predict_grad_layer` groups the blocks: the owned blocks of a batch fitted together go through ONE
-        cimrgp_kinv_diag_batched call per sub-batch (scratch bounded by LOO_SCRATCH_BYTES; their alpha is recomputed from
-        a copy of z: a batch keeps z, not alpha), the others one by one on the stream pool."""
-        done = set()
-        for bt in self.batches:
-            idx = [i for i, l in enumerate(bt.regions) if l in owned]
-            if len(idx) < 2 or idx != list(range(idx[0], idx[0] + len(idx))):
-                continue
-            strip = dev.kinv_diag_scratch_bytes(bt.n, 256, y_all.dtype)
-            per_call = int(max(1, min(len(idx), LOO_SCRATCH_BYTES // strip)))
-            for c0 in range(0, len(idx), per_call):
-                i0, nb = idx[c0], len(idx[c0:c0 + per_call])
-                karena, ws_arena = bt.karena[i0:i0 + nb], bt.ws_arena[i0:i0 + nb]
-                alpha = dev.solve_lt_batched(karena, bt.n, karena.stride(1), ws_arena, bt.z[i0:i0 + nb].clone())
-                d = dev.kinv_diag_batched(karena, bt.n, ws_arena, LOO_SCRATCH_BYTES)
-                dev.loo(y_all, alpha, d, mean, var, starts=bt.starts[i0:i0 + nb])
-            done.update(bt.regions[i] for i in idx)
-        rest = [l for l in owned if l not in done]
-        if not rest:
-            return
-        fan = fan_factory(len(rest), max(self.blocks[l].n for l in rest))
-        for l in rest:
-            a = y[l].storage_offset() // y[l].stride(0)
-            b = a + int(y[l].shape[0])
-            with torch.cuda.stream(fan.stream()):
-                self.blocks[l].loo(y[l], mean[a:b], None if var is None else var[a:b])
-        fan.join()
+        observations, ``y``: its region views (lists indexed by region, as for :meth:`update_scale_given_axis`).  Through
+        :meth:`_run_layer` on the training rows: ONE cimrgp_kinv_diag_batched call per sub-batch (scratch bounded by
+        LOO_SCRATCH_BYTES, with :meth:`_FittedBatch.alpha`), the others one by one on the stream pool."""
+        def batched(bt, t_starts, ns):
+            alpha = bt.alpha()
+            d = dev.kinv_diag_batched(bt.karena, bt.n, bt.ws_arena, LOO_SCRATCH_BYTES)
+            dev.loo(y_all, alpha, d, mean, var, starts=bt.starts)
+
+        def single(l, a, b):
+            r0 = y[l].storage_offset() // y[l].stride(0)
+            r1 = r0 + int(y[l].shape[0])
+            self.blocks[l].loo(y[l], mean[r0:r1], None if var is None else var[r0:r1])
+
+        self._run_layer(owned, None, y_all.device, lambda bt, ns: dev.kinv_diag_scratch_bytes(bt.n, 256, y_all.dtype),
+                        lambda: LOO_SCRATCH_BYTES, batched, single)
 
     def joint_layer(self, layer, x_all, xs, test_bounds, owned, add_noise, cov_out=None, samples=None, seed=0, jitter=1e-6):
         """This layer's share of the joint predictive distribution at the test points (test block l = rows
-        test_bounds[l] of ``xs``, served by training block l), through :func:`joint_run`: blocks that were fitted
-        together and have equally many test points in ONE cimrgp_layer_joint_cov call per memory-bounded sub-batch (as
-        :meth:`predict_layer` groups them), the others as batches of one.  Returns the largest relative jitter used."""
-        calls, done = [], set()
-        esz = xs.element_size()
-        for bt in self.batches:
-            by_ns = {}
-            for i, l in enumerate(bt.regions):
-                if l in owned:
-                    a, b = (int(v) for v in test_bounds[l])
-                    by_ns.setdefault(b - a, []).append((i, a))
-            for ns, items in by_ns.items():
-                idx = [i for i, _ in items]
-                contiguous = idx == list(range(idx[0], idx[0] + len(idx)))
-                if ns <= 0 or len(items) < 2 or not contiguous:
-                    continue
-                ldc, ldw = dev.joint_ld(ns, xs.dtype), dev.joint_ld(bt.n, xs.dtype)
-                per_block = ns * (ldc + ldw) * esz + dev.potrf_workspace_bytes(ns, xs.dtype) + 16
-                free_bytes = torch.cuda.mem_get_info(xs.device)[0] + torch.cuda.memory_reserved(xs.device) \
-                    - torch.cuda.memory_allocated(xs.device)
-                per_call = int(max(1, min(len(items), (0.4 * free_bytes) // per_block)))
-                for c0 in range(0, len(items), per_call):
-                    part = items[c0:c0 + per_call]
-                    i0, nb = part[0][0], len(part)
-                    t_starts = torch.tensor([a for _, a in part], dtype=torch.int64).to(xs.device, non_blocking=True)
-                    calls.append(_JointCall([bt.regions[i] for i, _ in part], x_all, bt.starts[i0:i0 + nb], bt.n, t_starts, ns,
-                                            bt.karena[i0:i0 + nb], bt.ws_arena[i0:i0 + nb], bt.noise[i0:i0 + nb]))
-                done.update(bt.regions[i] for i, _ in items)
-        for l in sorted(owned):
-            if l not in done:
-                a, b = (int(v) for v in test_bounds[l])
-                if b > a:
-                    calls.append(single_joint_call(self.blocks[l], l, xs.device, a, b))
+        test_bounds[l] of ``xs``, served by training block l), through :func:`joint_run`: :meth:`_run_layer` collects
+        ONE cimrgp_layer_joint_cov call per sub-batch and the other blocks as batches of one; they run afterwards, in
+        that order (``joint_run`` reads ``info`` back per call).  Returns the largest relative jitter used."""
+        calls = []
+
+        def per_block(bt, ns):
+            ldc, ldw = dev.joint_ld(ns, xs.dtype), dev.joint_ld(bt.n, xs.dtype)
+            return ns * (ldc + ldw) * xs.element_size() + dev.potrf_workspace_bytes(ns, xs.dtype) + 16
+
+        self._run_layer(owned, test_bounds, xs.device, per_block, lambda: 0.4 * free_device_bytes(xs.device),
+                        lambda bt, t_starts, ns: calls.append(_JointCall(bt, x_all, t_starts, ns)),
+                        lambda l, a, b: calls.append(self.blocks[l].joint_call(l, a, b)), fan_out=False)
         used = 0.0
         for call in calls:
             used = max(used, joint_run(call, self.kernel, xs, layer, add_noise, cov_out, samples, seed, jitter))

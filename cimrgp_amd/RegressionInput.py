@@ -26,7 +26,7 @@ import torch
 from . import device as dev
 from ._lib import COV_RBF
 from .KernelClass import RBFKernel, DenseMaternKernel
-from .Posteriors import DenseBlock, NOISE_FRACTION, joint_run, single_joint_call
+from .Posteriors import DenseBlock, NOISE_FRACTION, joint_run
 
 
 def log_marginal_likelihood(x, y, ell, sf, noise, cov=COV_RBF, want_grad=True):
@@ -229,11 +229,16 @@ class GP_RBF(RegressionMethod):
     def _predict(self, test_data):
         return self._predict_mean_var(test_data, want_var=False)[0]
 
-    def _predict_mean_var(self, test_data, want_var):
-        blk = self.block
-        xs = dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, blk.x.device)
+    def _test_inputs(self, test_data):
+        """The (preprocessed) test inputs on the block's device, in the block's units (ARD: divided by the length-scales)."""
+        xs = dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, self.block.x.device)
         if self.ARD:
             xs = (xs * self._scale).contiguous()
+        return xs
+
+    def _predict_mean_var(self, test_data, want_var):
+        blk = self.block
+        xs = self._test_inputs(test_data)
         q = blk.alpha.shape[1]
         mean = torch.zeros((xs.shape[0], q), dtype=self.dtype, device=xs.device)
         var = torch.zeros(xs.shape[0], dtype=self.dtype, device=xs.device) if want_var else None
@@ -259,9 +264,7 @@ class GP_RBF(RegressionMethod):
         if self.preprocess:
             test_data = self._preprocess(test_data, False)
         blk = self.block
-        xs = dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, blk.x.device)
-        if self.ARD:
-            xs = (xs * self._scale).contiguous()
+        xs = self._test_inputs(test_data)
         ns, d = int(xs.shape[0]), int(xs.shape[1])
         q = blk.alpha.shape[1]
         mean_grad = torch.zeros((ns, d, q), dtype=self.dtype, device=xs.device)
@@ -309,11 +312,8 @@ class GP_RBF(RegressionMethod):
 
     def _joint(self, test_data, cov_out=None, samples=None, seed=0):
         blk = self.block
-        xs = dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, blk.x.device)
-        if self.ARD:
-            xs = (xs * self._scale).contiguous()
-        call = single_joint_call(blk, 0, xs.device, 0, xs.shape[0])
-        joint_run(call, blk.kernel, xs, 0, False, cov_out, samples, seed)
+        xs = self._test_inputs(test_data)
+        joint_run(blk.joint_call(0, 0, xs.shape[0]), blk.kernel, xs, 0, False, cov_out, samples, seed)
         return xs.shape[0]
 
     def predict_with_covariance(self, test_data):
