@@ -176,6 +176,13 @@ hipStream_t solve_queue_for(hipStream_t st);
 hipStream_t front_queue_for(hipStream_t st);
 
 // --------------------------------------------------------- host launchers ----
+// block.hip: the three stages of cimrgp_block_posterior[_staged] on their streams, with the records of staged calls
+// in flight; staged_shutdown_ destroys those records' events (cimrgp_shutdown)
+template <typename T> int block_posterior_typed(const void* x, int64_t n, int d, const void* y, int q, const void* xs, int64_t ns,
+                                                double ell, double sf2, double noise, void* k, int64_t ldk, void* ws, int32_t* info,
+                                                void* w, int64_t ldw, void* alpha, void* z, void* scratch, void* mean, void* var,
+                                                int add_noise, int accumulate, hipStream_t s_front, hipStream_t st, hipStream_t s_solve);
+int staged_shutdown_();
 // potrf.hip
 template <typename T> int potrf_run(T* k, int64_t n, int64_t ld, T* ws, int32_t* info, T* b, int64_t m, int64_t ldb,
                                     hipStream_t st, hipStream_t ready_on = nullptr);

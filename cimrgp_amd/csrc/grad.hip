@@ -9,7 +9,7 @@
 //                  pass over the pairs; the cross-covariance and its derivative are never stored
 //   layer_grad     per block: the batched cross-Gram and forward row solve (as cimrgp_layer_predict), the batched
 //                  backward row solve above, then the batched contraction
-#include "common.hpp"
+#include "abi.hpp"
 
 namespace cimrgp {
 
@@ -374,10 +374,6 @@ static int layer_grad_run(int cov, const T* x, const int64_t* starts, int64_t n,
 
 using namespace cimrgp;
 
-static inline hipStream_t GS(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static inline int64_t gepc(int dtype) { return dtype == CIMRGP_F64 ? 2 : 4; }
-static inline int64_t gesz(int dtype) { return dtype == CIMRGP_F64 ? 8 : 4; }
-
 extern "C" {
 
 int cimrgp_trsm_rows_lt_batched(int dtype, const void* l_dev, int64_t n, int64_t ldl, int64_t l_stride, const void* workspace_dev,
@@ -385,12 +381,12 @@ int cimrgp_trsm_rows_lt_batched(int dtype, const void* l_dev, int64_t n, int64_t
                                 void* stream)
 {
     const char* fn = "cimrgp_trsm_rows_lt";
-    CIMRGP_REQUIRE(dtype == CIMRGP_F32 || dtype == CIMRGP_F64, fn, "unknown dtype");
+    CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(l_dev && workspace_dev && b_dev, fn, "null pointer");
     CIMRGP_REQUIRE(batch >= 1 && batch < 65536, fn, "batch count out of range");
     CIMRGP_REQUIRE(n >= 1 && n < (1ll << 30) && m >= 0 && m < (1ll << 30), fn, "bad dimensions");
     CIMRGP_REQUIRE(ldl >= n && ldb >= n, fn, "leading dimension too small");
-    const int64_t e = gepc(dtype);
+    const int64_t e = elems_per_16_bytes(dtype);
     CIMRGP_REQUIRE(ldl % e == 0 && ldb % e == 0 && l_stride % e == 0 && b_stride % e == 0, fn,
                    "leading dimensions and strides must be multiples of 16 bytes");
     CIMRGP_REQUIRE(aligned16(l_dev) && aligned16(workspace_dev) && aligned16(b_dev), fn, "pointers must be 16-byte aligned");
@@ -400,11 +396,12 @@ int cimrgp_trsm_rows_lt_batched(int dtype, const void* l_dev, int64_t n, int64_t
     PotrfBatch bt;
     bt.count = batch;
     bt.sk = l_stride;
-    bt.sws = (int64_t)(workspace_stride_bytes / (size_t)gesz(dtype));
+    bt.sws = (int64_t)(workspace_stride_bytes / elem_bytes(dtype));
     bt.sb = b_stride;
-    if (dtype == CIMRGP_F64)
-        return rows_lt_run<double>((const double*)l_dev, n, ldl, (const double*)workspace_dev, (double*)b_dev, m, ldb, GS(stream), bt, fn);
-    return rows_lt_run<float>((const float*)l_dev, n, ldl, (const float*)workspace_dev, (float*)b_dev, m, ldb, GS(stream), bt, fn);
+    return with_dtype(dtype, fn, [&](auto tag) {
+        using T = decltype(tag);
+        return rows_lt_run<T>((const T*)l_dev, n, ldl, (const T*)workspace_dev, (T*)b_dev, m, ldb, stream_of(stream), bt, fn);
+    });
 }
 
 int cimrgp_trsm_rows_lt(int dtype, const void* l_dev, int64_t n, int64_t ldl, const void* workspace_dev, void* b_dev, int64_t m,
@@ -418,7 +415,7 @@ int cimrgp_cov_predict_grad(int dtype, int cov, const void* x_dev, int64_t n, in
                             void* var_grad_dev, int accumulate, void* stream)
 {
     const char* fn = "cimrgp_cov_predict_grad";
-    CIMRGP_REQUIRE(dtype == CIMRGP_F32 || dtype == CIMRGP_F64, fn, "unknown dtype");
+    CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
     CIMRGP_REQUIRE(x_dev && xs_dev, fn, "null pointer");
     CIMRGP_REQUIRE(mean_grad_dev == nullptr || alpha_dev != nullptr, fn, "null pointer (alpha)");
@@ -428,12 +425,11 @@ int cimrgp_cov_predict_grad(int dtype, int cov, const void* x_dev, int64_t n, in
     CIMRGP_REQUIRE(q >= 1 && q <= GR_MAXQ, fn, "number of outputs must be in [1, 8]");
     CIMRGP_REQUIRE(ell > 0.0 && sf2 > 0.0, fn, "kernel parameters must be positive");
     CIMRGP_REQUIRE(var_grad_dev == nullptr || ldb >= n, fn, "leading dimension of beta smaller than n");
-    auto run = [&](auto tag) {
+    return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         return predict_grad_run<T>(cov, (const T*)x_dev, nullptr, n, d, (const T*)alpha_dev, 0, q, (const T*)xs_dev, nullptr, ns, 1, ell,
-                                   sf2, (const T*)beta_dev, ldb, 0, (T*)mean_grad_dev, (T*)var_grad_dev, accumulate, GS(stream), fn);
-    };
-    return dtype == CIMRGP_F64 ? run(double()) : run(float());
+                                   sf2, (const T*)beta_dev, ldb, 0, (T*)mean_grad_dev, (T*)var_grad_dev, accumulate, stream_of(stream), fn);
+    });
 }
 
 int cimrgp_layer_predict_grad_cov(int dtype, int cov, const void* x_dev, const int64_t* starts_dev, int64_t n, int d, const void* xs_dev,
@@ -443,7 +439,7 @@ int cimrgp_layer_predict_grad_cov(int dtype, int cov, const void* x_dev, const i
                                   int accumulate, void* stream)
 {
     const char* fn = "cimrgp_layer_predict_grad_cov";
-    CIMRGP_REQUIRE(dtype == CIMRGP_F32 || dtype == CIMRGP_F64, fn, "unknown dtype");
+    CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
     CIMRGP_REQUIRE(x_dev && starts_dev && xs_dev && t_starts_dev && alpha_dev, fn, "null pointer");
     CIMRGP_REQUIRE(var_grad_dev == nullptr || (l_arena_dev && ws_arena_dev && w_arena_dev), fn, "null pointer (factor, workspace or W)");
@@ -454,23 +450,22 @@ int cimrgp_layer_predict_grad_cov(int dtype, int cov, const void* x_dev, const i
     CIMRGP_REQUIRE(ell > 0.0 && sf2 > 0.0, fn, "kernel parameters must be positive");
     if (var_grad_dev != nullptr) {
         CIMRGP_REQUIRE(ldl >= n && ldw >= n, fn, "leading dimension too small");
-        const int64_t e = gepc(dtype);
+        const int64_t e = elems_per_16_bytes(dtype);
         CIMRGP_REQUIRE(ldl % e == 0 && ldw % e == 0 && l_stride % e == 0 && w_stride % e == 0, fn,
                        "leading dimensions and strides must be multiples of 16 bytes");
         CIMRGP_REQUIRE(aligned16(l_arena_dev) && aligned16(ws_arena_dev) && aligned16(w_arena_dev), fn, "pointers must be 16-byte aligned");
         CIMRGP_REQUIRE(ws_stride_bytes >= cimrgp_potrf_workspace_bytes(dtype, n) || batch == 1, fn, "workspace stride too small");
         CIMRGP_REQUIRE(ws_stride_bytes % 16 == 0 || batch == 1, fn, "workspace stride must be a multiple of 16 bytes");
-        CIMRGP_REQUIRE(batch == 1 || ns == 0 || (l_stride >= n * ldl - (ldl - n) && w_stride >= (ns - 1) * ldw + n), fn,
+        CIMRGP_REQUIRE(batch == 1 || ns == 0 || (block_stride_ok(l_stride, n, n, ldl) && w_stride >= (ns - 1) * ldw + n), fn,
                        "block stride too small");
     }
-    auto run = [&](auto tag) {
+    return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         return layer_grad_run<T>(cov, (const T*)x_dev, starts_dev, n, d, (const T*)xs_dev, t_starts_dev, ns, batch, ell, sf2,
                                  (const T*)l_arena_dev, ldl, l_stride, (const T*)ws_arena_dev, (int64_t)(ws_stride_bytes / sizeof(T)),
                                  (const T*)alpha_dev, q, (T*)w_arena_dev, ldw, w_stride, (T*)mean_grad_dev, (T*)var_grad_dev, accumulate,
-                                 GS(stream));
-    };
-    return dtype == CIMRGP_F64 ? run(double()) : run(float());
+                                 stream_of(stream));
+    });
 }
 
 }  // extern "C"

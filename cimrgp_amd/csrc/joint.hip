@@ -6,7 +6,7 @@
 //   layer_sample  out^T += Z^T L^T per block: k_layer_sample, gemm_tile's body with a positive sign, B read as lower
 //                 triangular and K cut at the last row of each column tile (tiles above the diagonal are never
 //                 computed: ns^2 cols flops instead of 2 ns^2 cols)
-#include "common.hpp"
+#include "abi.hpp"
 #include "gemm_tile.hpp"
 
 namespace cimrgp {
@@ -179,17 +179,13 @@ static int layer_sample_run(const T* l, int64_t ldl, int64_t sl, int64_t ns, int
 
 using namespace cimrgp;
 
-static inline hipStream_t JS(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static inline int64_t jepc(int dtype) { return dtype == CIMRGP_F64 ? 2 : 4; }
-static inline int64_t esz_of(int dtype) { return dtype == CIMRGP_F64 ? 8 : 4; }
-
 extern "C" {
 
 int cimrgp_normal_fill(int dtype, uint64_t seed, const uint64_t* keys_dev, int batch, int64_t col0, int64_t cols, int64_t ns,
                        void* z_dev, int64_t ldz, int64_t z_stride, void* stream)
 {
     const char* fn = "cimrgp_normal_fill";
-    CIMRGP_REQUIRE(dtype == CIMRGP_F32 || dtype == CIMRGP_F64, fn, "unknown dtype");
+    CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(keys_dev && z_dev, fn, "null pointer");
     CIMRGP_REQUIRE(batch >= 1 && batch < 65536, fn, "batch count out of range");
     CIMRGP_REQUIRE(cols >= 0 && ns >= 0 && col0 >= 0, fn, "negative size");
@@ -198,8 +194,10 @@ int cimrgp_normal_fill(int dtype, uint64_t seed, const uint64_t* keys_dev, int b
     CIMRGP_REQUIRE(ldz >= ns && ldz >= 1, fn, "leading dimension of z smaller than ns");
     CIMRGP_REQUIRE(batch == 1 || cols == 0 || z_stride >= (cols - 1) * ldz + ns, fn, "block stride too small");
     CIMRGP_REQUIRE(cols * (int64_t)batch < (1ll << 40), fn, "too many columns");
-    if (dtype == CIMRGP_F64) return normal_fill_run<double>(seed, keys_dev, batch, col0, cols, ns, (double*)z_dev, ldz, z_stride, JS(stream));
-    return normal_fill_run<float>(seed, keys_dev, batch, col0, cols, ns, (float*)z_dev, ldz, z_stride, JS(stream));
+    return with_dtype(dtype, fn, [&](auto tag) {
+        using T = decltype(tag);
+        return normal_fill_run<T>(seed, keys_dev, batch, col0, cols, ns, (T*)z_dev, ldz, z_stride, stream_of(stream));
+    });
 }
 
 int cimrgp_layer_joint_cov(int dtype, int cov, const void* x_dev, const int64_t* starts_dev, int64_t n, int d, const void* xs_dev,
@@ -209,7 +207,7 @@ int cimrgp_layer_joint_cov(int dtype, int cov, const void* x_dev, const int64_t*
                            void* cws_arena_dev, size_t cws_stride_bytes, int32_t* info_dev, void* stream)
 {
     const char* fn = "cimrgp_layer_joint_cov";
-    CIMRGP_REQUIRE(dtype == CIMRGP_F32 || dtype == CIMRGP_F64, fn, "unknown dtype");
+    CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
     CIMRGP_REQUIRE(x_dev && starts_dev && xs_dev && t_starts_dev && l_arena_dev && ws_arena_dev && w_arena_dev && c_arena_dev, fn,
                    "null pointer");
@@ -219,26 +217,25 @@ int cimrgp_layer_joint_cov(int dtype, int cov, const void* x_dev, const int64_t*
     CIMRGP_REQUIRE(d >= 1 && d <= 8, fn, "input dimension must be in [1, 8]");
     CIMRGP_REQUIRE(ell > 0.0 && sf2 > 0.0, fn, "kernel parameters must be positive");
     CIMRGP_REQUIRE(ldl >= n && ldw >= n && ldc >= ns && ldc >= 1, fn, "leading dimension too small");
-    const int64_t e = jepc(dtype);
+    const int64_t e = elems_per_16_bytes(dtype);
     CIMRGP_REQUIRE(ldl % e == 0 && ldw % e == 0 && ldc % e == 0 && l_stride % e == 0 && w_stride % e == 0 && c_stride % e == 0, fn,
                    "leading dimensions and strides must be multiples of 16 bytes");
-    CIMRGP_REQUIRE(ldw * (int64_t)esz_of(dtype) >= 128, fn, "leading dimension of W must span at least 128 bytes");
-    CIMRGP_REQUIRE(batch == 1 || (l_stride >= n * ldl - (ldl - n) && w_stride >= ns * ldw - (ldw - n) &&
-                                  c_stride >= ns * ldc - (ldc - ns)), fn, "block stride too small");
+    CIMRGP_REQUIRE(ldw * (int64_t)elem_bytes(dtype) >= 128, fn, "leading dimension of W must span at least 128 bytes");
+    CIMRGP_REQUIRE(batch == 1 || (block_stride_ok(l_stride, n, n, ldl) && block_stride_ok(w_stride, ns, n, ldw) &&
+                                  block_stride_ok(c_stride, ns, ns, ldc)), fn, "block stride too small");
     CIMRGP_REQUIRE(aligned16(l_arena_dev) && aligned16(ws_arena_dev) && aligned16(w_arena_dev) && aligned16(c_arena_dev) &&
                    aligned16(cws_arena_dev), fn, "pointers must be 16-byte aligned");
     CIMRGP_REQUIRE(ws_stride_bytes >= cimrgp_potrf_workspace_bytes(dtype, n), fn, "workspace stride too small");
     CIMRGP_REQUIRE(cws_arena_dev == nullptr ||
-                   (cws_stride_bytes >= cimrgp_potrf_workspace_bytes(dtype, ns) && cws_stride_bytes % 16 == 0), fn,
+                   workspace_stride_ok(dtype, ns, cws_stride_bytes), fn,
                    "factor workspace stride too small or misaligned");
-    auto run = [&](auto tag) {
+    return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         return joint_cov_run<T>(cov, (const T*)x_dev, starts_dev, n, d, (const T*)xs_dev, t_starts_dev, ns, batch, ell, sf2,
                                 (const T*)l_arena_dev, ldl, l_stride, (const T*)ws_arena_dev, (int64_t)(ws_stride_bytes / sizeof(T)),
                                 (const T*)diag_dev, (T*)w_arena_dev, ldw, w_stride, (T*)c_arena_dev, ldc, c_stride,
-                                (T*)cws_arena_dev, (int64_t)(cws_stride_bytes / sizeof(T)), info_dev, JS(stream));
-    };
-    return dtype == CIMRGP_F64 ? run(double()) : run(float());
+                                (T*)cws_arena_dev, (int64_t)(cws_stride_bytes / sizeof(T)), info_dev, stream_of(stream));
+    });
 }
 
 int cimrgp_layer_sample(int dtype, const void* l_arena_dev, int64_t ldl, int64_t l_stride, int64_t ns, int batch, const void* z_dev,
@@ -246,22 +243,22 @@ int cimrgp_layer_sample(int dtype, const void* l_arena_dev, int64_t ldl, int64_t
                         void* stream)
 {
     const char* fn = "cimrgp_layer_sample";
-    CIMRGP_REQUIRE(dtype == CIMRGP_F32 || dtype == CIMRGP_F64, fn, "unknown dtype");
+    CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(l_arena_dev && z_dev && t_starts_dev && out_dev, fn, "null pointer");
     CIMRGP_REQUIRE(batch >= 1 && batch < 65536, fn, "batch count out of range");
     CIMRGP_REQUIRE(cols >= 0 && ns >= 0 && cols < (1ll << 30) && ns < (1ll << 30), fn, "bad dimensions");
     CIMRGP_REQUIRE(ldl >= ns && ldz >= ns && ld_out >= 1 && ldl < (1ll << 23) && ldz < (1ll << 23), fn, "bad leading dimension");
-    const int64_t e = jepc(dtype);
+    const int64_t e = elems_per_16_bytes(dtype);
     CIMRGP_REQUIRE(ldl % e == 0 && ldz % e == 0 && l_stride % e == 0 && z_stride % e == 0, fn,
                    "leading dimensions and strides must be multiples of 16 bytes");
-    CIMRGP_REQUIRE(ldl * (int64_t)esz_of(dtype) >= 128 && ldz * (int64_t)esz_of(dtype) >= 128, fn,
+    CIMRGP_REQUIRE(ldl * (int64_t)elem_bytes(dtype) >= 128 && ldz * (int64_t)elem_bytes(dtype) >= 128, fn,
                    "leading dimensions must span at least 128 bytes (a K stage of the tile loads 128 bytes per row)");
     CIMRGP_REQUIRE(aligned16(l_arena_dev) && aligned16(z_dev), fn, "pointers must be 16-byte aligned");
-    if (dtype == CIMRGP_F64)
-        return layer_sample_run<double>((const double*)l_arena_dev, ldl, l_stride, ns, batch, (const double*)z_dev, ldz, z_stride, cols,
-                                        t_starts_dev, (double*)out_dev, ld_out, JS(stream));
-    return layer_sample_run<float>((const float*)l_arena_dev, ldl, l_stride, ns, batch, (const float*)z_dev, ldz, z_stride, cols,
-                                   t_starts_dev, (float*)out_dev, ld_out, JS(stream));
+    return with_dtype(dtype, fn, [&](auto tag) {
+        using T = decltype(tag);
+        return layer_sample_run<T>((const T*)l_arena_dev, ldl, l_stride, ns, batch, (const T*)z_dev, ldz, z_stride, cols, t_starts_dev,
+                                   (T*)out_dev, ld_out, stream_of(stream));
+    });
 }
 
 }  // extern "C"

@@ -13,7 +13,7 @@
 //   loo          k_loo_tail: y - alpha / d, 1 / d
 // A row's values depend on its global index alone (tiles and strips are aligned to global row numbers, every K loop
 // has a fixed order): the result is bit-identical whatever the strip height.
-#include "common.hpp"
+#include "abi.hpp"
 #include "gemm_tile.hpp"
 
 namespace cimrgp {
@@ -260,68 +260,64 @@ static int kinv_diag_run(const T* l, int64_t n, int64_t ldl, const T* ws, T* scr
 
 using namespace cimrgp;
 
-static inline hipStream_t LS(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static inline int64_t lepc(int dtype) { return dtype == CIMRGP_F64 ? 2 : 4; }
-static inline int64_t lesz(int dtype) { return dtype == CIMRGP_F64 ? 8 : 4; }
-
 extern "C" {
 
 int cimrgp_trtri_rows(int dtype, const void* l_dev, int64_t n, int64_t ldl, const void* workspace_dev, int64_t r0, int64_t m,
                       void* u_dev, int64_t ldu, void* stream)
 {
     const char* fn = "cimrgp_trtri_rows";
-    CIMRGP_REQUIRE(dtype == CIMRGP_F32 || dtype == CIMRGP_F64, fn, "unknown dtype");
+    CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(l_dev && workspace_dev && u_dev, fn, "null pointer");
     CIMRGP_REQUIRE(n >= 1 && n < (1ll << 30) && m >= 0, fn, "bad dimensions");
     CIMRGP_REQUIRE(r0 >= 0 && r0 % CIMRGP_NB == 0, fn, "r0 must be a multiple of 256");
     CIMRGP_REQUIRE(r0 <= n && m <= n - r0, fn, "rows [r0, r0 + m) must lie in [0, n)");
     CIMRGP_REQUIRE(ldl >= n && ldu >= n, fn, "leading dimension too small");
-    const int64_t e = lepc(dtype);
+    const int64_t e = elems_per_16_bytes(dtype);
     CIMRGP_REQUIRE(ldl % e == 0 && ldu % e == 0, fn, "leading dimensions must be multiples of 16 bytes");
     CIMRGP_REQUIRE(aligned16(l_dev) && aligned16(workspace_dev) && aligned16(u_dev), fn, "pointers must be 16-byte aligned");
-    PotrfBatch bt;
-    if (dtype == CIMRGP_F64)
-        return trtri_rows_run<double>((const double*)l_dev, n, ldl, (const double*)workspace_dev, r0, m, (double*)u_dev, ldu, LS(stream),
-                                      bt, fn);
-    return trtri_rows_run<float>((const float*)l_dev, n, ldl, (const float*)workspace_dev, r0, m, (float*)u_dev, ldu, LS(stream), bt, fn);
+    return with_dtype(dtype, fn, [&](auto tag) {
+        using T = decltype(tag);
+        return trtri_rows_run<T>((const T*)l_dev, n, ldl, (const T*)workspace_dev, r0, m, (T*)u_dev, ldu, stream_of(stream), PotrfBatch(),
+                                 fn);
+    });
 }
 
 size_t cimrgp_kinv_diag_scratch_bytes(int dtype, int64_t n, int64_t strip_rows)
 {
-    if ((dtype != CIMRGP_F32 && dtype != CIMRGP_F64) || n < 1 || n >= (1ll << 30)) return 0;
+    if (!dtype_known(dtype) || n < 1 || n >= (1ll << 30)) return 0;
     const int64_t top = loo_round256(n);
     int64_t strip = strip_rows < CIMRGP_NB ? CIMRGP_NB : (strip_rows > top ? top : loo_round256(strip_rows));
-    return (size_t)(strip * loo_ldu(n) * lesz(dtype));
+    return (size_t)(strip * loo_ldu(n)) * elem_bytes(dtype);
 }
 
 static int kinv_diag_entry(const char* fn, int dtype, const void* l_dev, int64_t n, int64_t ldl, int64_t l_stride,
                            const void* workspace_dev, size_t workspace_stride_bytes, void* scratch_dev, size_t scratch_bytes,
                            void* diag_out_dev, int batch, void* stream)
 {
-    CIMRGP_REQUIRE(dtype == CIMRGP_F32 || dtype == CIMRGP_F64, fn, "unknown dtype");
+    CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(l_dev && workspace_dev && scratch_dev && diag_out_dev, fn, "null pointer");
     CIMRGP_REQUIRE(batch >= 1 && batch < 65536, fn, "batch count out of range");
     CIMRGP_REQUIRE(n >= 1 && n < (1ll << 30), fn, "bad dimensions");
     CIMRGP_REQUIRE(ldl >= n, fn, "leading dimension too small");
-    const int64_t e = lepc(dtype);
+    const int64_t e = elems_per_16_bytes(dtype);
     CIMRGP_REQUIRE(ldl % e == 0 && l_stride % e == 0, fn, "leading dimensions and strides must be multiples of 16 bytes");
     CIMRGP_REQUIRE(aligned16(l_dev) && aligned16(workspace_dev) && aligned16(scratch_dev), fn, "pointers must be 16-byte aligned");
     CIMRGP_REQUIRE(workspace_stride_bytes >= cimrgp_potrf_workspace_bytes(dtype, n) || batch == 1, fn, "workspace stride too small");
     CIMRGP_REQUIRE(workspace_stride_bytes % 16 == 0 || batch == 1, fn, "workspace stride must be a multiple of 16 bytes");
-    CIMRGP_REQUIRE(batch == 1 || l_stride >= n * ldl - (ldl - n), fn, "block stride too small");
-    const size_t row_bytes = (size_t)(loo_ldu(n) * lesz(dtype));
+    CIMRGP_REQUIRE(batch == 1 || block_stride_ok(l_stride, n, n, ldl), fn, "block stride too small");
+    const size_t row_bytes = (size_t)loo_ldu(n) * elem_bytes(dtype);
     CIMRGP_REQUIRE(scratch_bytes / (size_t)batch >= (size_t)CIMRGP_NB * row_bytes, fn, "scratch too small");
     int64_t strip = (int64_t)(scratch_bytes / (size_t)batch / row_bytes) / CIMRGP_NB * CIMRGP_NB;
     strip = std::min<int64_t>(strip, loo_round256(n));
     PotrfBatch bt;
     bt.count = batch;
     bt.sk = l_stride;
-    bt.sws = (int64_t)(workspace_stride_bytes / (size_t)lesz(dtype));
-    if (dtype == CIMRGP_F64)
-        return kinv_diag_run<double>((const double*)l_dev, n, ldl, (const double*)workspace_dev, (double*)scratch_dev, strip,
-                                     (double*)diag_out_dev, LS(stream), bt, fn);
-    return kinv_diag_run<float>((const float*)l_dev, n, ldl, (const float*)workspace_dev, (float*)scratch_dev, strip, (float*)diag_out_dev,
-                                LS(stream), bt, fn);
+    bt.sws = (int64_t)(workspace_stride_bytes / elem_bytes(dtype));
+    return with_dtype(dtype, fn, [&](auto tag) {
+        using T = decltype(tag);
+        return kinv_diag_run<T>((const T*)l_dev, n, ldl, (const T*)workspace_dev, (T*)scratch_dev, strip, (T*)diag_out_dev,
+                                stream_of(stream), bt, fn);
+    });
 }
 
 int cimrgp_kinv_diag_batched(int dtype, const void* l_dev, int64_t n, int64_t ldl, int64_t l_stride, const void* workspace_dev,
@@ -342,7 +338,7 @@ int cimrgp_kinv_diag(int dtype, const void* l_dev, int64_t n, int64_t ldl, const
 static int loo_entry(const char* fn, int dtype, const void* y_dev, const int64_t* starts_dev, const void* alpha_dev, const void* diag_dev,
                      int64_t n, int q, int batch, void* mean_out_dev, void* var_out_dev, void* stream)
 {
-    CIMRGP_REQUIRE(dtype == CIMRGP_F32 || dtype == CIMRGP_F64, fn, "unknown dtype");
+    CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(diag_dev, fn, "null pointer");
     CIMRGP_REQUIRE(mean_out_dev == nullptr || (y_dev && alpha_dev), fn, "null pointer (y or alpha)");
     CIMRGP_REQUIRE(batch >= 1 && batch < 65536, fn, "batch count out of range");
@@ -350,14 +346,13 @@ static int loo_entry(const char* fn, int dtype, const void* y_dev, const int64_t
     CIMRGP_REQUIRE(q >= 1 && q <= LOO_MAXQ, fn, "number of outputs must be in [1, 8]");
     if (n == 0 || (mean_out_dev == nullptr && var_out_dev == nullptr)) return 0;
     const dim3 grid((unsigned)((n + 255) / 256), (unsigned)batch);
-    if (dtype == CIMRGP_F64)
-        hipLaunchKernelGGL((k_loo_tail<double>), grid, dim3(256), 0, LS(stream), (const double*)y_dev, starts_dev, (const double*)alpha_dev,
-                           (const double*)diag_dev, (int)n, q, (double*)mean_out_dev, (double*)var_out_dev);
-    else
-        hipLaunchKernelGGL((k_loo_tail<float>), grid, dim3(256), 0, LS(stream), (const float*)y_dev, starts_dev, (const float*)alpha_dev,
-                           (const float*)diag_dev, (int)n, q, (float*)mean_out_dev, (float*)var_out_dev);
-    CIMRGP_LAUNCH_CHECK(fn);
-    return 0;
+    return with_dtype(dtype, fn, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((k_loo_tail<T>), grid, dim3(256), 0, stream_of(stream), (const T*)y_dev, starts_dev, (const T*)alpha_dev,
+                           (const T*)diag_dev, (int)n, q, (T*)mean_out_dev, (T*)var_out_dev);
+        CIMRGP_LAUNCH_CHECK(fn);
+        return 0;
+    });
 }
 
 int cimrgp_loo_batched(int dtype, const void* y_dev, const int64_t* starts_dev, const void* alpha_dev, const void* diag_dev, int64_t n,

@@ -77,19 +77,15 @@ def _cov_id(cov):
 
 def rbf_gram(x, ell, sf2, diag_add=0.0, lower_only=False, out=None, cov=_lib.COV_RBF):
     """D1.  x: (n x d) device tensor.  Returns the (n x ld) buffer; [:, :n] is K.
-    ``cov``: covariance id (``_lib.COV_*``, a kernel object's ``.cov``); the RBF goes through the
-    original entry point (cimrgp_rbf_gram), the Matern ones through cimrgp_cov_gram."""
+    ``cov``: covariance id (``_lib.COV_*``, a kernel object's ``.cov``); every covariance, the RBF included, goes
+    through cimrgp_cov_gram (bit-identical to cimrgp_rbf_gram for the RBF)."""
     cov = _cov_id(cov)             # an unknown id is refused before any allocation
     n, d = x.shape
     if out is None:
         out = alloc_matrix(n, n, x.dtype, x.device)
     lib = _lib.load()
-    if cov != _lib.COV_RBF:
-        _lib.check(lib.cimrgp_cov_gram(_DT[x.dtype], cov, _p(x), n, d, float(ell), float(sf2), float(diag_add),
-                                       _p(out), out.stride(0), int(bool(lower_only)), _stream()), "cimrgp_cov_gram")
-        return out
-    _lib.check(lib.cimrgp_rbf_gram(_DT[x.dtype], _p(x), n, d, float(ell), float(sf2), float(diag_add),
-                                   _p(out), out.stride(0), int(bool(lower_only)), _stream()), "cimrgp_rbf_gram")
+    _lib.check(lib.cimrgp_cov_gram(_DT[x.dtype], cov, _p(x), n, d, float(ell), float(sf2), float(diag_add),
+                                   _p(out), out.stride(0), int(bool(lower_only)), _stream()), "cimrgp_cov_gram")
     return out
 
 
@@ -101,12 +97,8 @@ def rbf_cross(xa, xb, ell, sf2, out=None, cov=_lib.COV_RBF):
     if out is None:
         out = alloc_matrix(na, nb, xa.dtype, xa.device)
     lib = _lib.load()
-    if cov != _lib.COV_RBF:
-        _lib.check(lib.cimrgp_cov_cross(_DT[xa.dtype], cov, _p(xa), na, _p(xb), nb, d, float(ell), float(sf2),
-                                        _p(out), out.stride(0), _stream()), "cimrgp_cov_cross")
-        return out
-    _lib.check(lib.cimrgp_rbf_cross(_DT[xa.dtype], _p(xa), na, _p(xb), nb, d, float(ell), float(sf2),
-                                    _p(out), out.stride(0), _stream()), "cimrgp_rbf_cross")
+    _lib.check(lib.cimrgp_cov_cross(_DT[xa.dtype], cov, _p(xa), na, _p(xb), nb, d, float(ell), float(sf2),
+                                    _p(out), out.stride(0), _stream()), "cimrgp_cov_cross")
     return out
 
 
@@ -176,30 +168,29 @@ def block_posterior(x, y, xs, ell, sf2, noise, kbuf, wbuf, ws, info, alpha, z, m
     return mean, var
 
 
+def _context_queue(entry, stream):
+    """``entry`` (cimrgp_solve_queue / cimrgp_front_queue) for ``stream`` (default: the current stream), wrapped as a torch
+    stream; ``stream`` itself when it owns no context."""
+    cur = torch.cuda.current_stream() if stream is None else stream
+    out = ctypes.c_void_p()
+    _lib.check(getattr(_lib.load(), entry)(cur.cuda_stream, ctypes.byref(out)), entry)
+    if (out.value or 0) == (cur.cuda_stream or 0):
+        return cur
+    return torch.cuda.ExternalStream(out.value, device=cur.device)
+
+
 def solve_queue(stream=None):
     """The stream to pass as ``streams[2]`` of :func:`block_posterior` (cimrgp_solve_queue, include/cimrgp.h): the
     look-ahead context's queue that is idle between two factorisations on ``stream`` (default: the current stream),
     wrapped as a torch stream; ``stream`` itself when it owns no context."""
-    lib = _lib.load()
-    cur = torch.cuda.current_stream() if stream is None else stream
-    out = ctypes.c_void_p()
-    _lib.check(lib.cimrgp_solve_queue(cur.cuda_stream, ctypes.byref(out)), "cimrgp_solve_queue")
-    if (out.value or 0) == (cur.cuda_stream or 0):
-        return cur
-    return torch.cuda.ExternalStream(out.value, device=cur.device)
+    return _context_queue("cimrgp_solve_queue", stream)
 
 
 def front_queue(stream=None):
     """The stream to pass as ``streams[0]`` of :func:`block_posterior` when consecutive calls are independent blocks
     (cimrgp_front_queue, include/cimrgp.h): the look-ahead context's queue that falls idle before a factorisation on
     ``stream`` ends, wrapped as a torch stream; ``stream`` itself when it owns no context."""
-    lib = _lib.load()
-    cur = torch.cuda.current_stream() if stream is None else stream
-    out = ctypes.c_void_p()
-    _lib.check(lib.cimrgp_front_queue(cur.cuda_stream, ctypes.byref(out)), "cimrgp_front_queue")
-    if (out.value or 0) == (cur.cuda_stream or 0):
-        return cur
-    return torch.cuda.ExternalStream(out.value, device=cur.device)
+    return _context_queue("cimrgp_front_queue", stream)
 
 
 def potrf_rows_batched(karena, n, ld, ws_arena, info, barena=None, m=0, ldb=0):
@@ -246,8 +237,7 @@ def _layer_work_areas(batch, q, n, ldr, dtype, device):
 
 def layer_fit(x, y, fbar, train_out, starts, n, ell, sf2, noise_fixed, noise_frac, noise_floor, shared_bias, shared_noise,
               karena, ws_arena, info, bias, noise, z, alpha, cov=_lib.COV_RBF):
-    """The fit of ``batch`` equal-sized blocks of one layer in ONE call (cimrgp_layer_fit, include/cimrgp.h;
-    cimrgp_layer_fit_cov for a Matern ``cov``).
+    """The fit of ``batch`` equal-sized blocks of one layer in ONE call (cimrgp_layer_fit_cov, include/cimrgp.h).
     x, y, fbar, train_out: the LAYER's arrays (N x d / N x q); starts: device int64 (batch,) row offsets.
     karena (batch, n, ld), ws_arena (batch, ws_bytes) uint8, info (batch,) int32, bias (batch, q), noise (batch,),
     z / alpha (batch, n, q) are filled.  noise_fixed < 0: from the statistics (or ``shared_noise``)."""
@@ -258,40 +248,27 @@ def layer_fit(x, y, fbar, train_out, starts, n, ell, sf2, noise_fixed, noise_fra
     d = int(x.shape[1])
     ldr = padded_ld(n)
     rows, scratch = _layer_work_areas(batch, q, int(n), ldr, y.dtype, y.device)
-    if cov != _lib.COV_RBF:
-        _lib.check(lib.cimrgp_layer_fit_cov(_DT[y.dtype], cov, _p(x), _p(y), _p(fbar), _p(train_out), _p(starts), batch, int(n), d,
-                                            q, float(ell), float(sf2), float(noise_fixed), float(noise_frac), float(noise_floor),
-                                            _p(shared_bias), _p(shared_noise), _p(karena), karena.stride(1), karena.stride(0),
-                                            _p(ws_arena), ws_arena.stride(0), _p(info), _p(rows), ldr, _p(z), _p(alpha), _p(bias),
-                                            _p(noise), _p(scratch), _stream()), "cimrgp_layer_fit_cov")
-        return
-    _lib.check(lib.cimrgp_layer_fit(_DT[y.dtype], _p(x), _p(y), _p(fbar), _p(train_out), _p(starts), batch, int(n), d, q,
-                                    float(ell), float(sf2), float(noise_fixed), float(noise_frac), float(noise_floor),
-                                    _p(shared_bias), _p(shared_noise), _p(karena), karena.stride(1), karena.stride(0),
-                                    _p(ws_arena), ws_arena.stride(0), _p(info), _p(rows), ldr, _p(z), _p(alpha), _p(bias),
-                                    _p(noise), _p(scratch), _stream()), "cimrgp_layer_fit")
+    _lib.check(lib.cimrgp_layer_fit_cov(_DT[y.dtype], cov, _p(x), _p(y), _p(fbar), _p(train_out), _p(starts), batch, int(n), d,
+                                        q, float(ell), float(sf2), float(noise_fixed), float(noise_frac), float(noise_floor),
+                                        _p(shared_bias), _p(shared_noise), _p(karena), karena.stride(1), karena.stride(0),
+                                        _p(ws_arena), ws_arena.stride(0), _p(info), _p(rows), ldr, _p(z), _p(alpha), _p(bias),
+                                        _p(noise), _p(scratch), _stream()), "cimrgp_layer_fit_cov")
 
 
 def layer_predict(x, starts, n, xs, t_starts, ns, ell, sf2, larena, ws_arena, z, bias, noise, mean, var, cov=_lib.COV_RBF):
     """Predictive mean and variance of ``batch`` equal-sized blocks at ``ns`` test points each in ONE call
-    (cimrgp_layer_predict): accumulates into mean (N* x q) / var (N*,) at rows t_starts[b] ...; ``noise``
+    (cimrgp_layer_predict_cov): accumulates into mean (N* x q) / var (N*,) at rows t_starts[b] ...; ``noise``
     (batch,) or None is added to the variance."""
     cov = _cov_id(cov)             # an unknown id is refused before any allocation
     lib = _lib.load()
     batch = int(larena.shape[0])
     ldw = padded_ld(n)
     w = torch.empty((batch, max(int(ns), 1), ldw), dtype=x.dtype, device=x.device)
-    if cov != _lib.COV_RBF:
-        _lib.check(lib.cimrgp_layer_predict_cov(_DT[x.dtype], cov, _p(x), _p(starts), int(n), int(x.shape[1]), _p(xs), _p(t_starts),
-                                                int(ns), batch, float(ell), float(sf2), _p(larena), larena.stride(1),
-                                                larena.stride(0), _p(ws_arena), ws_arena.stride(0), _p(z), int(z.shape[2]), _p(bias),
-                                                _p(noise), _p(w), ldw, w.stride(0), _p(mean), _p(var), _stream()),
-                   "cimrgp_layer_predict_cov")
-        return
-    _lib.check(lib.cimrgp_layer_predict(_DT[x.dtype], _p(x), _p(starts), int(n), int(x.shape[1]), _p(xs), _p(t_starts), int(ns),
-                                        batch, float(ell), float(sf2), _p(larena), larena.stride(1), larena.stride(0),
-                                        _p(ws_arena), ws_arena.stride(0), _p(z), int(z.shape[2]), _p(bias), _p(noise),
-                                        _p(w), ldw, w.stride(0), _p(mean), _p(var), _stream()), "cimrgp_layer_predict")
+    _lib.check(lib.cimrgp_layer_predict_cov(_DT[x.dtype], cov, _p(x), _p(starts), int(n), int(x.shape[1]), _p(xs), _p(t_starts),
+                                            int(ns), batch, float(ell), float(sf2), _p(larena), larena.stride(1),
+                                            larena.stride(0), _p(ws_arena), ws_arena.stride(0), _p(z), int(z.shape[2]), _p(bias),
+                                            _p(noise), _p(w), ldw, w.stride(0), _p(mean), _p(var), _stream()),
+               "cimrgp_layer_predict_cov")
 
 
 def joint_ld(cols, dtype):
@@ -535,14 +512,9 @@ def predict_mean(x, alpha, xs, ell, sf2, bias=None, out=None, accumulate=False, 
     if out is None:
         out = torch.empty((ns, q), dtype=x.dtype, device=x.device)
         accumulate = False
-    if cov != _lib.COV_RBF:
-        _lib.check(lib.cimrgp_cov_predict_mean(_DT[x.dtype], cov, _p(x), n, d, _p(alpha), q, _p(xs), ns, float(ell),
-                                               float(sf2), _p(bias), _p(out), int(bool(accumulate)), _stream()),
-                   "cimrgp_cov_predict_mean")
-        return out
-    _lib.check(lib.cimrgp_predict_mean(_DT[x.dtype], _p(x), n, d, _p(alpha), q, _p(xs), ns, float(ell),
-                                       float(sf2), _p(bias), _p(out), int(bool(accumulate)), _stream()),
-               "cimrgp_predict_mean")
+    _lib.check(lib.cimrgp_cov_predict_mean(_DT[x.dtype], cov, _p(x), n, d, _p(alpha), q, _p(xs), ns, float(ell),
+                                           float(sf2), _p(bias), _p(out), int(bool(accumulate)), _stream()),
+               "cimrgp_cov_predict_mean")
     return out
 
 
@@ -621,14 +593,9 @@ def lml_grad(x, kinv, n, alpha, ell, sf2, noise, cov=_lib.COV_RBF):
     lib = _lib.load()
     out = torch.empty(3, dtype=torch.float64, device=x.device)
     scratch = torch.empty(max(lib.cimrgp_lml_grad_scratch_bytes(int(n)), 8) // 8, dtype=torch.float64, device=x.device)
-    if cov != _lib.COV_RBF:
-        _lib.check(lib.cimrgp_cov_lml_grad(_DT[x.dtype], cov, _p(x), int(n), x.shape[1], _p(kinv), kinv.stride(0), _p(alpha),
-                                           alpha.shape[1], float(ell), float(sf2), float(noise), _p(out), _p(scratch), _stream()),
-                   "cimrgp_cov_lml_grad")
-        return out
-    _lib.check(lib.cimrgp_lml_grad(_DT[x.dtype], _p(x), int(n), x.shape[1], _p(kinv), kinv.stride(0), _p(alpha),
-                                   alpha.shape[1], float(ell), float(sf2), float(noise), _p(out), _p(scratch), _stream()),
-               "cimrgp_lml_grad")
+    _lib.check(lib.cimrgp_cov_lml_grad(_DT[x.dtype], cov, _p(x), int(n), x.shape[1], _p(kinv), kinv.stride(0), _p(alpha),
+                                       alpha.shape[1], float(ell), float(sf2), float(noise), _p(out), _p(scratch), _stream()),
+               "cimrgp_cov_lml_grad")
     return out
 
 
@@ -639,14 +606,9 @@ def lml_grad_ard(x_scaled, kinv, n, alpha, sf2, noise, cov=_lib.COV_RBF):
     d = x_scaled.shape[1]
     out = torch.empty(d + 2, dtype=torch.float64, device=x_scaled.device)
     scratch = torch.empty(max(lib.cimrgp_lml_grad_scratch_bytes(int(n)), 8) // 8, dtype=torch.float64, device=x_scaled.device)
-    if cov != _lib.COV_RBF:
-        _lib.check(lib.cimrgp_cov_lml_grad_ard(_DT[x_scaled.dtype], cov, _p(x_scaled), int(n), d, _p(kinv), kinv.stride(0),
-                                               _p(alpha), alpha.shape[1], float(sf2), float(noise), _p(out), _p(scratch),
-                                               _stream()), "cimrgp_cov_lml_grad_ard")
-        return out
-    _lib.check(lib.cimrgp_lml_grad_ard(_DT[x_scaled.dtype], _p(x_scaled), int(n), d, _p(kinv), kinv.stride(0), _p(alpha),
-                                       alpha.shape[1], float(sf2), float(noise), _p(out), _p(scratch), _stream()),
-               "cimrgp_lml_grad_ard")
+    _lib.check(lib.cimrgp_cov_lml_grad_ard(_DT[x_scaled.dtype], cov, _p(x_scaled), int(n), d, _p(kinv), kinv.stride(0),
+                                           _p(alpha), alpha.shape[1], float(sf2), float(noise), _p(out), _p(scratch),
+                                           _stream()), "cimrgp_cov_lml_grad_ard")
     return out
 
 
@@ -655,15 +617,20 @@ def _f64dev(a, device):
     return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(device)
 
 
+def _interval_dev(interval, d, device):
+    iv = _f64dev(np.asarray(interval, dtype=np.float64).reshape(-1), device)
+    if iv.numel() != d:
+        raise ValueError('Basis interval should have the same dimensionality as the input.')
+    return iv
+
+
 def laplace_basis(x, interval, n_basis, out=None):
     """Phi (n x m) of the Dirichlet-Laplacian eigenfunctions on [-L, L]^d for device points x."""
     n, d = x.shape
     if out is None:
         out = torch.empty((n, int(n_basis)), dtype=x.dtype, device=x.device)
     lib = _lib.load()
-    iv = _f64dev(np.asarray(interval, dtype=np.float64).reshape(-1), x.device)
-    if iv.numel() != d:
-        raise ValueError('Basis interval should have the same dimensionality as the input.')
+    iv = _interval_dev(interval, d, x.device)
     if not x.is_contiguous():
         raise ValueError("laplace_basis needs contiguous inputs")
     _lib.check(lib.cimrgp_laplace_basis(_DT[x.dtype], _p(x), n, d, _p(iv), int(n_basis), _p(out), _stream()),
@@ -683,13 +650,6 @@ class BlockMoments(object):
         self.resid_sq = float(rec[m * q + 2 * m + q])
         self.fvar_sum = float(rec[m * q + 2 * m + q + 1])
         self.n = int(n)
-
-
-def _interval_dev(interval, d, device):
-    iv = _f64dev(np.asarray(interval, dtype=np.float64).reshape(-1), device)
-    if iv.numel() != d:
-        raise ValueError('Basis interval should have the same dimensionality as the input.')
-    return iv
 
 
 def basis_moments(x, interval, n_basis, y, fbar, fvar, eau):

@@ -9,8 +9,8 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DC
 mkdir -p tuning_obj
 pids=()
 OBJS=()
-for f in api gemm_nt potrf gram solve misc reduced layer comm joint grad; do
-    if [ ! -f "tuning_obj/$f.o" ] || [ "$f.hip" -nt "tuning_obj/$f.o" ] || [ common.hpp -nt "tuning_obj/$f.o" ] || [ gemm_tile.hpp -nt "tuning_obj/$f.o" ] || [ chain_kernels.hpp -nt "tuning_obj/$f.o" ] || [ rows_kernels.hpp -nt "tuning_obj/$f.o" ] || [ ../../include/cimrgp.h -nt "tuning_obj/$f.o" ] || [ ../../include/cimrgp_objective.h -nt "tuning_obj/$f.o" ] || [ ../../include/cimrgp_joint.h -nt "tuning_obj/$f.o" ] || [ ../../include/cimrgp_grad.h -nt "tuning_obj/$f.o" ]; then
+for f in api block gemm_nt potrf gram solve misc reduced layer comm joint grad loo; do
+    if [ ! -f "tuning_obj/$f.o" ] || [ "$f.hip" -nt "tuning_obj/$f.o" ] || [ common.hpp -nt "tuning_obj/$f.o" ] || [ abi.hpp -nt "tuning_obj/$f.o" ] || [ gemm_tile.hpp -nt "tuning_obj/$f.o" ] || [ chain_kernels.hpp -nt "tuning_obj/$f.o" ] || [ rows_kernels.hpp -nt "tuning_obj/$f.o" ] || [ ../../include/cimrgp.h -nt "tuning_obj/$f.o" ] || [ ../../include/cimrgp_objective.h -nt "tuning_obj/$f.o" ] || [ ../../include/cimrgp_joint.h -nt "tuning_obj/$f.o" ] || [ ../../include/cimrgp_grad.h -nt "tuning_obj/$f.o" ]; then
         $HIPCC $FLAGS -c "$f.hip" -o "tuning_obj/$f.o" &
         pids+=($!)
     fi
