@@ -363,3 +363,149 @@ class GP_Matern(GP_RBF):
 
     def _make_kernel(self, l, sf, noise=None):
         return DenseMaternKernel(nu=self.nu, l=l, sf=sf, noise=noise)
+
+
+class SparseGP(RegressionMethod):
+    """Inducing-point GP regression plugin (:class:`~cimrgp_amd.Sparse.SparseBlock`): ``approximation='fitc'`` or
+    ``'vfe'``, cost n m^2 for m = ``num_inducing`` inducing inputs.  ``Z=None`` draws them from the z-scored training
+    inputs, ``numpy.random.RandomState(seed).permutation(n)[:min(n, num_inducing)]``; a given ``Z`` (m x d) is in the
+    caller's units and is z-scored with the inputs.  ``nu`` in {0.5, 1.5, 2.5} selects the Matern covariance, None the
+    RBF.  The noise is ``labels.var() * 0.01`` on the z-scored labels, as for ``GP_RBF``.  ``optimize=True``: L-BFGS-B
+    over (log variance, log length-scale, log noise) with Z fixed, on SciPy's own two-point differences of the
+    GPU-evaluated objective; the default keeps the starting values, as the reference's sparse plugins do."""
+    name = 'SparseGP'
+
+    def __init__(self, num_inducing=1000, approximation='fitc', lengthscale=1., variance=1., nu=None, Z=None, seed=0, jitter=1e-6,
+                 dtype='f64', device=None, optimize=False, max_iters=200):
+        super(SparseGP, self).__init__()
+        from .Sparse import APPROXIMATIONS
+        if str(approximation).lower() not in APPROXIMATIONS:
+            raise ValueError("approximation must be 'fitc' or 'vfe', got %r" % (approximation,))
+        if int(num_inducing) < 1:
+            raise ValueError('num_inducing must be at least 1')
+        self.num_inducing = int(num_inducing)
+        self.approximation = str(approximation).lower()
+        self.nu = None if nu is None else float(nu)
+        self._initial = (float(lengthscale), float(variance))
+        self.kernel = self._make_kernel(lengthscale, variance)          # ValueError for an unsupported nu
+        self.Z = None if Z is None else np.atleast_2d(np.asarray(Z, dtype=np.float64))
+        self.seed = seed
+        self.jitter = float(jitter)
+        self.dtype = dev.as_torch_dtype(dtype)
+        self.device = device
+        self.optimize = optimize
+        self.max_iters = max_iters
+        self.optimizer_result = None
+        self.block = None
+        self.inducing_ids = None             # rows of the training set drawn as inducing inputs (Z=None)
+
+    def _make_kernel(self, l, sf, noise=None):
+        if self.nu is None:
+            return RBFKernel(l=l, sf=sf, noise=noise)
+        return DenseMaternKernel(nu=self.nu, l=l, sf=sf, noise=noise)
+
+    def inducing_draw(self, n):
+        """The documented draw of inducing rows among n training rows."""
+        return np.random.RandomState(self.seed).permutation(n)[:min(n, self.num_inducing)]
+
+    def _inducing_inputs(self, inputs):
+        """Z in the (z-scored) units of ``inputs``."""
+        if self.Z is None:
+            self.inducing_ids = self.inducing_draw(inputs.shape[0])
+            return inputs[self.inducing_ids]
+        self.inducing_ids = None
+        if self.Z.shape[1] != inputs.shape[1]:
+            raise ValueError('Z must have the dimension of the inputs')
+        return (self.Z - self.data_mean) / self.data_std if self.preprocess else self.Z
+
+    def _block(self, ell, sf, noise):
+        from .Sparse import SparseBlock
+        return SparseBlock(self._x, self._z, self._make_kernel(ell, sf, noise), self.approximation, self.jitter)
+
+    def log_marginal_likelihood(self, ell=None, sf=None, noise=None):
+        """The FITC marginal likelihood / the VFE bound of the fitted data at (ell, sf, noise); the fitted values by
+        default.  Raises LinAlgError if a factorisation fails or a lambda_i is not positive."""
+        if self.block is None:
+            raise RuntimeError('call fit() before log_marginal_likelihood()')
+        if ell is None and sf is None and noise is None:
+            return self.block.log_marginal_likelihood()
+        k = self.kernel
+        blk = self._block(k.l if ell is None else float(ell), k.sf if sf is None else float(sf),
+                          k.noise if noise is None else float(noise))
+        return blk.fit(self._y).log_marginal_likelihood()
+
+    def _optimize(self, noise0):
+        from scipy.optimize import minimize
+        theta0 = np.log([self.kernel.sf, self.kernel.l, noise0])
+
+        def objective(theta):
+            sf, ell, noise = np.exp(theta)
+            try:
+                return -self._block(float(ell), float(sf), float(noise)).fit(self._y).log_marginal_likelihood()
+            except np.linalg.LinAlgError:
+                return 1e100
+
+        res = minimize(objective, theta0, jac=None, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
+        self.optimizer_result = res
+        sf, ell, noise = np.exp(res.x)
+        return float(ell), float(sf), float(noise)
+
+    def _fit(self, train_data):
+        inputs, labels = train_data
+        device = dev.require_gpu(self.device)
+        inputs = np.atleast_2d(np.asarray(inputs, dtype=np.float64))
+        labels = np.atleast_2d(np.asarray(labels, dtype=np.float64))
+        self.block = None
+        self.kernel = self._make_kernel(self._initial[0], self._initial[1], float(labels.var()) * NOISE_FRACTION)
+        self._x = dev.to_device(inputs, self.dtype, device)
+        self._y = dev.to_device(labels, self.dtype, device)
+        self._z = dev.to_device(self._inducing_inputs(inputs), self.dtype, device)
+        if self.optimize:
+            ell, sf, noise = self._optimize(self.kernel.noise)
+            self.kernel = self._make_kernel(ell, sf, noise)
+        self.block = self._block(self.kernel.l, self.kernel.sf, self.kernel.noise).fit(self._y)
+        return True
+
+    def _predict(self, test_data):
+        return self._predict_mean_var(test_data, want_var=False)[0]
+
+    def _predict_mean_var(self, test_data, want_var, include_noise=False, budget_bytes=None):
+        blk = self.block
+        if blk is None:
+            raise RuntimeError('call fit() before predict()')
+        xs = dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, blk.x.device)
+        mean = torch.empty((xs.shape[0], blk.gamma.shape[1]), dtype=self.dtype, device=xs.device)
+        var = torch.empty(xs.shape[0], dtype=self.dtype, device=xs.device) if want_var else None
+        blk.predict(xs, mean, var, include_noise=include_noise, budget_bytes=budget_bytes)
+        return mean.double().cpu().numpy(), None if var is None else var.double().cpu().numpy()
+
+    def predict_with_variance(self, test_data, include_noise=False, budget_bytes=None):
+        """Mean (un-z-scored) and predictive variance, left in z-scored label units as ``GP_RBF.predict_with_variance``
+        leaves it (latent; ``include_noise`` adds the noise).  ``budget_bytes``: work area of the chunked prediction."""
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        mean, var = self._predict_mean_var(test_data, True, include_noise, budget_bytes)
+        if self.preprocess:
+            mean = self._reverse_trans_labels(mean)
+        return mean, var
+
+
+class SGP_FITC(SparseGP):
+    """The reference's ``SGP_FITC`` plugin: :class:`SparseGP` with ``approximation='fitc'``."""
+    name = 'SGP_FITC'
+
+    def __init__(self, num_inducing=1000, lengthscale=1., variance=1., nu=None, Z=None, seed=0, jitter=1e-6, dtype='f64',
+                 device=None, optimize=False, max_iters=200):
+        super(SGP_FITC, self).__init__(num_inducing, 'fitc', lengthscale, variance, nu, Z, seed, jitter, dtype, device, optimize,
+                                       max_iters)
+
+
+class SparseGP_RBF(SparseGP):
+    """The reference's ``SparseGP_RBF`` plugin: :class:`SparseGP` with ``approximation='vfe'``, the bound GPy's
+    ``SparseGPRegression`` optimises (without the reference's ``+ Linear`` term)."""
+    name = 'SparseGP_RBF'
+
+    def __init__(self, num_inducing=1000, lengthscale=1., variance=1., nu=None, Z=None, seed=0, jitter=1e-6, dtype='f64',
+                 device=None, optimize=False, max_iters=200):
+        super(SparseGP_RBF, self).__init__(num_inducing, 'vfe', lengthscale, variance, nu, Z, seed, jitter, dtype, device, optimize,
+                                           max_iters)

@@ -116,6 +116,14 @@ LOO_SIGNATURES = {
     "cimrgp_loo_batched": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/cimrgp_sparse.h (inducing-point sparse GP regression)
+SPARSE_SIGNATURES = {
+    "cimrgp_wsyrk_tn_scratch_bytes": (_sz, [_i32, _i64, _i64, _i32]),
+    "cimrgp_wsyrk_tn": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _dbl, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "cimrgp_sparse_lambda": (_i32, [_i32, _vp, _i64, _i64, _i64, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp]),
+    "cimrgp_sparse_tail": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _dbl, _dbl, _vp, _vp, _i32, _vp]),
+}
+
 _lib = None
 
 
@@ -136,7 +144,7 @@ def load():
             "There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + \
-            list(JOINT_SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(LOO_SIGNATURES.items()):
+            list(JOINT_SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(LOO_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if a symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -429,6 +429,56 @@ def loo(y, alpha, diag, mean_out=None, var_out=None, starts=None):
                                           int(diag.shape[0]), _p(mean_out), _p(var_out), _stream()), "cimrgp_loo_batched")
 
 
+def wsyrk_tn_scratch_bytes(n, m, q, dtype):
+    return int(_lib.load().cimrgp_wsyrk_tn_scratch_bytes(_DT[dtype], int(n), int(m), int(q)))
+
+
+def wsyrk_tn(abuf, n, m, w, r=None, diag_add=0.0, out=None, g=None, scratch=None):
+    """lower(out)[:m, :m] = diag_add I + A^T diag(w) A and, with ``r`` (n x q), g (m x q) = A^T diag(w) r, for
+    A = abuf[:n, :m] (cimrgp_wsyrk_tn, include/cimrgp_sparse.h).  Returns (out, g); out is allocated with a padded
+    pitch if None, the scratch for this call only if None."""
+    lib = _lib.load()
+    dtype = abuf.dtype
+    q = 0 if r is None else int(r.shape[1])
+    if out is None:
+        out = alloc_matrix(m, m, dtype, abuf.device)
+    if r is not None and g is None:
+        g = torch.empty((int(m), q), dtype=dtype, device=abuf.device)
+    nbytes = wsyrk_tn_scratch_bytes(n, m, q, dtype)
+    if scratch is None:
+        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=abuf.device)
+    _lib.check(lib.cimrgp_wsyrk_tn(_DT[dtype], _p(abuf), int(n), int(m), abuf.stride(0), _p(w), _p(r), q, float(diag_add), _p(out),
+                                   out.stride(0), _p(g), _p(scratch), scratch.numel(), _stream()), "cimrgp_wsyrk_tn")
+    return out, g
+
+
+def sparse_lambda(abuf, n, m, sf2, noise, mode, lam=None, w=None, sums=None):
+    """lam, w = 1 / lam (n,) and sums = [sum log lam, sum (sf2 - q_i), #(lam <= 0)] (device float64[3]) from one pass
+    over A = abuf[:n, :m] (cimrgp_sparse_lambda); mode 0: FITC, 1: VFE."""
+    lib = _lib.load()
+    if lam is None:
+        lam = torch.empty(int(n), dtype=abuf.dtype, device=abuf.device)
+    if w is None:
+        w = torch.empty(int(n), dtype=abuf.dtype, device=abuf.device)
+    if sums is None:
+        sums = torch.empty(3, dtype=torch.float64, device=abuf.device)
+    _lib.check(lib.cimrgp_sparse_lambda(_DT[abuf.dtype], _p(abuf), int(n), int(m), abuf.stride(0), float(sf2), float(noise), int(mode),
+                                        _p(lam), _p(w), _p(sums), _stream()), "cimrgp_sparse_lambda")
+    return lam, w, sums
+
+
+def sparse_tail(astar, wstar, ns, m, gamma, sf2, extra_var=0.0, mean_out=None, var_out=None, accumulate=False):
+    """mean_out (ns x q) (+)= W* gamma, var_out (ns) (+)= sf2 + extra_var - sum A*^2 + sum W*^2 (cimrgp_sparse_tail);
+    either output may be None.  astar and wstar share their pitch."""
+    lib = _lib.load()
+    if astar is not None and astar.stride(0) != wstar.stride(0):
+        raise ValueError("astar and wstar must have the same row pitch")
+    q = 0 if gamma is None else int(gamma.shape[1])
+    _lib.check(lib.cimrgp_sparse_tail(_DT[wstar.dtype], _p(astar), _p(wstar), int(ns), int(m), wstar.stride(0), _p(gamma), q,
+                                      float(sf2), float(extra_var), _p(mean_out), _p(var_out), int(bool(accumulate)), _stream()),
+               "cimrgp_sparse_tail")
+
+
 def layer_lml_scratch_bytes(n, q, batch, dtype):
     return int(_lib.load().cimrgp_layer_lml_grad_scratch_bytes(_DT[dtype], int(n), int(q), int(batch)))
 

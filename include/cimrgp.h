@@ -473,4 +473,8 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
 /* Leave-one-out cross-validation of a fitted block and the triangular inverse behind it: include/cimrgp_loo.h. */
 #include "cimrgp_loo.h"
 
+/* Inducing-point (sparse) GP regression: the weighted transposed product, lambda and the predictive tail:
+ * include/cimrgp_sparse.h. */
+#include "cimrgp_sparse.h"
+
 #endif /* CIMRGP_H */
