@@ -372,17 +372,30 @@ class SparseGP(RegressionMethod):
     caller's units and is z-scored with the inputs.  ``nu`` in {0.5, 1.5, 2.5} selects the Matern covariance, None the
     RBF.  The noise is ``labels.var() * 0.01`` on the z-scored labels, as for ``GP_RBF``.  ``optimize=True``: L-BFGS-B
     over (log variance, log length-scale, log noise) with Z fixed, on SciPy's own two-point differences of the
-    GPU-evaluated objective; the default keeps the starting values, as the reference's sparse plugins do."""
+    GPU-evaluated objective; the default keeps the starting values, as the reference's sparse plugins do.
+    ``jac='analytic'`` gives L-BFGS-B the analytic gradient instead (:meth:`~cimrgp_amd.Sparse.SparseBlock.lml_grad`: one
+    call per step instead of four evaluations); ``optimize_inducing=True`` (needs ``optimize=True, jac='analytic'``) also
+    learns Z, as GPy's ``SparseGPRegression`` does: the parameter vector is [log sf, log l, log noise, Z.ravel()] with Z in
+    the z-scored units of the fit.  After the fit ``inducing_inputs`` holds Z in the caller's units.  With a Matern 1/2
+    covariance the objective has a kink wherever an inducing input sits on a training input or on another inducing input
+    (Z drawn from the data starts there); the gradient takes dk/dz = 0 at r = 0 and the combination is not refused."""
     name = 'SparseGP'
 
     def __init__(self, num_inducing=1000, approximation='fitc', lengthscale=1., variance=1., nu=None, Z=None, seed=0, jitter=1e-6,
-                 dtype='f64', device=None, optimize=False, max_iters=200):
+                 dtype='f64', device=None, optimize=False, max_iters=200, jac='2-point', optimize_inducing=False):
         super(SparseGP, self).__init__()
         from .Sparse import APPROXIMATIONS
         if str(approximation).lower() not in APPROXIMATIONS:
             raise ValueError("approximation must be 'fitc' or 'vfe', got %r" % (approximation,))
         if int(num_inducing) < 1:
             raise ValueError('num_inducing must be at least 1')
+        if jac not in ('2-point', 'analytic'):
+            raise ValueError("jac must be '2-point' or 'analytic', got %r" % (jac,))
+        if optimize_inducing and not (optimize and jac == 'analytic'):
+            raise ValueError("optimize_inducing=True needs optimize=True and jac='analytic'")
+        self.jac = jac
+        self.optimize_inducing = bool(optimize_inducing)
+        self.inducing_inputs = None          # Z of the fitted model, in the caller's units
         self.num_inducing = int(num_inducing)
         self.approximation = str(approximation).lower()
         self.nu = None if nu is None else float(nu)
@@ -434,6 +447,43 @@ class SparseGP(RegressionMethod):
                           k.noise if noise is None else float(noise))
         return blk.fit(self._y).log_marginal_likelihood()
 
+    def log_marginal_likelihood_grad(self, ell=None, sf=None, noise=None, want_z=True):
+        """``(lml, dtheta, dZ)`` of the fitted data at (ell, sf, noise), the fitted values by default: the objective of
+        :meth:`log_marginal_likelihood`, its gradient w.r.t. (log sf, log ell, log noise) as a (3,) array and, with
+        ``want_z``, w.r.t. the inducing inputs in the (z-scored) units of the fit as an (m, d) array, else None.
+        Raises as :meth:`log_marginal_likelihood` does."""
+        if self.block is None:
+            raise RuntimeError('call fit() before log_marginal_likelihood_grad()')
+        k = self.kernel
+        blk = self._block(k.l if ell is None else float(ell), k.sf if sf is None else float(sf),
+                          k.noise if noise is None else float(noise))
+        lml, dtheta, dz = blk.lml_grad(self._y, want_z=want_z)
+        return lml, dtheta, None if dz is None else dz.double().cpu().numpy()
+
+    def _optimize_analytic(self, noise0):
+        """L-BFGS-B on the analytic gradient over [log sf, log l, log noise] and, with ``optimize_inducing``, Z."""
+        from scipy.optimize import minimize
+        theta0 = np.log([self.kernel.sf, self.kernel.l, noise0])
+        zshape = tuple(self._z.shape)
+        if self.optimize_inducing:
+            theta0 = np.concatenate([theta0, self._z.double().cpu().numpy().ravel()])
+
+        def objective(theta):
+            sf, ell, noise = np.exp(theta[:3])
+            if self.optimize_inducing:
+                self._z = dev.to_device(theta[3:].reshape(zshape), self.dtype, self._x.device)
+            try:
+                lml, dtheta, dz = self._block(float(ell), float(sf), float(noise)).lml_grad(self._y, want_z=self.optimize_inducing)
+            except np.linalg.LinAlgError:
+                return 1e100, np.zeros(theta.shape[0])
+            grad = dtheta if dz is None else np.concatenate([dtheta, dz.double().cpu().numpy().ravel()])
+            return -lml, -grad
+
+        res = minimize(objective, theta0, jac=True, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
+        if self.optimize_inducing:
+            self._z = dev.to_device(res.x[3:].reshape(zshape), self.dtype, self._x.device)
+        return res
+
     def _optimize(self, noise0):
         from scipy.optimize import minimize
         theta0 = np.log([self.kernel.sf, self.kernel.l, noise0])
@@ -445,9 +495,12 @@ class SparseGP(RegressionMethod):
             except np.linalg.LinAlgError:
                 return 1e100
 
-        res = minimize(objective, theta0, jac=None, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
+        if self.jac == 'analytic':
+            res = self._optimize_analytic(noise0)
+        else:
+            res = minimize(objective, theta0, jac=None, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
         self.optimizer_result = res
-        sf, ell, noise = np.exp(res.x)
+        sf, ell, noise = np.exp(res.x[:3])
         return float(ell), float(sf), float(noise)
 
     def _fit(self, train_data):
@@ -464,6 +517,8 @@ class SparseGP(RegressionMethod):
             ell, sf, noise = self._optimize(self.kernel.noise)
             self.kernel = self._make_kernel(ell, sf, noise)
         self.block = self._block(self.kernel.l, self.kernel.sf, self.kernel.noise).fit(self._y)
+        z = self._z.double().cpu().numpy()
+        self.inducing_inputs = z * self.data_std + self.data_mean if self.preprocess else z
         return True
 
     def _predict(self, test_data):
@@ -495,9 +550,9 @@ class SGP_FITC(SparseGP):
     name = 'SGP_FITC'
 
     def __init__(self, num_inducing=1000, lengthscale=1., variance=1., nu=None, Z=None, seed=0, jitter=1e-6, dtype='f64',
-                 device=None, optimize=False, max_iters=200):
+                 device=None, optimize=False, max_iters=200, jac='2-point', optimize_inducing=False):
         super(SGP_FITC, self).__init__(num_inducing, 'fitc', lengthscale, variance, nu, Z, seed, jitter, dtype, device, optimize,
-                                       max_iters)
+                                       max_iters, jac, optimize_inducing)
 
 
 class SparseGP_RBF(SparseGP):
@@ -506,6 +561,6 @@ class SparseGP_RBF(SparseGP):
     name = 'SparseGP_RBF'
 
     def __init__(self, num_inducing=1000, lengthscale=1., variance=1., nu=None, Z=None, seed=0, jitter=1e-6, dtype='f64',
-                 device=None, optimize=False, max_iters=200):
+                 device=None, optimize=False, max_iters=200, jac='2-point', optimize_inducing=False):
         super(SparseGP_RBF, self).__init__(num_inducing, 'vfe', lengthscale, variance, nu, Z, seed, jitter, dtype, device, optimize,
-                                           max_iters)
+                                           max_iters, jac, optimize_inducing)

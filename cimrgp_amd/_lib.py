@@ -124,6 +124,14 @@ SPARSE_SIGNATURES = {
     "cimrgp_sparse_tail": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _dbl, _dbl, _vp, _vp, _i32, _vp]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/cimrgp_sparse_grad.h (gradients of the sparse objective)
+SPARSE_GRAD_SIGNATURES = {
+    "cimrgp_cov_pair_grad_scratch_bytes": (_sz, [_i64, _i64, _i32]),
+    "cimrgp_cov_pair_grad": (_i32, [_i32, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "cimrgp_sparse_grad_rows": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _dbl, _vp, _vp, _vp, _vp]),
+    "cimrgp_sparse_grad_combine": (_i32, [_i32, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp]),
+}
+
 _lib = None
 
 
@@ -144,7 +152,8 @@ def load():
             "There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + \
-            list(JOINT_SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(LOO_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items()):
+            list(JOINT_SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(LOO_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items()) + \
+            list(SPARSE_GRAD_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if a symbol is missing
         fn.restype = res
         fn.argtypes = args

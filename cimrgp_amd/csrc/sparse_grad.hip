@@ -1,0 +1,418 @@
+// Gradients of the sparse (inducing-point) objective: the three calls of include/cimrgp_sparse_grad.h.
+//   cov_pair_grad        k_cov_pair_grad    one tile of 128 columns of G and one slice of its rows per workgroup: k, g and
+//                                           dk/dlog l recomputed per pair, the products with G and every sum in FP64;
+//                                           the partial db and the two partial scalar sums go to scratch
+//                        k_pair_grad_reduce adds the partials in slice (and tile) order, applies scale / accumulate
+//   sparse_grad_rows     k_sparse_grad_rows (a wave per row: V_i gamma, |V_i|^2 -> beta_i, h_i) and k_sparse_grad_sums
+//                                           (one workgroup: the two sums in a fixed order, t)
+//   sparse_grad_combine  k_sparse_grad_combine (a wave per row, in place on Y)
+//
+// k_cov_pair_grad.  The layout is the cross-Gram kernel's (gram.hip) read instead of written: a lane owns the 16 bytes
+// of a row of G it loads with ONE instruction -- EPL = 2 doubles / 4 floats -- and the lanes of a wave are adjacent
+// along the row, so every load instruction reads whole 512-byte runs (1 row x 64 lanes in FP64, 2 rows x 32 lanes in
+// FP32).  The lane's EPL points of xb stay in registers for the whole slice, its EPL x d sums of db too; the row's
+// point of xa is the same address for every lane of the row (one request).  The next row's G chunk and xa point are
+// loaded before the current row's exponentials.  A chunk that straddles column nb, or is not 16-byte aligned, is read
+// element by element: no column >= nb and no row >= na of G is read.
+#include "abi.hpp"
+
+namespace cimrgp {
+
+namespace {
+
+constexpr int PG_CT = 128;                    // columns of G per workgroup
+constexpr int PG_MAXD = 8;
+constexpr int PG_TARGET_WGS = 1024;           // tiles x S aims at four workgroups per compute unit (256 units)
+constexpr int PG_SLICE_ALIGN = 8;             // rows of G per pass of a workgroup (4 waves x 2 rows in FP32)
+constexpr int SG_MAXQ = 8;
+
+// S(na, nb) and the slice length: a function of na and nb alone (not of the dtype, the device or its load).
+static inline int64_t pg_tiles(int64_t nb) { return (nb + PG_CT - 1) / PG_CT; }
+static inline int64_t pg_slice_len(int64_t na, int64_t nb)
+{
+    int64_t s = PG_TARGET_WGS / pg_tiles(nb);
+    const int64_t smax = (na + 255) / 256;                             // a slice is at least 256 rows
+    if (s > smax) s = smax;
+    if (s < 1) s = 1;
+    const int64_t len = (na + s - 1) / s;
+    return (len + PG_SLICE_ALIGN - 1) / PG_SLICE_ALIGN * PG_SLICE_ALIGN;
+}
+static inline int64_t pg_slices(int64_t na, int64_t nb) { const int64_t len = pg_slice_len(na, nb); return (na + len - 1) / len; }
+static inline bool pg_sizes_ok(int64_t na, int64_t nb, int d)
+{
+    return na >= 1 && na <= CIMRGP_PAIR_GRAD_MAX_NA && nb >= 1 && nb <= CIMRGP_PAIR_GRAD_MAX_NB && d >= 1 && d <= PG_MAXD;
+}
+// doubles of scratch: the partial db, then the partial sums
+static inline int64_t pg_dbpart_elems(int64_t na, int64_t nb, int d) { return pg_slices(na, nb) * pg_tiles(nb) * PG_CT * d; }
+static inline int64_t pg_sumpart_elems(int64_t na, int64_t nb) { return pg_slices(na, nb) * pg_tiles(nb) * 2; }
+
+// k, g (dk/da_e = -g (a_e - b_e)) and dk/dlog l of one pair from the squared distance, in the dtype: the Cov<COV>
+// policies' expressions (common.hpp), and grad.hip's g(r).
+template <int COV, typename T, int D>
+static __device__ __forceinline__ void pair_terms(T d2, T df0, T c, T sf2, T& kv, T& gv, T& lv)
+{
+    if constexpr (COV == CIMRGP_COV_RBF) {
+        kv = Cov<COV>::template value<T, D>(d2, df0, c, sf2);
+        gv = kv * ((T)-2 * c);
+        lv = gv * d2;
+    } else {
+        const T r = Cov<COV>::template radius<T, D>(d2, df0);
+        const T t = c * r;
+        const T v = exp(-t);
+        kv = sf2 * Cov<COV>::poly(t) * v;
+        gv = Cov<COV>::ard(t, r, v, c, sf2);
+        lv = Cov<COV>::dlogl(t, v, sf2);
+    }
+}
+
+// blockIdx.x = tile + tiles * slice.
+template <typename T, int COV, int D>
+__global__ __launch_bounds__(256)
+void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb, int nb, int d, const T* __restrict__ G, int64_t ldg,
+                     T c, T sf2, int tiles, int slice_len, int want_db, double* __restrict__ dbpart, double* __restrict__ sumpart)
+{
+    constexpr int EPL = 16 / (int)sizeof(T);    // elements per lane and row
+    constexpr int LPR = PG_CT / EPL;            // lanes per tile row
+    constexpr int RPI = 64 / LPR;               // rows per wave and load instruction
+    constexpr int NPH = 4 * RPI;                // row phases of the workgroup
+    constexpr int DD = D ? D : PG_MAXD;
+    __shared__ double red[NPH * PG_CT];
+    __shared__ double sred[4][2];
+    const int slice = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - slice * tiles;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cx = (lane % LPR) * EPL;          // first column of this lane inside the tile
+    const int phase = wave * RPI + lane / LPR;
+    const int gc = tile * PG_CT + cx;
+    const int r0 = slice * slice_len, r1 = min(na, r0 + slice_len);
+
+    T xc[EPL][DD];
+#pragma unroll
+    for (int b = 0; b < EPL; ++b)
+#pragma unroll
+        for (int k = 0; k < DD; ++k) xc[b][k] = ((D || k < d) && gc + b < nb) ? xb[(int64_t)(gc + b) * d + k] : (T)0;
+    const bool whole = gc + EPL <= nb;          // the lane's chunk lies inside the matrix
+
+    auto load_g = [&](int i, T* gv) {
+        const T* src = G + (int64_t)i * ldg + gc;
+        if (whole && (reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
+            const uint4 v = *reinterpret_cast<const uint4*>(src);
+            __builtin_memcpy(gv, &v, 16);
+        } else {
+#pragma unroll
+            for (int b = 0; b < EPL; ++b) gv[b] = (gc + b < nb) ? src[b] : (T)0;
+        }
+    };
+    auto load_x = [&](int i, T* xr) {
+#pragma unroll
+        for (int k = 0; k < DD; ++k) xr[k] = (D || k < d) ? xa[(int64_t)i * d + k] : (T)0;
+    };
+
+    double acc[EPL][DD], sk = 0.0, sl = 0.0;
+#pragma unroll
+    for (int b = 0; b < EPL; ++b)
+#pragma unroll
+        for (int k = 0; k < DD; ++k) acc[b][k] = 0.0;
+
+    T gcur[EPL], xcur[DD], gnext[EPL], xnext[DD];
+    int i = r0 + phase;
+    if (i < r1) { load_g(i, gcur); load_x(i, xcur); }
+    for (; i < r1; i += NPH) {
+        const bool more = i + NPH < r1;
+        if (more) { load_g(i + NPH, gnext); load_x(i + NPH, xnext); }
+#pragma unroll
+        for (int b = 0; b < EPL; ++b) {
+            T df[DD], d2 = (T)0;
+#pragma unroll
+            for (int k = 0; k < DD; ++k) {
+                df[k] = xcur[k] - xc[b][k];
+                d2 += df[k] * df[k];
+            }
+            T kv, gv, lv;
+            pair_terms<COV, T, D>(d2, df[0], c, sf2, kv, gv, lv);
+            const double w = (double)gcur[b];
+            sk += w * (double)kv;
+            sl += w * (double)lv;
+            const double wg = w * (double)gv;
+#pragma unroll
+            for (int k = 0; k < DD; ++k) acc[b][k] += wg * (double)df[k];
+        }
+        if (more) {
+#pragma unroll
+            for (int b = 0; b < EPL; ++b) gcur[b] = gnext[b];
+#pragma unroll
+            for (int k = 0; k < DD; ++k) xcur[k] = xnext[k];
+        }
+    }
+
+    // the two scalar sums: pairwise over the lanes of a wave, then the four waves in order
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sk += __shfl_xor(sk, off, 64);
+        sl += __shfl_xor(sl, off, 64);
+    }
+    if (lane == 0) { sred[wave][0] = sk; sred[wave][1] = sl; }
+    __syncthreads();
+    if (tid < 2) sumpart[(int64_t)blockIdx.x * 2 + tid] = ((sred[0][tid] + sred[1][tid]) + sred[2][tid]) + sred[3][tid];
+    if (!want_db) return;
+    // db: per dimension, the NPH row phases of a column are added in phase order
+    double* out = dbpart + (int64_t)blockIdx.x * PG_CT * d;
+#pragma unroll
+    for (int k = 0; k < DD; ++k) {
+        if (!(D || k < d)) break;
+#pragma unroll
+        for (int b = 0; b < EPL; ++b) red[phase * PG_CT + cx + b] = acc[b][k];
+        __syncthreads();
+        if (tid < PG_CT) {
+            double s = red[tid];
+#pragma unroll
+            for (int p = 1; p < NPH; ++p) s += red[p * PG_CT + tid];
+            out[tid * d + k] = s;
+        }
+        __syncthreads();
+    }
+}
+
+// blockIdx.x < dblocks: 256 elements of db, each the sum of its S partials in slice order; the last workgroup (sums
+// wanted): thread t adds the partials t, t + 256, .. of both scalar sums (tile-major within a slice), then the 256
+// partial sums are added pairwise in LDS.
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_pair_grad_reduce(const double* __restrict__ dbpart, const double* __restrict__ sumpart, int nb, int d, int tiles, int slices,
+                        int dblocks, double scale, int accumulate, T* __restrict__ db, double* __restrict__ sums)
+{
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x < dblocks) {
+        const int64_t e = (int64_t)blockIdx.x * 256 + tid;
+        if (e >= (int64_t)nb * d) return;
+        const int j = (int)(e / d), k = (int)(e - (int64_t)j * d);
+        const int tile = j / PG_CT, jj = j - tile * PG_CT;
+        const double* p = dbpart + ((int64_t)tile * PG_CT + jj) * d + k;
+        double s = p[0];
+        for (int sl = 1; sl < slices; ++sl) s += p[(int64_t)sl * tiles * PG_CT * d];
+        s *= scale;
+        db[e] = accumulate ? (T)((double)db[e] + s) : (T)s;
+        return;
+    }
+    __shared__ double red[2][256];
+    const int64_t parts = (int64_t)tiles * slices;
+    double s0 = 0.0, s1 = 0.0;
+    for (int64_t p = tid; p < parts; p += 256) {
+        s0 += sumpart[2 * p];
+        s1 += sumpart[2 * p + 1];
+    }
+    red[0][tid] = s0;
+    red[1][tid] = s1;
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {
+        if (tid < half) {
+            red[0][tid] += red[0][tid + half];
+            red[1][tid] += red[1][tid + half];
+        }
+        __syncthreads();
+    }
+    if (tid < 2) sums[tid] = accumulate ? sums[tid] + red[tid][0] : red[tid][0];
+}
+
+// ----------------------------------------------------------------------- rows ----
+// A wave per row (4 rows per workgroup), as k_sparse_rowsq / k_sparse_tail: lane l takes columns l, l + 64, .. in FP64,
+// then the 64 partial sums are added pairwise (xor 32, 16, .. 1): a fixed order.  t <- h_i (k_sparse_grad_sums turns it
+// into t for VFE).
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_sparse_grad_rows(const T* __restrict__ V, int64_t ldv, int n, int m, const T* __restrict__ gamma, const T* __restrict__ r,
+                        const T* __restrict__ w, int q, T* __restrict__ beta, T* __restrict__ t)
+{
+    const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n) return;
+    const T* v = V + (int64_t)row * ldv;
+    double sv = 0.0, acc[SG_MAXQ];
+#pragma unroll
+    for (int c = 0; c < SG_MAXQ; ++c) acc[c] = 0.0;
+    for (int j = lane; j < m; j += 64) {
+        const double vv = (double)v[j];
+        sv += vv * vv;
+#pragma unroll
+        for (int c = 0; c < SG_MAXQ; ++c)
+            if (c < q) acc[c] += vv * (double)gamma[(int64_t)j * q + c];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sv += __shfl_xor(sv, off, 64);
+#pragma unroll
+        for (int c = 0; c < SG_MAXQ; ++c) acc[c] += __shfl_xor(acc[c], off, 64);
+    }
+    if (lane != 0) return;
+    const double wi = (double)w[row];
+    double bsq = 0.0;
+#pragma unroll
+    for (int c = 0; c < SG_MAXQ; ++c) {
+        if (c < q) {
+            const double bt = wi * ((double)r[(int64_t)row * q + c] - acc[c]);
+            beta[(int64_t)row * q + c] = (T)bt;
+            bsq += bt * bt;
+        }
+    }
+    t[row] = (T)(0.5 * (bsq - (double)q * (wi - wi * wi * sv)));
+}
+
+// One workgroup of 1024 threads: thread k takes i = k, k + 1024, ..; the 1024 partial sums are added pairwise in LDS.
+template <typename T>
+__global__ __launch_bounds__(1024)
+void k_sparse_grad_sums(T* __restrict__ t, int n, int mode, double tvfe, double* __restrict__ sums)
+{
+    __shared__ double red[2][1024];
+    const int tid = threadIdx.x;
+    const T tv = (T)tvfe;
+    double sh = 0.0, st = 0.0;
+    for (int i = tid; i < n; i += 1024) {
+        const T h = t[i];
+        sh += (double)h;
+        if (mode == 1) {
+            t[i] = tv;
+            st += (double)tv;
+        } else {
+            st += (double)h;
+        }
+    }
+    red[0][tid] = sh;
+    red[1][tid] = st;
+    __syncthreads();
+    for (int half = 512; half > 0; half >>= 1) {
+        if (tid < half) {
+            red[0][tid] += red[0][tid + half];
+            red[1][tid] += red[1][tid + half];
+        }
+        __syncthreads();
+    }
+    if (tid < 2) sums[tid] = red[tid][0];
+}
+
+// -------------------------------------------------------------------- combine ----
+// A wave per row: lane l takes columns l, l + 64, ..: the loads and the store of a wave are contiguous runs.
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_sparse_grad_combine(const T* __restrict__ A, int64_t lda, T* __restrict__ Y, int64_t ldy, int n, int m,
+                           const T* __restrict__ beta, const T* __restrict__ b, const T* __restrict__ w, const T* __restrict__ t, int q)
+{
+    const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n) return;
+    double bt[SG_MAXQ];
+#pragma unroll
+    for (int c = 0; c < SG_MAXQ; ++c) bt[c] = c < q ? (double)beta[(int64_t)row * q + c] : 0.0;
+    const double qw = (double)q * (double)w[row], t2 = 2.0 * (double)t[row];
+    const T* a = A + (int64_t)row * lda;
+    T* y = Y + (int64_t)row * ldy;
+    for (int j = lane; j < m; j += 64) {
+        double s = 0.0;
+#pragma unroll
+        for (int c = 0; c < SG_MAXQ; ++c)
+            if (c < q) s += bt[c] * (double)b[(int64_t)j * q + c];
+        y[j] = (T)(s - qw * (double)y[j] - t2 * (double)a[j]);
+    }
+}
+
+}  // namespace
+
+template <typename T, int COV>
+static int pair_grad_run_cov(const T* xa, int64_t na, const T* xb, int64_t nb, int d, const T* g, int64_t ldg, double ell, double sf2,
+                             double scale, int accumulate, double* sums, T* db, double* scratch, hipStream_t st, const char* fn)
+{
+    const int64_t tiles = pg_tiles(nb), len = pg_slice_len(na, nb), slices = pg_slices(na, nb);
+    double* dbpart = scratch;
+    double* sumpart = scratch + pg_dbpart_elems(na, nb, d);
+    const dim3 grid((unsigned)(tiles * slices));
+    const T c = (T)cov_scale(COV, ell);
+#define CIMRGP_PAIR_LAUNCH(D_)                                                                                                  \
+    hipLaunchKernelGGL((k_cov_pair_grad<T, COV, D_>), grid, dim3(256), 0, st, xa, (int)na, xb, (int)nb, d, g, ldg, c, (T)sf2,   \
+                       (int)tiles, (int)len, db != nullptr ? 1 : 0, dbpart, sumpart)
+    if (d == 1)      CIMRGP_PAIR_LAUNCH(1);
+    else if (d == 2) CIMRGP_PAIR_LAUNCH(2);
+    else             CIMRGP_PAIR_LAUNCH(0);
+#undef CIMRGP_PAIR_LAUNCH
+    CIMRGP_LAUNCH_CHECK(fn);
+    const int64_t dblocks = db != nullptr ? (nb * d + 255) / 256 : 0;
+    hipLaunchKernelGGL((k_pair_grad_reduce<T>), dim3((unsigned)(dblocks + (sums != nullptr ? 1 : 0))), dim3(256), 0, st,
+                       (const double*)dbpart, (const double*)sumpart, (int)nb, d, (int)tiles, (int)slices, (int)dblocks, scale, accumulate,
+                       db, sums);
+    CIMRGP_LAUNCH_CHECK(fn);
+    return 0;
+}
+
+}  // namespace cimrgp
+
+using namespace cimrgp;
+
+extern "C" {
+
+size_t cimrgp_cov_pair_grad_scratch_bytes(int64_t na, int64_t nb, int d)
+{
+    if (!pg_sizes_ok(na, nb, d)) return 0;
+    return (size_t)(pg_dbpart_elems(na, nb, d) + pg_sumpart_elems(na, nb)) * sizeof(double);
+}
+
+int cimrgp_cov_pair_grad(int dtype, int cov, const void* xa_dev, int64_t na, const void* xb_dev, int64_t nb, int d, const void* g_dev,
+                         int64_t ldg, double ell, double sf2, double scale, int accumulate, double* sums_dev, void* db_dev,
+                         void* scratch_dev, size_t scratch_bytes, void* stream)
+{
+    const char* fn = "cimrgp_cov_pair_grad";
+    CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
+    CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
+    CIMRGP_REQUIRE(xa_dev && xb_dev && g_dev && scratch_dev, fn, "null pointer");
+    CIMRGP_REQUIRE(na >= 1 && na <= CIMRGP_PAIR_GRAD_MAX_NA, fn, "na must be in [1, 16777216]");
+    CIMRGP_REQUIRE(nb >= 1 && nb <= CIMRGP_PAIR_GRAD_MAX_NB, fn, "nb must be in [1, 1048576]");
+    CIMRGP_REQUIRE(d >= 1 && d <= PG_MAXD, fn, "input dimension must be in [1, 8]");
+    CIMRGP_REQUIRE(ldg >= nb, fn, "leading dimension too small");
+    CIMRGP_REQUIRE(ell > 0.0 && sf2 > 0.0, fn, "kernel parameters must be positive");
+    CIMRGP_REQUIRE((reinterpret_cast<uintptr_t>(scratch_dev) & 7u) == 0, fn, "scratch must be 8-byte aligned");
+    CIMRGP_REQUIRE(scratch_bytes >= cimrgp_cov_pair_grad_scratch_bytes(na, nb, d), fn, "scratch too small");
+    if (sums_dev == nullptr && db_dev == nullptr) return 0;
+    return with_dtype(dtype, fn, [&](auto tag) {
+        using T = decltype(tag);
+        return with_cov(cov, [&](auto cv) {
+            return pair_grad_run_cov<T, decltype(cv)::value>((const T*)xa_dev, na, (const T*)xb_dev, nb, d, (const T*)g_dev, ldg, ell, sf2,
+                                                              scale, accumulate, sums_dev, (T*)db_dev, (double*)scratch_dev,
+                                                              stream_of(stream), fn);
+        });
+    });
+}
+
+int cimrgp_sparse_grad_rows(int dtype, const void* v_dev, int64_t n, int64_t m, int64_t ldv, const void* gamma_dev, const void* r_dev,
+                            const void* w_dev, int q, int mode, double noise, void* beta_dev, void* t_dev, double* sums_dev, void* stream)
+{
+    const char* fn = "cimrgp_sparse_grad_rows";
+    CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
+    CIMRGP_REQUIRE(v_dev && gamma_dev && r_dev && w_dev && beta_dev && t_dev && sums_dev, fn, "null pointer");
+    CIMRGP_REQUIRE(n >= 1 && n < (1ll << 31) && m >= 1 && m < (1ll << 31) && ldv >= m, fn, "bad dimensions");
+    CIMRGP_REQUIRE(q >= 1 && q <= SG_MAXQ, fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(mode == 0 || mode == 1, fn, "mode must be 0 (FITC) or 1 (VFE)");
+    CIMRGP_REQUIRE(noise > 0.0, fn, "noise must be positive");
+    return with_dtype(dtype, fn, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((k_sparse_grad_rows<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream_of(stream), (const T*)v_dev, ldv,
+                           (int)n, (int)m, (const T*)gamma_dev, (const T*)r_dev, (const T*)w_dev, q, (T*)beta_dev, (T*)t_dev);
+        CIMRGP_LAUNCH_CHECK(fn);
+        hipLaunchKernelGGL((k_sparse_grad_sums<T>), dim3(1), dim3(1024), 0, stream_of(stream), (T*)t_dev, (int)n, mode,
+                           -0.5 * (double)q / noise, sums_dev);
+        CIMRGP_LAUNCH_CHECK(fn);
+        return 0;
+    });
+}
+
+int cimrgp_sparse_grad_combine(int dtype, const void* a_dev, int64_t lda, void* y_dev, int64_t ldy, int64_t n, int64_t m,
+                               const void* beta_dev, const void* b_dev, const void* w_dev, const void* t_dev, int q, void* stream)
+{
+    const char* fn = "cimrgp_sparse_grad_combine";
+    CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
+    CIMRGP_REQUIRE(a_dev && y_dev && beta_dev && b_dev && w_dev && t_dev, fn, "null pointer");
+    CIMRGP_REQUIRE(n >= 1 && n < (1ll << 31) && m >= 1 && m < (1ll << 31) && lda >= m && ldy >= m, fn, "bad dimensions");
+    CIMRGP_REQUIRE(q >= 1 && q <= SG_MAXQ, fn, "number of outputs must be in [1, 8]");
+    return with_dtype(dtype, fn, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((k_sparse_grad_combine<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream_of(stream), (const T*)a_dev, lda,
+                           (T*)y_dev, ldy, (int)n, (int)m, (const T*)beta_dev, (const T*)b_dev, (const T*)w_dev, (const T*)t_dev, q);
+        CIMRGP_LAUNCH_CHECK(fn);
+        return 0;
+    });
+}
+
+}  // extern "C"

@@ -479,6 +479,57 @@ def sparse_tail(astar, wstar, ns, m, gamma, sf2, extra_var=0.0, mean_out=None, v
                "cimrgp_sparse_tail")
 
 
+def cov_pair_grad_scratch_bytes(na, nb, d):
+    return int(_lib.load().cimrgp_cov_pair_grad_scratch_bytes(int(na), int(nb), int(d)))
+
+
+def cov_pair_grad(xa, xb, gbuf, ell, sf2, scale=1.0, accumulate=False, sums=None, db=None, want_sums=True, want_db=True,
+                  cov=_lib.COV_RBF, scratch=None):
+    """sums (device float64[2]) (+)= [sum G o K, sum G o dK/dlog l] and db (nb x d) (+)= scale sum_i G_ij g(r_ij) (xa_i - xb_j)
+    for G = gbuf[:na, :nb] and the pairs (xa_i, xb_j) (cimrgp_cov_pair_grad, include/cimrgp_sparse_grad.h).  Returns
+    (sums, db); an output that is wanted and not given is allocated, the scratch for this call only if None."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
+    lib = _lib.load()
+    na, d = xa.shape
+    nb = xb.shape[0]
+    if want_sums and sums is None:
+        sums = torch.zeros(2, dtype=torch.float64, device=xa.device)
+    if want_db and db is None:
+        db = torch.zeros((int(nb), int(d)), dtype=xa.dtype, device=xa.device)
+    nbytes = cov_pair_grad_scratch_bytes(na, nb, d)
+    if scratch is None:
+        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=xa.device)
+    _lib.check(lib.cimrgp_cov_pair_grad(_DT[xa.dtype], cov, _p(xa), int(na), _p(xb), int(nb), int(d), _p(gbuf), gbuf.stride(0),
+                                        float(ell), float(sf2), float(scale), int(bool(accumulate)), _p(sums if want_sums else None),
+                                        _p(db if want_db else None), _p(scratch), scratch.numel(), _stream()), "cimrgp_cov_pair_grad")
+    return sums, db
+
+
+def sparse_grad_rows(vbuf, n, m, gamma, r, w, mode, noise, beta=None, t=None, sums=None):
+    """beta (n x q), t (n) and sums = [sum h_i, sum t_i] (device float64[2]) from one pass over V = vbuf[:n, :m]
+    (cimrgp_sparse_grad_rows); mode 0: FITC, 1: VFE."""
+    lib = _lib.load()
+    q = int(gamma.shape[1])
+    if beta is None:
+        beta = torch.empty((int(n), q), dtype=vbuf.dtype, device=vbuf.device)
+    if t is None:
+        t = torch.empty(int(n), dtype=vbuf.dtype, device=vbuf.device)
+    if sums is None:
+        sums = torch.empty(2, dtype=torch.float64, device=vbuf.device)
+    _lib.check(lib.cimrgp_sparse_grad_rows(_DT[vbuf.dtype], _p(vbuf), int(n), int(m), vbuf.stride(0), _p(gamma), _p(r), _p(w), q,
+                                           int(mode), float(noise), _p(beta), _p(t), _p(sums), _stream()), "cimrgp_sparse_grad_rows")
+    return beta, t, sums
+
+
+def sparse_grad_combine(abuf, ybuf, n, m, beta, b, w, t):
+    """ybuf[:n, :m] <- beta b^T - q diag(w) Y - 2 diag(t) A in place (cimrgp_sparse_grad_combine)."""
+    lib = _lib.load()
+    _lib.check(lib.cimrgp_sparse_grad_combine(_DT[abuf.dtype], _p(abuf), abuf.stride(0), _p(ybuf), ybuf.stride(0), int(n), int(m),
+                                              _p(beta), _p(b), _p(w), _p(t), int(beta.shape[1]), _stream()),
+               "cimrgp_sparse_grad_combine")
+    return ybuf
+
+
 def layer_lml_scratch_bytes(n, q, batch, dtype):
     return int(_lib.load().cimrgp_layer_lml_grad_scratch_bytes(_DT[dtype], int(n), int(q), int(batch)))
 

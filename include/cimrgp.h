@@ -477,4 +477,8 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
  * include/cimrgp_sparse.h. */
 #include "cimrgp_sparse.h"
 
+/* Analytic gradients of the sparse objective (hyper-parameters and inducing inputs): the pair contraction and the two
+ * row-wise calls: include/cimrgp_sparse_grad.h. */
+#include "cimrgp_sparse_grad.h"
+
 #endif /* CIMRGP_H */
