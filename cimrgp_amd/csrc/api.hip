@@ -145,15 +145,16 @@ static int layer_fit_impl(const char* fn, int dtype, int cov, const void* x_dev,
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         LayerFit<T> a;
-        a.cov = cov;
-        a.x = (const T*)x_dev; a.y = (const T*)y_dev; a.fbar = (const T*)fbar_dev; a.train_out = (T*)train_out_dev; a.starts = starts_dev;
-        a.batch = batch; a.n = n; a.d = d; a.q = q;
-        a.ell = ell; a.sf2 = sf2; a.noise_fixed = noise_fixed; a.noise_frac = noise_frac; a.noise_floor = noise_floor;
-        a.shared_bias = (const T*)shared_bias_dev; a.shared_noise = (const T*)shared_noise_dev;
-        a.k = (T*)k_arena_dev; a.ldk = ldk; a.sk = k_stride;
-        a.ws = (T*)ws_arena_dev; a.sws = (int64_t)(ws_stride_bytes / sizeof(T)); a.info = info_dev;
-        a.rows = (T*)rows_arena_dev; a.ldr = ldr; a.srows = (int64_t)q * ldr;
-        a.z = (T*)z_dev; a.alpha = (T*)alpha_dev; a.bias = (T*)bias_dev; a.noise = (T*)noise_dev; a.scratch = (T*)scratch_dev;
+        FitFront<T>& fr = a.fr;
+        fr.bc = BatchCov{batch, d, cov, ell, sf2};
+        fr.tr = Points<T>{(const T*)x_dev, starts_dev, n};
+        fr.f = Factors<T>{{(T*)k_arena_dev, ldk, k_stride}, (T*)ws_arena_dev, (int64_t)(ws_stride_bytes / sizeof(T))};
+        fr.info = info_dev;
+        fr.y = (const T*)y_dev; fr.fbar = (const T*)fbar_dev; fr.q = q; fr.shared_bias = (const T*)shared_bias_dev;
+        fr.noise_fixed = noise_fixed; fr.noise_frac = noise_frac; fr.noise_floor = noise_floor; fr.shared_noise = (const T*)shared_noise_dev;
+        fr.rows = Arena<T>{(T*)rows_arena_dev, ldr, (int64_t)q * ldr};
+        fr.z = (T*)z_dev; fr.alpha = (T*)alpha_dev; fr.work = (T*)scratch_dev; fr.bias = (T*)bias_dev; fr.noise = (T*)noise_dev;
+        a.train_out = (T*)train_out_dev;
         return layer_fit_run<T>(a, stream_of(stream));
     });
 }
@@ -177,14 +178,12 @@ static int layer_predict_impl(const char* fn, int dtype, int cov, const void* x_
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         LayerPredict<T> a;
-        a.cov = cov;
-        a.x = (const T*)x_dev; a.starts = starts_dev; a.n = n; a.d = d;
-        a.xs = (const T*)xs_dev; a.t_starts = t_starts_dev; a.ns = ns; a.batch = batch;
-        a.ell = ell; a.sf2 = sf2;
-        a.l = (const T*)l_arena_dev; a.ldl = ldl; a.sl = l_stride;
-        a.ws = (const T*)ws_arena_dev; a.sws = (int64_t)(ws_stride_bytes / sizeof(T));
+        a.bc = BatchCov{batch, d, cov, ell, sf2};
+        a.tr = Points<T>{(const T*)x_dev, starts_dev, n};
+        a.te = Points<T>{(const T*)xs_dev, t_starts_dev, ns};
+        a.f = Factors<const T>{{(const T*)l_arena_dev, ldl, l_stride}, (const T*)ws_arena_dev, (int64_t)(ws_stride_bytes / sizeof(T))};
         a.z = (const T*)z_dev; a.q = q; a.bias = (const T*)bias_dev; a.noise = (const T*)noise_dev;
-        a.w = (T*)w_arena_dev; a.ldw = ldw; a.sw = w_stride; a.mean = (T*)mean_dev; a.var = (T*)var_dev;
+        a.w = Arena<T>{(T*)w_arena_dev, ldw, w_stride}; a.mean = (T*)mean_dev; a.var = (T*)var_dev;
         return layer_predict_run<T>(a, stream_of(stream));
     });
 }
@@ -305,7 +304,7 @@ int cimrgp_block_posterior_staged(int dtype, const void* x_dev, int64_t n, int d
     CIMRGP_REQUIRE(x_dev && y_dev && k_dev && workspace_dev && info_dev && w_dev && alpha_dev && z_dev && scratch_dev, fn, "null pointer");
     CIMRGP_REQUIRE(ns == 0 || (xs_dev && mean_dev && var_dev), fn, "null pointer (test points)");
     CIMRGP_REQUIRE(n >= 1 && ns >= 0 && ldk >= n && ldw >= n, fn, "bad dimensions");
-    CIMRGP_REQUIRE(q >= 1 && q <= 8, fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(q >= 1 && q <= MAXQ, fn, "number of outputs must be in [1, 8]");
     CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     const int64_t e = elems_per_16_bytes(dtype);
     CIMRGP_REQUIRE(ldk % e == 0 && ldw % e == 0, fn, "leading dimensions must be multiples of 16 bytes");
@@ -335,11 +334,7 @@ int cimrgp_potrf_rows_batched(int dtype, void* k_dev, int64_t n, int64_t ldk, in
     CIMRGP_REQUIRE(m == 0 || (block_stride_ok(b_stride, m, n, ldb) && b_stride % e == 0), fn, "row-block stride too small or misaligned");
     CIMRGP_REQUIRE(workspace_stride_ok(dtype, n, workspace_stride_bytes), fn, "workspace stride too small or misaligned");
     if (n == 0) return check_hip(hipMemsetAsync(info_dev, 0, sizeof(int32_t) * (size_t)batch, stream_of(stream)), fn, "memset");
-    PotrfBatch bt;
-    bt.count = batch;
-    bt.sk = k_stride;
-    bt.sws = (int64_t)(workspace_stride_bytes / elem_bytes(dtype));
-    bt.sb = b_stride;
+    const PotrfBatch bt{batch, k_stride, (int64_t)(workspace_stride_bytes / elem_bytes(dtype)), b_stride};
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         return potrf_batched_run<T>((T*)k_dev, n, ldk, (T*)workspace_dev, info_dev, (T*)b_dev, m, ldb, bt, stream_of(stream));
@@ -354,10 +349,7 @@ int cimrgp_solve_lt_batched(int dtype, const void* l_dev, int64_t n, int64_t ldl
     CIMRGP_REQUIRE(batch >= 1, fn, "batch must be >= 1");
     CIMRGP_REQUIRE(n >= 0 && ldl >= n, fn, "bad dimensions");
     CIMRGP_REQUIRE(workspace_stride_bytes >= cimrgp_potrf_workspace_bytes(dtype, n), fn, "workspace stride too small");
-    PotrfBatch bt;
-    bt.count = batch;
-    bt.sk = l_stride;
-    bt.sws = (int64_t)(workspace_stride_bytes / elem_bytes(dtype));
+    const PotrfBatch bt{batch, l_stride, (int64_t)(workspace_stride_bytes / elem_bytes(dtype)), 0};
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         return potrs_run<T>((const T*)l_dev, n, ldl, (const T*)workspace_dev, (T*)z_dev, q, nullptr, (T*)scratch_dev, true,
@@ -668,8 +660,8 @@ int cimrgp_layer_lml_grad_cov(int dtype, int cov, const void* x_dev, const void*
     CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
     CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(batch >= 1 && batch < 65536 && n >= 1 && n < (1ll << 30) && ldk >= n, fn, "bad dimensions");
-    CIMRGP_REQUIRE(d >= 1 && d <= 8, fn, "input dimension must be in [1, 8]");
-    CIMRGP_REQUIRE(q >= 1 && q <= 8, fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
+    CIMRGP_REQUIRE(q >= 1 && q <= MAXQ, fn, "number of outputs must be in [1, 8]");
     const int64_t e = elems_per_16_bytes(dtype);
     CIMRGP_REQUIRE(ldk % e == 0 && k_stride % e == 0, fn, "leading dimensions and strides must be multiples of 16 bytes");
     CIMRGP_REQUIRE(block_stride_ok(k_stride, n, n, ldk), fn, "matrix stride too small");
@@ -680,14 +672,14 @@ int cimrgp_layer_lml_grad_cov(int dtype, int cov, const void* x_dev, const void*
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         LayerLml<T> a;
-        a.cov = cov;
-        a.x = (const T*)x_dev; a.y = (const T*)y_dev; a.fbar = (const T*)fbar_dev; a.starts = starts_dev;
-        a.batch = batch; a.n = n; a.d = d; a.q = q;
-        a.ell = ell; a.sf2 = sf2; a.noise = noise;
-        a.shared_bias = (const T*)shared_bias_dev;
-        a.k = (T*)k_arena_dev; a.ldk = ldk; a.sk = k_stride; a.kinv = (T*)kinv_arena_dev;
-        a.ws = (T*)ws_arena_dev; a.sws = (int64_t)(ws_stride_bytes / sizeof(T)); a.info = info_dev;
-        a.scratch = scratch_dev; a.out = out_dev;
+        FitFront<T>& fr = a.fr;
+        fr.bc = BatchCov{batch, d, cov, ell, sf2};
+        fr.tr = Points<T>{(const T*)x_dev, starts_dev, n};
+        fr.f = Factors<T>{{(T*)k_arena_dev, ldk, k_stride}, (T*)ws_arena_dev, (int64_t)(ws_stride_bytes / sizeof(T))};
+        fr.info = info_dev;
+        fr.y = (const T*)y_dev; fr.fbar = (const T*)fbar_dev; fr.q = q; fr.shared_bias = (const T*)shared_bias_dev;
+        fr.noise_fixed = noise;
+        a.kinv = (T*)kinv_arena_dev; a.scratch = scratch_dev; a.out = out_dev;
         return layer_lml_grad_run<T>(a, stream_of(stream));
     });
 }

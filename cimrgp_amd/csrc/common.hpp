@@ -23,6 +23,12 @@ int  check_hip(hipError_t e, const char* fn, const char* what);
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// The limits of every entry point: at most 8 input dimensions and 8 outputs (they size __shared__ and register arrays)
+constexpr int MAXD = 8;
+constexpr int MAXQ = 8;
+// Row pitch (elements) of the matrices the library lays out itself: device.padded_ld's rule (a multiple of 16, never of 512)
+static inline int64_t padded_ld(int64_t n) { const int64_t ld = (n + 15) / 16 * 16; return ld % 512 == 0 ? ld + 16 : ld; }
+
 // ------------------------------------------------------------ MFMA traits ----
 // 16x16x4 matrix-core tiles, one 8-byte "k-slot" per lane per operand:
 //   lane l supplies A[row = l & 15][kslot = l >> 4] and B^T[col = l & 15][kslot = l >> 4].
@@ -175,6 +181,20 @@ hipStream_t solve_queue_for(hipStream_t st);
 // (potrf.hip) the context's queue that falls idle before a factorisation on st ends: cimrgp_front_queue
 hipStream_t front_queue_for(hipStream_t st);
 
+// ------------------------------------------------ a layer's batch of blocks ----
+// The operands every per-layer call passes around (strides in elements).  U is T or const T.
+// `batch` matrices of pitch ld, `stride` apart
+template <typename U> struct Arena { U* p = nullptr; int64_t ld = 0, stride = 0; };
+// one side of a batch: block b is the n rows of x from row starts[b] (NULL: one block at row 0)
+template <typename T> struct Points { const T* x = nullptr; const int64_t* starts = nullptr; int64_t n = 0; };
+// what both sides share: the number of blocks, the input dimension and the covariance
+struct BatchCov { int batch = 1; int d = 0; int cov = CIMRGP_COV_RBF; double ell = 0, sf2 = 0; };
+// the blocks' Cholesky factors and the factorisation's workspaces (potrf.hip), sws apart
+template <typename U> struct Factors { Arena<U> l; U* ws = nullptr; int64_t sws = 0; };
+// where the inverted 256 x 256 diagonal panels start in a factorisation workspace: behind the ceil(n / 64) inverted
+// 64 x 64 blocks (potrf.hip, build_invT)
+static inline int64_t ws_invT_offset(int64_t n) { return (n + 63) / 64 * (64 * 64); }
+
 // --------------------------------------------------------- host launchers ----
 // block.hip: the three stages of cimrgp_block_posterior[_staged] on their streams, with the records of staged calls
 // in flight; staged_shutdown_ destroys those records' events (cimrgp_shutdown)
@@ -188,6 +208,8 @@ template <typename T> int potrf_run(T* k, int64_t n, int64_t ld, T* ws, int32_t*
                                     hipStream_t st, hipStream_t ready_on = nullptr);
 // `batch` equal-sized factorisations in the same launches (strides in elements / ints)
 struct PotrfBatch { int count = 1; int64_t sk = 0, sws = 0, sb = 0; };
+// `count` factors f with carried rows (or right-hand sides) sb apart
+template <typename U> static inline PotrfBatch potrf_batch(int count, const Factors<U>& f, int64_t sb) { return PotrfBatch{count, f.l.stride, f.sws, sb}; }
 template <typename T> int potrf_batched_run(T* k, int64_t n, int64_t ld, T* ws, int32_t* info, T* b, int64_t m, int64_t ldb,
                                             PotrfBatch bt, hipStream_t st);
 template <typename T> int solve_rows_run(const T* l, int64_t n, int64_t ld, const T* ws, T* b, int64_t m,
@@ -203,6 +225,7 @@ int profile_collect(double* total_ms, double* total_flops, int64_t* launches, do
 // pers: compute units for the persistent form of the update (-1: knobs().gemm_pers, 0: never)
 // head_first + flag: the look-ahead's combined head + bulk update as one persistent launch (gemm_nt.hip)
 struct GemmBatch { int count = 1; int64_t sc = 0, sa = 0, sb = 0; int skip_first = 0; int pers = -1; int head_first = 0; int* flag = nullptr; int pers_force = 0; };
+static inline GemmBatch gemm_batch(int count, int64_t sc, int64_t sa, int64_t sb) { GemmBatch g; g.count = count; g.sc = sc; g.sa = sa; g.sb = sb; return g; }
 bool gemm_uses_tile64(int64_t m, int64_t n, bool lower, int count = 1);
 int gemm_pers_head_tiles(int64_t m, int k, int elem_bytes);
 template <typename T> int gemm_nt_sub(T* c, int64_t ldc, const T* a, int64_t lda, const T* b, int64_t ldb,
@@ -284,9 +307,9 @@ template <> struct Cov<CIMRGP_COV_MATERN52> : MaternCov<CIMRGP_COV_MATERN52> {};
 template <typename T> int rbf_gram_run(const T* xa, int64_t na, const T* xb, int64_t nb, int d, double ell, double sf2,
                                        double diag_add, T* k, int64_t ld, bool symm, bool lower_only, hipStream_t st,
                                        int cov = CIMRGP_COV_RBF, const char* fn = nullptr);
-template <typename T> int rbf_gram_batched_run(const T* xa, const int64_t* a_starts, int64_t na, const T* xb, const int64_t* b_starts,
-                                               int64_t nb, int d, double ell, double sf2, const T* diag_dev, T* k, int64_t ld,
-                                               int64_t kstride, int batch, bool symm, hipStream_t st, int cov = CIMRGP_COV_RBF);
+// K_b = k(rows_b, cols_b) for every block b into arena k; symm: rows == cols, the lower tiles, + diag_dev[b] on the diagonal
+template <typename T> int rbf_gram_batched_run(const BatchCov& bc, const Points<T>& rows, const Points<T>& cols, const T* diag_dev,
+                                               const Arena<T>& k, bool symm, hipStream_t st);
 template <typename T> int predict_mean_run(const T* x, int64_t n, int d, const T* alpha, int q, const T* xs, int64_t ns,
                                            double ell, double sf2, const T* bias, T* mean, int accumulate, hipStream_t st,
                                            int cov = CIMRGP_COV_RBF, const char* fn = nullptr);
@@ -316,43 +339,45 @@ template <typename T> int lml_grad_batched_run(const T* x, const int64_t* starts
                                                double sf2, double noise, double* out, double* partial, hipStream_t st, int cov,
                                                const char* fn);
 
-// layer.hip: one call per layer for a batch of equal-sized blocks (strides in elements)
-template <typename T> struct LayerFit {
-    const T* x; const T* y; const T* fbar; T* train_out; const int64_t* starts;
-    int batch; int64_t n; int d; int q;
-    double ell, sf2, noise_fixed, noise_frac, noise_floor;
-    int cov = CIMRGP_COV_RBF;
-    const T* shared_bias; const T* shared_noise;
-    T* k; int64_t ldk, sk; T* ws; int64_t sws; int32_t* info;
-    T* rows; int64_t ldr, srows;
-    T* z; T* alpha; T* bias; T* noise; T* scratch;
+// layer.hip: one call per layer for a batch of equal-sized blocks
+// The fit front end (fit_front_run): statistics -> bias, noise | residual rows | Gram + noise | factorisation with the
+// rows carried | z | backward solve (alpha).  f.l holds the Gram matrices, then the factors.
+template <typename T> struct FitFront {
+    BatchCov bc; Points<T> tr; Factors<T> f; int32_t* info = nullptr;
+    const T* y = nullptr; const T* fbar = nullptr; int q = 0; const T* shared_bias = nullptr;
+    // noise[b]: the fixed value if >= 0, else the shared one if given, else max(frac var, floor)
+    double noise_fixed = 0, noise_frac = 0, noise_floor = 0; const T* shared_noise = nullptr;
+    Arena<T> rows; bool eye = false;     // the carried rows: q residual rows per block, then (eye) the n rows of the identity
+    T* z = nullptr; T* alpha = nullptr; T* work = nullptr; T* bias = nullptr; T* noise = nullptr;   // work: potrs_run's scratch
 };
+template <typename T> struct LayerFit { FitFront<T> fr; T* train_out = nullptr; };
 template <typename T> int layer_fit_run(const LayerFit<T>& a, hipStream_t st);
+// W_b = K(tests_b, train_b) L_b^-T into arena w: the cross-Gram, then the row solve (predict, joint covariance, gradient)
+template <typename T> int cross_solve_run(const BatchCov& bc, const Points<T>& train, const Factors<const T>& f, const Points<T>& tests,
+                                          const Arena<T>& w, hipStream_t st);
 template <typename T> struct LayerPredict {
-    const T* x; const int64_t* starts; int64_t n; int d;
-    const T* xs; const int64_t* t_starts; int64_t ns; int batch;
-    double ell, sf2;
-    int cov = CIMRGP_COV_RBF;
-    const T* l; int64_t ldl, sl; const T* ws; int64_t sws;
-    const T* z; int q; const T* bias; const T* noise;
-    T* w; int64_t ldw, sw;
-    T* mean; T* var;
+    BatchCov bc; Points<T> tr; Factors<const T> f; Points<T> te;
+    const T* z = nullptr; int q = 0; const T* bias = nullptr; const T* noise = nullptr;
+    Arena<T> w; T* mean = nullptr; T* var = nullptr;
 };
 template <typename T> int layer_predict_run(const LayerPredict<T>& a, hipStream_t st);
+// joint.hip: c.l = the covariance blocks, factored in place with the workspaces c.ws when those are given
+template <typename T> struct LayerJoint {
+    BatchCov bc; Points<T> tr; Factors<const T> f; Points<T> te;
+    const T* diag = nullptr; Arena<T> w; Factors<T> c; int32_t* info = nullptr;
+};
+// grad.hip: alpha_b at alpha + b sa; w: the work area of the layer call (its beta), or the caller's beta (single block)
+template <typename T> struct LayerGrad {
+    BatchCov bc; Points<T> tr; Factors<const T> f; Points<T> te;
+    const T* alpha = nullptr; int64_t sa = 0; int q = 0; Arena<T> w; T* mg = nullptr; T* vg = nullptr; int accumulate = 0;
+};
 // log marginal likelihood + gradient of a batch of blocks (cimrgp_layer_lml_grad_cov); the scratch holds the carried
 // rows (q residual rows + the identity, per block), z, alpha, the backward solve's work area, bias, noise and the
-// gradient's tile records, at the byte offsets of lml_scratch_layout
+// gradient's tile records, at the byte offsets of lml_scratch_layout: layer_lml_grad_run points fr's rows, z, alpha,
+// work, bias and noise there (fr.noise_fixed is the call's noise)
 struct LmlScratch { int64_t ldr = 0, srows = 0; size_t rows = 0, z = 0, alpha = 0, work = 0, bias = 0, noise = 0, partial = 0, total = 0; };
 LmlScratch lml_scratch_layout(size_t esz, int64_t n, int q, int batch);
-template <typename T> struct LayerLml {
-    const T* x; const T* y; const T* fbar; const int64_t* starts;
-    int batch; int64_t n; int d; int q;
-    double ell, sf2, noise;
-    int cov = CIMRGP_COV_RBF;
-    const T* shared_bias;
-    T* k; int64_t ldk, sk; T* kinv; T* ws; int64_t sws; int32_t* info;
-    void* scratch; double* out;
-};
+template <typename T> struct LayerLml { FitFront<T> fr; T* kinv = nullptr; void* scratch = nullptr; double* out = nullptr; };
 template <typename T> int layer_lml_grad_run(const LayerLml<T>& a, hipStream_t st);
 
 // reduced.hip

@@ -7,16 +7,13 @@
 //                  both on the matrix cores (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32, Mx<T> in common.hpp)
 //   predict_grad   k_cov_predict_grad: g(r) recomputed per (test point, training point) pair, both contractions in one
 //                  pass over the pairs; the cross-covariance and its derivative are never stored
-//   layer_grad     per block: the batched cross-Gram and forward row solve (as cimrgp_layer_predict), the batched
+//   layer_grad     per block: the shared cross-Gram and forward row solve (cross_solve_run, layer.hip), the batched
 //                  backward row solve above, then the batched contraction
 #include "abi.hpp"
 
 namespace cimrgp {
 
 namespace {
-
-constexpr int GR_MAXD = 8;
-constexpr int GR_MAXQ = 8;
 
 // ---------------------------------------------------------------- B_p <- B_p inv(L_pp) ----
 // One workgroup = 16 rows of B and the whole panel (w <= 256 columns): the strip is read into LDS before anything is
@@ -196,7 +193,7 @@ void k_cov_predict_grad(const T* __restrict__ x, const int64_t* __restrict__ sta
                         const T* __restrict__ beta, int64_t ldb, int64_t sbeta, T* __restrict__ mg, T* __restrict__ vg,
                         int accumulate)
 {
-    constexpr int DD = D ? D : GR_MAXD;
+    constexpr int DD = D ? D : MAXD;
     const int64_t b = blockIdx.y;
     const int64_t xoff = starts ? starts[b] : 0;
     const int64_t toff = t_starts ? t_starts[b] : 0;
@@ -287,8 +284,8 @@ static int rows_lt_run(const T* l, int64_t n, int64_t ldl, const T* ws, T* b, in
                        const char* fn)
 {
     if (n <= 0 || m <= 0) return 0;
-    const int64_t nslab = (n + 63) / 64, npan = (n + CIMRGP_NB - 1) / CIMRGP_NB;
-    const T* invT = ws + nslab * 64 * 64;
+    const int64_t npan = (n + CIMRGP_NB - 1) / CIMRGP_NB;
+    const T* invT = ws + ws_invT_offset(n);
     const int64_t strips = (m + 15) / 16, tiles_m = (m + UP_T - 1) / UP_T;
     CIMRGP_REQUIRE(strips < (1ll << 31) && tiles_m * (n / UP_T + 1) < (1ll << 31), fn, "grid too large");
     for (int64_t p = npan - 1; p >= 0; --p) {
@@ -306,22 +303,22 @@ static int rows_lt_run(const T* l, int64_t n, int64_t ldl, const T* ws, T* b, in
     return 0;
 }
 
+// the contraction of a.bc.batch blocks; beta: a.w's arena with the rows of K(xs, x) K^-1, or NULL (no variance gradient)
 template <typename T, int COV>
-static int predict_grad_run_cov(const T* x, const int64_t* starts, int64_t n, int d, const T* alpha, int64_t sa, int q, const T* xs,
-                                const int64_t* t_starts, int64_t ns, int batch, double ell, double sf2, const T* beta, int64_t ldb,
-                                int64_t sbeta, T* mg, T* vg, int accumulate, hipStream_t st, const char* fn)
+static int predict_grad_run_cov(const LayerGrad<T>& a, const T* beta, hipStream_t st, const char* fn)
 {
-    if (ns <= 0 || (mg == nullptr && vg == nullptr)) return 0;
-    const dim3 grid((unsigned)((ns + PG_TS - 1) / PG_TS), (unsigned)batch);
-    const T c = (T)cov_scale(COV, ell);
-#define CIMRGP_PG_LAUNCH(D_, Q_)                                                                                         \
-    hipLaunchKernelGGL((k_cov_predict_grad<T, COV, D_, Q_>), grid, dim3(256), 0, st, x, starts, (int)n, d, alpha, sa, q, xs,   \
-                       t_starts, (int)ns, c, (T)sf2, beta, ldb, sbeta, mg, vg, accumulate)
+    if (a.te.n <= 0 || (a.mg == nullptr && a.vg == nullptr)) return 0;
+    const dim3 grid((unsigned)((a.te.n + PG_TS - 1) / PG_TS), (unsigned)a.bc.batch);
+    const int d = a.bc.d;
+    const T c = (T)cov_scale(COV, a.bc.ell);
+#define CIMRGP_PG_LAUNCH(D_, Q_)                                                                                             \
+    hipLaunchKernelGGL((k_cov_predict_grad<T, COV, D_, Q_>), grid, dim3(256), 0, st, a.tr.x, a.tr.starts, (int)a.tr.n, d, a.alpha, \
+                       a.sa, a.q, a.te.x, a.te.starts, (int)a.te.n, c, (T)a.bc.sf2, beta, a.w.ld, a.w.stride, a.mg, a.vg, a.accumulate)
 #define CIMRGP_PG_D(Q_)                             \
     { if (d == 1)      CIMRGP_PG_LAUNCH(1, Q_);     \
       else if (d == 2) CIMRGP_PG_LAUNCH(2, Q_);     \
       else             CIMRGP_PG_LAUNCH(0, Q_); }
-    switch (q) {
+    switch (a.q) {
         case 1: CIMRGP_PG_D(1); break;
         case 2: CIMRGP_PG_D(2); break;
         case 3: CIMRGP_PG_D(3); break;
@@ -335,39 +332,24 @@ static int predict_grad_run_cov(const T* x, const int64_t* starts, int64_t n, in
 }
 
 template <typename T>
-static int predict_grad_run(int cov, const T* x, const int64_t* starts, int64_t n, int d, const T* alpha, int64_t sa, int q, const T* xs,
-                            const int64_t* t_starts, int64_t ns, int batch, double ell, double sf2, const T* beta, int64_t ldb,
-                            int64_t sbeta, T* mg, T* vg, int accumulate, hipStream_t st, const char* fn)
+static int predict_grad_run(const LayerGrad<T>& a, const T* beta, hipStream_t st, const char* fn)
 {
-    return with_cov(cov, [&](auto cv) {
-        return predict_grad_run_cov<T, decltype(cv)::value>(x, starts, n, d, alpha, sa, q, xs, t_starts, ns, batch, ell, sf2, beta, ldb,
-                                                             sbeta, mg, vg, accumulate, st, fn);
-    });
+    return with_cov(a.bc.cov, [&](auto cv) { return predict_grad_run_cov<T, decltype(cv)::value>(a, beta, st, fn); });
 }
 
 template <typename T>
-static int layer_grad_run(int cov, const T* x, const int64_t* starts, int64_t n, int d, const T* xs, const int64_t* t_starts, int64_t ns,
-                          int batch, double ell, double sf2, const T* l, int64_t ldl, int64_t sl, const T* ws, int64_t sws,
-                          const T* alpha, int q, T* w, int64_t ldw, int64_t sw, T* mg, T* vg, int accumulate, hipStream_t st)
+static int layer_grad_run(const LayerGrad<T>& a, hipStream_t st)
 {
     const char* fn = "cimrgp_layer_predict_grad_cov";
-    if (ns <= 0 || (mg == nullptr && vg == nullptr)) return 0;
-    if (vg != nullptr) {
-        // W_b = K(xs_b, x_b) L_b^-T (layer_predict_run's first two steps), then beta_b = W_b L_b^-1
-        int rc = rbf_gram_batched_run<T>(xs, t_starts, ns, x, starts, n, d, ell, sf2, (const T*)nullptr, w, ldw, sw, batch, false, st, cov);
+    if (a.te.n <= 0 || (a.mg == nullptr && a.vg == nullptr)) return 0;
+    if (a.vg != nullptr) {
+        // W_b = K(xs_b, x_b) L_b^-T, then beta_b = W_b L_b^-1
+        int rc = cross_solve_run<T>(a.bc, a.tr, a.f, a.te, a.w, st);
         if (rc) return rc;
-        PotrfBatch bt;
-        bt.count = batch;
-        bt.sk = sl;
-        bt.sws = sws;
-        bt.sb = sw;
-        rc = solve_rows_run<T>(l, n, ldl, ws, w, ns, ldw, st, bt);
-        if (rc) return rc;
-        rc = rows_lt_run<T>(l, n, ldl, ws, w, ns, ldw, st, bt, fn);
+        rc = rows_lt_run<T>(a.f.l.p, a.tr.n, a.f.l.ld, a.f.ws, a.w.p, a.te.n, a.w.ld, st, potrf_batch(a.bc.batch, a.f, a.w.stride), fn);
         if (rc) return rc;
     }
-    return predict_grad_run<T>(cov, x, starts, n, d, alpha, n * q, q, xs, t_starts, ns, batch, ell, sf2, vg ? w : nullptr, ldw, sw, mg,
-                               vg, accumulate, st, fn);
+    return predict_grad_run<T>(a, a.vg ? (const T*)a.w.p : nullptr, st, fn);
 }
 
 }  // namespace cimrgp
@@ -393,11 +375,7 @@ int cimrgp_trsm_rows_lt_batched(int dtype, const void* l_dev, int64_t n, int64_t
     CIMRGP_REQUIRE(workspace_stride_bytes >= cimrgp_potrf_workspace_bytes(dtype, n) || batch == 1, fn, "workspace stride too small");
     CIMRGP_REQUIRE(workspace_stride_bytes % 16 == 0 || batch == 1, fn, "workspace stride must be a multiple of 16 bytes");
     CIMRGP_REQUIRE(batch == 1 || m == 0 || b_stride >= (m - 1) * ldb + n, fn, "block stride too small");
-    PotrfBatch bt;
-    bt.count = batch;
-    bt.sk = l_stride;
-    bt.sws = (int64_t)(workspace_stride_bytes / elem_bytes(dtype));
-    bt.sb = b_stride;
+    const PotrfBatch bt{batch, l_stride, (int64_t)(workspace_stride_bytes / elem_bytes(dtype)), b_stride};
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         return rows_lt_run<T>((const T*)l_dev, n, ldl, (const T*)workspace_dev, (T*)b_dev, m, ldb, stream_of(stream), bt, fn);
@@ -421,14 +399,20 @@ int cimrgp_cov_predict_grad(int dtype, int cov, const void* x_dev, int64_t n, in
     CIMRGP_REQUIRE(mean_grad_dev == nullptr || alpha_dev != nullptr, fn, "null pointer (alpha)");
     CIMRGP_REQUIRE(var_grad_dev == nullptr || beta_dev != nullptr, fn, "null pointer (beta)");
     CIMRGP_REQUIRE(n >= 1 && n < (1ll << 31) && ns >= 0 && ns < (1ll << 31), fn, "bad dimensions");
-    CIMRGP_REQUIRE(d >= 1 && d <= GR_MAXD, fn, "input dimension must be in [1, 8]");
-    CIMRGP_REQUIRE(q >= 1 && q <= GR_MAXQ, fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
+    CIMRGP_REQUIRE(q >= 1 && q <= MAXQ, fn, "number of outputs must be in [1, 8]");
     CIMRGP_REQUIRE(ell > 0.0 && sf2 > 0.0, fn, "kernel parameters must be positive");
     CIMRGP_REQUIRE(var_grad_dev == nullptr || ldb >= n, fn, "leading dimension of beta smaller than n");
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
-        return predict_grad_run<T>(cov, (const T*)x_dev, nullptr, n, d, (const T*)alpha_dev, 0, q, (const T*)xs_dev, nullptr, ns, 1, ell,
-                                   sf2, (const T*)beta_dev, ldb, 0, (T*)mean_grad_dev, (T*)var_grad_dev, accumulate, stream_of(stream), fn);
+        LayerGrad<T> a;
+        a.bc = BatchCov{1, d, cov, ell, sf2};
+        a.tr = Points<T>{(const T*)x_dev, nullptr, n};
+        a.te = Points<T>{(const T*)xs_dev, nullptr, ns};
+        a.alpha = (const T*)alpha_dev; a.q = q;
+        a.w.ld = ldb;
+        a.mg = (T*)mean_grad_dev; a.vg = (T*)var_grad_dev; a.accumulate = accumulate;
+        return predict_grad_run<T>(a, (const T*)beta_dev, stream_of(stream), fn);
     });
 }
 
@@ -445,8 +429,8 @@ int cimrgp_layer_predict_grad_cov(int dtype, int cov, const void* x_dev, const i
     CIMRGP_REQUIRE(var_grad_dev == nullptr || (l_arena_dev && ws_arena_dev && w_arena_dev), fn, "null pointer (factor, workspace or W)");
     CIMRGP_REQUIRE(batch >= 1 && batch < 65536, fn, "batch count out of range");
     CIMRGP_REQUIRE(n >= 1 && n < (1ll << 30) && ns >= 0 && ns < (1ll << 30), fn, "bad dimensions");
-    CIMRGP_REQUIRE(d >= 1 && d <= GR_MAXD, fn, "input dimension must be in [1, 8]");
-    CIMRGP_REQUIRE(q >= 1 && q <= GR_MAXQ, fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
+    CIMRGP_REQUIRE(q >= 1 && q <= MAXQ, fn, "number of outputs must be in [1, 8]");
     CIMRGP_REQUIRE(ell > 0.0 && sf2 > 0.0, fn, "kernel parameters must be positive");
     if (var_grad_dev != nullptr) {
         CIMRGP_REQUIRE(ldl >= n && ldw >= n, fn, "leading dimension too small");
@@ -461,10 +445,15 @@ int cimrgp_layer_predict_grad_cov(int dtype, int cov, const void* x_dev, const i
     }
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
-        return layer_grad_run<T>(cov, (const T*)x_dev, starts_dev, n, d, (const T*)xs_dev, t_starts_dev, ns, batch, ell, sf2,
-                                 (const T*)l_arena_dev, ldl, l_stride, (const T*)ws_arena_dev, (int64_t)(ws_stride_bytes / sizeof(T)),
-                                 (const T*)alpha_dev, q, (T*)w_arena_dev, ldw, w_stride, (T*)mean_grad_dev, (T*)var_grad_dev, accumulate,
-                                 stream_of(stream));
+        LayerGrad<T> a;
+        a.bc = BatchCov{batch, d, cov, ell, sf2};
+        a.tr = Points<T>{(const T*)x_dev, starts_dev, n};
+        a.te = Points<T>{(const T*)xs_dev, t_starts_dev, ns};
+        a.f = Factors<const T>{{(const T*)l_arena_dev, ldl, l_stride}, (const T*)ws_arena_dev, (int64_t)(ws_stride_bytes / sizeof(T))};
+        a.alpha = (const T*)alpha_dev; a.sa = n * q; a.q = q;
+        a.w = Arena<T>{(T*)w_arena_dev, ldw, w_stride};
+        a.mg = (T*)mean_grad_dev; a.vg = (T*)var_grad_dev; a.accumulate = accumulate;
+        return layer_grad_run<T>(a, stream_of(stream));
     });
 }
 

@@ -15,7 +15,6 @@ namespace cimrgp {
 namespace {
 
 constexpr int GTILE = 64;
-constexpr int MAXD  = 8;
 
 // D = compile-time input dimension (1, 2) or 0 = run-time d <= 8 with fully
 // unrolled, predicated loops (run-time indexed register arrays would spill).
@@ -245,7 +244,6 @@ void k_cov_gram_batched(const T* __restrict__ xa, const int64_t* __restrict__ a_
 // reduction, no atomics).
 constexpr int PM_TS = 8;
 constexpr int PM_PH = 32;
-constexpr int MAXQ  = 8;
 
 // Q = number of outputs at compile time (a run-time guard inside the loop serialises the loads).
 template <typename T, int D, int Q>
@@ -427,23 +425,24 @@ int rbf_gram_run(const T* xa, int64_t na, const T* xb, int64_t nb, int d, double
 }
 
 template <typename T, int COV>
-static int gram_batched_run_cov(const T* xa, const int64_t* a_starts, int64_t na, const T* xb, const int64_t* b_starts, int64_t nb,
-                                int d, double ell, double sf2, const T* diag_dev, T* k, int64_t ld, int64_t kstride, int batch,
+static int gram_batched_run_cov(const BatchCov& bc, const Points<T>& rows, const Points<T>& cols, const T* diag_dev, const Arena<T>& k,
                                 bool symm, hipStream_t st)
 {
     const char* fn = "cimrgp_layer";
-    if (na <= 0 || nb <= 0 || batch <= 0) return 0;
+    const int64_t na = rows.n, nb = cols.n;
+    const int d = bc.d;
+    if (na <= 0 || nb <= 0 || bc.batch <= 0) return 0;
     CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
-    CIMRGP_REQUIRE(ell > 0.0, fn, "length-scale must be positive");
-    CIMRGP_REQUIRE(ld >= nb, fn, "leading dimension smaller than the number of columns");
-    CIMRGP_REQUIRE(na < (1ll << 30) && nb < (1ll << 30) && batch < 65536, fn, "batch too large");
+    CIMRGP_REQUIRE(bc.ell > 0.0, fn, "length-scale must be positive");
+    CIMRGP_REQUIRE(k.ld >= nb, fn, "leading dimension smaller than the number of columns");
+    CIMRGP_REQUIRE(na < (1ll << 30) && nb < (1ll << 30) && bc.batch < 65536, fn, "batch too large");
     const int64_t tm = (na + GTILE - 1) / GTILE, tn = (nb + GTILE - 1) / GTILE;
     const int64_t tiles = symm ? tm * (tm + 1) / 2 : tm * tn;
     CIMRGP_REQUIRE(tiles < (1ll << 31), fn, "grid too large");
-    const T c = (T)cov_scale(COV, ell);
+    const T c = (T)cov_scale(COV, bc.ell);
 #define CIMRGP_GRAMB_LAUNCH(SYMM_, D_)                                                                      \
-    hipLaunchKernelGGL((gram_batched_kernel<T, COV, SYMM_, D_>()), dim3((unsigned)tiles, (unsigned)batch), dim3(256), 0, st, \
-                       xa, a_starts, (int)na, xb, b_starts, (int)nb, d, c, (T)sf2, diag_dev, k, ld, kstride, (int)tn, symm ? 1 : 0)
+    hipLaunchKernelGGL((gram_batched_kernel<T, COV, SYMM_, D_>()), dim3((unsigned)tiles, (unsigned)bc.batch), dim3(256), 0, st, \
+                       rows.x, rows.starts, (int)na, cols.x, cols.starts, (int)nb, d, c, (T)bc.sf2, diag_dev, k.p, k.ld, k.stride, (int)tn, symm ? 1 : 0)
     if (symm) { if (d == 1) CIMRGP_GRAMB_LAUNCH(true, 1); else if (d == 2) CIMRGP_GRAMB_LAUNCH(true, 2); else CIMRGP_GRAMB_LAUNCH(true, 0); }
     else      { if (d == 1) CIMRGP_GRAMB_LAUNCH(false, 1); else if (d == 2) CIMRGP_GRAMB_LAUNCH(false, 2); else CIMRGP_GRAMB_LAUNCH(false, 0); }
 #undef CIMRGP_GRAMB_LAUNCH
@@ -452,14 +451,10 @@ static int gram_batched_run_cov(const T* xa, const int64_t* a_starts, int64_t na
 }
 
 template <typename T>
-int rbf_gram_batched_run(const T* xa, const int64_t* a_starts, int64_t na, const T* xb, const int64_t* b_starts, int64_t nb,
-                         int d, double ell, double sf2, const T* diag_dev, T* k, int64_t ld, int64_t kstride, int batch,
-                         bool symm, hipStream_t st, int cov)
+int rbf_gram_batched_run(const BatchCov& bc, const Points<T>& rows, const Points<T>& cols, const T* diag_dev, const Arena<T>& k, bool symm,
+                         hipStream_t st)
 {
-    return with_cov(cov, [&](auto c) {
-        return gram_batched_run_cov<T, decltype(c)::value>(xa, a_starts, na, xb, b_starts, nb, d, ell, sf2, diag_dev, k, ld, kstride,
-                                                           batch, symm, st);
-    });
+    return with_cov(bc.cov, [&](auto c) { return gram_batched_run_cov<T, decltype(c)::value>(bc, rows, cols, diag_dev, k, symm, st); });
 }
 
 template <typename T, int COV>
@@ -509,10 +504,10 @@ template int rbf_gram_run<double>(const double*, int64_t, const double*, int64_t
                                   double*, int64_t, bool, bool, hipStream_t, int, const char*);
 template int rbf_gram_run<float>(const float*, int64_t, const float*, int64_t, int, double, double, double,
                                  float*, int64_t, bool, bool, hipStream_t, int, const char*);
-template int rbf_gram_batched_run<double>(const double*, const int64_t*, int64_t, const double*, const int64_t*, int64_t, int,
-                                          double, double, const double*, double*, int64_t, int64_t, int, bool, hipStream_t, int);
-template int rbf_gram_batched_run<float>(const float*, const int64_t*, int64_t, const float*, const int64_t*, int64_t, int,
-                                         double, double, const float*, float*, int64_t, int64_t, int, bool, hipStream_t, int);
+template int rbf_gram_batched_run<double>(const BatchCov&, const Points<double>&, const Points<double>&, const double*,
+                                          const Arena<double>&, bool, hipStream_t);
+template int rbf_gram_batched_run<float>(const BatchCov&, const Points<float>&, const Points<float>&, const float*,
+                                         const Arena<float>&, bool, hipStream_t);
 template int predict_mean_run<double>(const double*, int64_t, int, const double*, int, const double*, int64_t,
                                       double, double, const double*, double*, int, hipStream_t, int, const char*);
 template int predict_mean_run<float>(const float*, int64_t, int, const float*, int, const float*, int64_t,

@@ -1,8 +1,8 @@
 // The joint predictive distribution of a layer's blocks (include/cimrgp_joint.h):
 //   normal_fill   counter-based standard normals (Philox4x32-10 + Box-Muller), one value per (seed, key, column, point)
-//   joint_cov     K(xs, xs) + diag - W W^T, W = K(xs, x) L^-T: the batched Gram, the cross-Gram and row solve of
-//                 layer_predict_run, the batched lower update (gemm_nt_sub as a SYRK), optionally the batched
-//                 factorisation and a zeroed strict upper triangle
+//   joint_cov     K(xs, xs) + diag - W W^T, W = K(xs, x) L^-T: the batched Gram, the shared cross-Gram and row solve
+//                 (cross_solve_run, layer.hip), the batched lower update (gemm_nt_sub as a SYRK), optionally the
+//                 batched factorisation and a zeroed strict upper triangle
 //   layer_sample  out^T += Z^T L^T per block: k_layer_sample, gemm_tile's body with a positive sign, B read as lower
 //                 triangular and K cut at the last row of each column tile (tiles above the diagonal are never
 //                 computed: ns^2 cols flops instead of 2 ns^2 cols)
@@ -122,42 +122,27 @@ static int normal_fill_run(uint64_t seed, const uint64_t* keys, int batch, int64
 }
 
 template <typename T>
-static int joint_cov_run(int cov, const T* x, const int64_t* starts, int64_t n, int d, const T* xs, const int64_t* t_starts, int64_t ns,
-                         int batch, double ell, double sf2, const T* l, int64_t ldl, int64_t sl, const T* ws, int64_t sws,
-                         const T* diag, T* w, int64_t ldw, int64_t sw, T* c, int64_t ldc, int64_t sc, T* cws, int64_t scws,
-                         int32_t* info, hipStream_t st)
+static int joint_cov_run(const LayerJoint<T>& a, hipStream_t st)
 {
     const char* fn = "cimrgp_layer_joint_cov";
+    const int64_t ns = a.te.n;
+    const Arena<T>& c = a.c.l;
     if (ns <= 0) return 0;
     // lower(C_b) = K(xs_b, xs_b) + diag_b I
-    int rc = rbf_gram_batched_run<T>(xs, t_starts, ns, xs, t_starts, ns, d, ell, sf2, diag, c, ldc, sc, batch, true, st, cov);
+    int rc = rbf_gram_batched_run<T>(a.bc, a.te, a.te, a.diag, c, true, st);
     if (rc) return rc;
-    // W_b = K(xs_b, x_b) L_b^-T (layer_predict_run's first two steps)
-    rc = rbf_gram_batched_run<T>(xs, t_starts, ns, x, starts, n, d, ell, sf2, (const T*)nullptr, w, ldw, sw, batch, false, st, cov);
-    if (rc) return rc;
-    PotrfBatch bt;
-    bt.count = batch;
-    bt.sk = sl;
-    bt.sws = sws;
-    bt.sb = sw;
-    rc = solve_rows_run<T>(l, n, ldl, ws, w, ns, ldw, st, bt);
+    // W_b = K(xs_b, x_b) L_b^-T
+    rc = cross_solve_run<T>(a.bc, a.tr, a.f, a.te, a.w, st);
     if (rc) return rc;
     // lower(C_b) -= W_b W_b^T
-    GemmBatch gb;
-    gb.count = batch;
-    gb.sc = sc;
-    gb.sa = gb.sb = sw;
-    rc = gemm_nt_sub<T>(c, ldc, w, ldw, w, ldw, ns, ns, (int)n, true, st, gb);
+    rc = gemm_nt_sub<T>(c.p, c.ld, a.w.p, a.w.ld, a.w.p, a.w.ld, ns, ns, (int)a.tr.n, true, st,
+                        gemm_batch(a.bc.batch, c.stride, a.w.stride, a.w.stride));
     if (rc) return rc;
-    if (cws == nullptr) return 0;
-    PotrfBatch ft;
-    ft.count = batch;
-    ft.sk = sc;
-    ft.sws = scws;
-    rc = potrf_batched_run<T>(c, ns, ldc, cws, info, (T*)nullptr, 0, 0, ft, st);
+    if (a.c.ws == nullptr) return 0;
+    rc = potrf_batched_run<T>(c.p, ns, c.ld, a.c.ws, a.info, (T*)nullptr, 0, 0, potrf_batch(a.bc.batch, a.c, 0), st);
     if (rc) return rc;
-    hipLaunchKernelGGL((k_joint_zero_upper<T>), dim3((unsigned)((ns * ns + 255) / 256), (unsigned)batch), dim3(256), 0, st, c, ldc, sc,
-                       ns);
+    hipLaunchKernelGGL((k_joint_zero_upper<T>), dim3((unsigned)((ns * ns + 255) / 256), (unsigned)a.bc.batch), dim3(256), 0, st, c.p,
+                       c.ld, c.stride, ns);
     CIMRGP_LAUNCH_CHECK(fn);
     return 0;
 }
@@ -214,7 +199,7 @@ int cimrgp_layer_joint_cov(int dtype, int cov, const void* x_dev, const int64_t*
     CIMRGP_REQUIRE(cws_arena_dev == nullptr || info_dev != nullptr, fn, "null pointer (info)");
     CIMRGP_REQUIRE(batch >= 1 && batch < 65536, fn, "batch count out of range");
     CIMRGP_REQUIRE(n >= 1 && n < (1ll << 30) && ns >= 0 && ns < (1ll << 30), fn, "bad dimensions");
-    CIMRGP_REQUIRE(d >= 1 && d <= 8, fn, "input dimension must be in [1, 8]");
+    CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
     CIMRGP_REQUIRE(ell > 0.0 && sf2 > 0.0, fn, "kernel parameters must be positive");
     CIMRGP_REQUIRE(ldl >= n && ldw >= n && ldc >= ns && ldc >= 1, fn, "leading dimension too small");
     const int64_t e = elems_per_16_bytes(dtype);
@@ -231,10 +216,16 @@ int cimrgp_layer_joint_cov(int dtype, int cov, const void* x_dev, const int64_t*
                    "factor workspace stride too small or misaligned");
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
-        return joint_cov_run<T>(cov, (const T*)x_dev, starts_dev, n, d, (const T*)xs_dev, t_starts_dev, ns, batch, ell, sf2,
-                                (const T*)l_arena_dev, ldl, l_stride, (const T*)ws_arena_dev, (int64_t)(ws_stride_bytes / sizeof(T)),
-                                (const T*)diag_dev, (T*)w_arena_dev, ldw, w_stride, (T*)c_arena_dev, ldc, c_stride,
-                                (T*)cws_arena_dev, (int64_t)(cws_stride_bytes / sizeof(T)), info_dev, stream_of(stream));
+        LayerJoint<T> a;
+        a.bc = BatchCov{batch, d, cov, ell, sf2};
+        a.tr = Points<T>{(const T*)x_dev, starts_dev, n};
+        a.te = Points<T>{(const T*)xs_dev, t_starts_dev, ns};
+        a.f = Factors<const T>{{(const T*)l_arena_dev, ldl, l_stride}, (const T*)ws_arena_dev, (int64_t)(ws_stride_bytes / sizeof(T))};
+        a.diag = (const T*)diag_dev;
+        a.w = Arena<T>{(T*)w_arena_dev, ldw, w_stride};
+        a.c = Factors<T>{{(T*)c_arena_dev, ldc, c_stride}, (T*)cws_arena_dev, (int64_t)(cws_stride_bytes / sizeof(T))};
+        a.info = info_dev;
+        return joint_cov_run<T>(a, stream_of(stream));
     });
 }
 

@@ -7,6 +7,9 @@
 //   fit      statistics -> bias, noise | residual rows | Gram + noise | factorisation with the residual
 //            rows carried (z = L^-1 r) | backward solve (alpha) | training-point prediction
 //   predict  cross-Gram | row-wise solve W = K* L^-T | mean = W z + bias, var = sf - sum W^2 (+ noise)
+// Two steps are shared: fit_front_run (everything of the fit up to alpha; also the front end of the log marginal
+// likelihood, with the identity among the carried rows) and cross_solve_run (predict's first two steps; also the W of the
+// joint covariance, joint.hip, and of the predictive gradient, grad.hip).
 // The Gram and cross-Gram take the layer's covariance policy (a.cov, CIMRGP_COV_*); k(0) = sf for every policy, so
 // the variance is the same expression for all of them.
 //
@@ -18,8 +21,6 @@
 namespace cimrgp {
 
 namespace {
-
-constexpr int LY_MAXQ = 8;
 
 template <typename T>
 static __device__ __forceinline__ T ly_block_sum(T v, T* red)
@@ -47,7 +48,7 @@ void k_layer_stats(const T* __restrict__ y, const T* __restrict__ fbar, const in
                    const T* __restrict__ shared_noise, T* __restrict__ bias, T* __restrict__ noise)
 {
     __shared__ T red[16];
-    __shared__ T smean[LY_MAXQ];
+    __shared__ T smean[MAXQ];
     const int b = blockIdx.x;
     const T* yb = y + starts[b] * q;
     const T* fb = fbar ? fbar + starts[b] * q : nullptr;
@@ -127,74 +128,6 @@ __global__ void k_layer_train_mean(const T* __restrict__ y, const T* __restrict_
 
 }  // namespace
 
-template <typename T>
-int layer_fit_run(const LayerFit<T>& a, hipStream_t st)
-{
-    const char* fn = "cimrgp_layer_fit";
-    CIMRGP_REQUIRE(a.batch >= 1 && a.batch < 65536, fn, "batch count out of range");
-    CIMRGP_REQUIRE(a.n > 0, fn, "empty blocks");
-    CIMRGP_REQUIRE(a.q >= 1 && a.q <= LY_MAXQ, fn, "number of outputs must be in [1, 8]");
-    const unsigned nb = (unsigned)a.batch;
-    const unsigned ge = (unsigned)((a.n * a.q + 255) / 256);
-    hipLaunchKernelGGL((k_layer_stats<T>), dim3(nb), dim3(1024), 0, st, a.y, a.fbar, a.starts, a.n, a.q,
-                       (T)a.noise_fixed, (T)a.noise_frac, (T)a.noise_floor, a.shared_bias, a.shared_noise, a.bias, a.noise);
-    CIMRGP_LAUNCH_CHECK(fn);
-    hipLaunchKernelGGL((k_layer_rows<T>), dim3(ge, nb), dim3(256), 0, st, a.y, a.fbar, a.starts, a.n, a.q,
-                       (const T*)a.bias, a.rows, a.ldr, a.srows);
-    CIMRGP_LAUNCH_CHECK(fn);
-    int rc = rbf_gram_batched_run<T>(a.x, a.starts, a.n, a.x, a.starts, a.n, a.d, a.ell, a.sf2, (const T*)a.noise, a.k, a.ldk,
-                                     a.sk, a.batch, true, st, a.cov);
-    if (rc) return rc;
-    PotrfBatch bt;
-    bt.count = a.batch;
-    bt.sk = a.sk;
-    bt.sws = a.sws;
-    bt.sb = a.srows;
-    rc = potrf_batched_run<T>(a.k, a.n, a.ldk, a.ws, a.info, a.rows, a.q, a.ldr, bt, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_layer_z<T>), dim3(ge, nb), dim3(256), 0, st, (const T*)a.rows, a.ldr, a.srows, a.n, a.q, a.z, a.alpha,
-                       a.scratch, 2 * (int64_t)a.q * a.n);
-    CIMRGP_LAUNCH_CHECK(fn);
-    rc = potrs_run<T>(a.k, a.n, a.ldk, a.ws, a.alpha, a.q, nullptr, a.scratch, true, st, bt, true);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_layer_train_mean<T>), dim3(ge, nb), dim3(256), 0, st, a.y, a.fbar, a.starts, a.n, a.q,
-                       (const T*)a.alpha, (const T*)a.noise, a.train_out);
-    CIMRGP_LAUNCH_CHECK(fn);
-    return 0;
-}
-
-template <typename T>
-int layer_predict_run(const LayerPredict<T>& a, hipStream_t st)
-{
-    const char* fn = "cimrgp_layer_predict";
-    CIMRGP_REQUIRE(a.batch >= 1 && a.batch < 65536, fn, "batch count out of range");
-    CIMRGP_REQUIRE(a.q >= 1 && a.q <= LY_MAXQ, fn, "number of outputs must be in [1, 8]");
-    if (a.ns <= 0 || a.n <= 0) return 0;
-    CIMRGP_REQUIRE(a.ldw >= a.n, fn, "leading dimension of W smaller than n");
-    // W_b = K(xs_b, x_b)
-    int rc = rbf_gram_batched_run<T>(a.xs, a.t_starts, a.ns, a.x, a.starts, a.n, a.d, a.ell, a.sf2, (const T*)nullptr, a.w, a.ldw,
-                                     a.sw, a.batch, false, st, a.cov);
-    if (rc) return rc;
-    // W_b <- W_b L_b^-T
-    PotrfBatch bt;
-    bt.count = a.batch;
-    bt.sk = a.sl;
-    bt.sws = a.sws;
-    bt.sb = a.sw;
-    rc = solve_rows_run<T>(a.l, a.n, a.ldl, a.ws, a.w, a.ns, a.ldw, st, bt);
-    if (rc) return rc;
-    // mean += W z + bias, var += sf - sum W^2 (+ noise)
-    return predict_from_w_run<T>((const T*)a.w, a.ns, a.n, a.ldw, a.z, a.q, a.sf2, 0.0, a.noise, a.bias, a.mean, a.var, 1, st,
-                                 a.batch, a.t_starts, a.sw);
-}
-
-// ---- log marginal likelihood and its gradient for a batch of blocks (cimrgp_layer_lml_grad_cov) ----
-//   statistics -> bias | residual rows r^T and the identity as q + n carried rows | Gram + noise | factorisation with
-//   the rows carried: z^T = r^T L^-T and U = L^-T come out of the same panel sweep | backward solve (alpha) |
-//   lower(K^-1) = U U^T (batched SYRK on the matrix cores) | gradient tiles + per-block finish (misc.hip)
-// K^-1 method (DESIGN.md): the identity rides through potrf_rows_batched as carried rows, then one batched SYRK: about
-// n^3 + n^3 flops per block on top of the factorisation, all in kernels the factorisation already uses.
-
 // rows[b][q + i][j] = (i == j): the identity below the q residual rows
 template <typename T>
 __global__ void k_layer_eye(T* __restrict__ rows, int64_t ldr, int64_t srows, int64_t n, int q)
@@ -205,6 +138,85 @@ __global__ void k_layer_eye(T* __restrict__ rows, int64_t ldr, int64_t srows, in
     const int64_t i = e / n, j = e - i * n;
     rows[b * srows + (q + i) * ldr + j] = (i == j) ? (T)1 : (T)0;
 }
+
+// The fit up to alpha, in the name of the entry point fn: bias, noise | carried rows (the residual, then the identity if
+// a.eye) | Gram + noise | factorisation with the rows carried | z, alpha0, work | backward solve
+template <typename T>
+static int fit_front_run(const FitFront<T>& a, hipStream_t st, const char* fn)
+{
+    const int64_t n = a.tr.n;
+    const unsigned nb = (unsigned)a.bc.batch;
+    const unsigned ge = (unsigned)((n * a.q + 255) / 256);
+    hipLaunchKernelGGL((k_layer_stats<T>), dim3(nb), dim3(1024), 0, st, a.y, a.fbar, a.tr.starts, n, a.q, (T)a.noise_fixed,
+                       (T)a.noise_frac, (T)a.noise_floor, a.shared_bias, a.shared_noise, a.bias, a.noise);
+    CIMRGP_LAUNCH_CHECK(fn);
+    hipLaunchKernelGGL((k_layer_rows<T>), dim3(ge, nb), dim3(256), 0, st, a.y, a.fbar, a.tr.starts, n, a.q, (const T*)a.bias,
+                       a.rows.p, a.rows.ld, a.rows.stride);
+    CIMRGP_LAUNCH_CHECK(fn);
+    if (a.eye) {
+        hipLaunchKernelGGL((k_layer_eye<T>), dim3((unsigned)((n * n + 255) / 256), nb), dim3(256), 0, st, a.rows.p, a.rows.ld,
+                           a.rows.stride, n, a.q);
+        CIMRGP_LAUNCH_CHECK(fn);
+    }
+    int rc = rbf_gram_batched_run<T>(a.bc, a.tr, a.tr, (const T*)a.noise, a.f.l, true, st);
+    if (rc) return rc;
+    const PotrfBatch bt = potrf_batch(a.bc.batch, a.f, a.rows.stride);
+    rc = potrf_batched_run<T>(a.f.l.p, n, a.f.l.ld, a.f.ws, a.info, a.rows.p, a.q + (a.eye ? n : 0), a.rows.ld, bt, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_layer_z<T>), dim3(ge, nb), dim3(256), 0, st, (const T*)a.rows.p, a.rows.ld, a.rows.stride, n, a.q, a.z,
+                       a.alpha, a.work, 2 * (int64_t)a.q * n);
+    CIMRGP_LAUNCH_CHECK(fn);
+    return potrs_run<T>(a.f.l.p, n, a.f.l.ld, a.f.ws, a.alpha, a.q, nullptr, a.work, true, st, bt, true);
+}
+
+template <typename T>
+int layer_fit_run(const LayerFit<T>& a, hipStream_t st)
+{
+    const char* fn = "cimrgp_layer_fit";
+    const FitFront<T>& fr = a.fr;
+    CIMRGP_REQUIRE(fr.bc.batch >= 1 && fr.bc.batch < 65536, fn, "batch count out of range");
+    CIMRGP_REQUIRE(fr.tr.n > 0, fn, "empty blocks");
+    CIMRGP_REQUIRE(fr.q >= 1 && fr.q <= MAXQ, fn, "number of outputs must be in [1, 8]");
+    const int rc = fit_front_run<T>(fr, st, fn);
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_layer_train_mean<T>), dim3((unsigned)((fr.tr.n * fr.q + 255) / 256), (unsigned)fr.bc.batch), dim3(256), 0, st,
+                       fr.y, fr.fbar, fr.tr.starts, fr.tr.n, fr.q, (const T*)fr.alpha, (const T*)fr.noise, a.train_out);
+    CIMRGP_LAUNCH_CHECK(fn);
+    return 0;
+}
+
+template <typename T>
+int cross_solve_run(const BatchCov& bc, const Points<T>& train, const Factors<const T>& f, const Points<T>& tests, const Arena<T>& w,
+                    hipStream_t st)
+{
+    // W_b = K(xs_b, x_b)
+    const int rc = rbf_gram_batched_run<T>(bc, tests, train, (const T*)nullptr, w, false, st);
+    if (rc) return rc;
+    // W_b <- W_b L_b^-T
+    return solve_rows_run<T>(f.l.p, train.n, f.l.ld, f.ws, w.p, tests.n, w.ld, st, potrf_batch(bc.batch, f, w.stride));
+}
+
+template <typename T>
+int layer_predict_run(const LayerPredict<T>& a, hipStream_t st)
+{
+    const char* fn = "cimrgp_layer_predict";
+    CIMRGP_REQUIRE(a.bc.batch >= 1 && a.bc.batch < 65536, fn, "batch count out of range");
+    CIMRGP_REQUIRE(a.q >= 1 && a.q <= MAXQ, fn, "number of outputs must be in [1, 8]");
+    if (a.te.n <= 0 || a.tr.n <= 0) return 0;
+    CIMRGP_REQUIRE(a.w.ld >= a.tr.n, fn, "leading dimension of W smaller than n");
+    const int rc = cross_solve_run<T>(a.bc, a.tr, a.f, a.te, a.w, st);
+    if (rc) return rc;
+    // mean += W z + bias, var += sf - sum W^2 (+ noise)
+    return predict_from_w_run<T>((const T*)a.w.p, a.te.n, a.tr.n, a.w.ld, a.z, a.q, a.bc.sf2, 0.0, a.noise, a.bias, a.mean, a.var, 1,
+                                 st, a.bc.batch, a.te.starts, a.w.stride);
+}
+
+// ---- log marginal likelihood and its gradient for a batch of blocks (cimrgp_layer_lml_grad_cov) ----
+//   statistics -> bias | residual rows r^T and the identity as q + n carried rows | Gram + noise | factorisation with
+//   the rows carried: z^T = r^T L^-T and U = L^-T come out of the same panel sweep | backward solve (alpha) |
+//   lower(K^-1) = U U^T (batched SYRK on the matrix cores) | gradient tiles + per-block finish (misc.hip)
+// K^-1 method (DESIGN.md): the identity rides through potrf_rows_batched as carried rows, then one batched SYRK: about
+// n^3 + n^3 flops per block on top of the factorisation, all in kernels the factorisation already uses.
 
 // k_b[0:n, 0:n] = 0 (the SYRK's C): the padding columns [n, ld) and the gaps between the blocks belong to the caller
 template <typename T>
@@ -231,8 +243,7 @@ __global__ void k_layer_neg_lower(T* __restrict__ k, int64_t ld, int64_t ks, int
 LmlScratch lml_scratch_layout(size_t esz, int64_t n, int q, int batch)
 {
     LmlScratch s;
-    s.ldr = (n + 15) / 16 * 16;
-    if (s.ldr % 512 == 0) s.ldr += 16;       // device.padded_ld's rule
+    s.ldr = padded_ld(n);                    // device.padded_ld's rule
     s.srows = (int64_t)(q + n) * s.ldr;
     auto seg = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
     const size_t nb = (size_t)batch;
@@ -252,57 +263,35 @@ template <typename T>
 int layer_lml_grad_run(const LayerLml<T>& a, hipStream_t st)
 {
     const char* fn = "cimrgp_layer_lml_grad_cov";
-    CIMRGP_REQUIRE(a.batch >= 1 && a.batch < 65536, fn, "batch count out of range");
-    CIMRGP_REQUIRE(a.n > 0 && a.n < (1ll << 30), fn, "bad dimensions");
-    CIMRGP_REQUIRE(a.q >= 1 && a.q <= LY_MAXQ, fn, "number of outputs must be in [1, 8]");
-    const LmlScratch sl = lml_scratch_layout(sizeof(T), a.n, a.q, a.batch);
+    FitFront<T> fr = a.fr;
+    const int64_t n = fr.tr.n;
+    CIMRGP_REQUIRE(fr.bc.batch >= 1 && fr.bc.batch < 65536, fn, "batch count out of range");
+    CIMRGP_REQUIRE(n > 0 && n < (1ll << 30), fn, "bad dimensions");
+    CIMRGP_REQUIRE(fr.q >= 1 && fr.q <= MAXQ, fn, "number of outputs must be in [1, 8]");
+    const LmlScratch sl = lml_scratch_layout(sizeof(T), n, fr.q, fr.bc.batch);
     char* base = (char*)a.scratch;
-    T* rows = (T*)(base + sl.rows);
-    T* z = (T*)(base + sl.z);
-    T* alpha = (T*)(base + sl.alpha);
-    T* work = (T*)(base + sl.work);
-    T* bias = (T*)(base + sl.bias);
-    T* noise = (T*)(base + sl.noise);
+    fr.rows = Arena<T>{(T*)(base + sl.rows), sl.ldr, sl.srows};
+    fr.eye = true;
+    fr.z = (T*)(base + sl.z);
+    fr.alpha = (T*)(base + sl.alpha);
+    fr.work = (T*)(base + sl.work);
+    fr.bias = (T*)(base + sl.bias);
+    fr.noise = (T*)(base + sl.noise);
     double* partial = (double*)(base + sl.partial);
-    const unsigned nb = (unsigned)a.batch;
-    const unsigned ge = (unsigned)((a.n * a.q + 255) / 256);
-    const unsigned gn = (unsigned)((a.n * a.n + 255) / 256);
-    hipLaunchKernelGGL((k_layer_stats<T>), dim3(nb), dim3(1024), 0, st, a.y, a.fbar, a.starts, a.n, a.q, (T)a.noise, (T)0, (T)0,
-                       a.shared_bias, (const T*)nullptr, bias, noise);
-    CIMRGP_LAUNCH_CHECK(fn);
-    hipLaunchKernelGGL((k_layer_rows<T>), dim3(ge, nb), dim3(256), 0, st, a.y, a.fbar, a.starts, a.n, a.q, (const T*)bias, rows,
-                       sl.ldr, sl.srows);
-    CIMRGP_LAUNCH_CHECK(fn);
-    hipLaunchKernelGGL((k_layer_eye<T>), dim3(gn, nb), dim3(256), 0, st, rows, sl.ldr, sl.srows, a.n, a.q);
-    CIMRGP_LAUNCH_CHECK(fn);
-    int rc = rbf_gram_batched_run<T>(a.x, a.starts, a.n, a.x, a.starts, a.n, a.d, a.ell, a.sf2, (const T*)noise, a.k, a.ldk, a.sk,
-                                     a.batch, true, st, a.cov);
+    int rc = fit_front_run<T>(fr, st, fn);
     if (rc) return rc;
-    PotrfBatch bt;
-    bt.count = a.batch;
-    bt.sk = a.sk;
-    bt.sws = a.sws;
-    bt.sb = sl.srows;
-    rc = potrf_batched_run<T>(a.k, a.n, a.ldk, a.ws, a.info, rows, a.q + a.n, sl.ldr, bt, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_layer_z<T>), dim3(ge, nb), dim3(256), 0, st, (const T*)rows, sl.ldr, sl.srows, a.n, a.q, z, alpha, work,
-                       2 * (int64_t)a.q * a.n);
+    const Arena<T>& k = fr.f.l;
+    const dim3 grid((unsigned)((n * n + 255) / 256), (unsigned)fr.bc.batch);
+    hipLaunchKernelGGL((k_layer_zero<T>), grid, dim3(256), 0, st, a.kinv, k.ld, k.stride, n);
     CIMRGP_LAUNCH_CHECK(fn);
-    rc = potrs_run<T>(a.k, a.n, a.ldk, a.ws, alpha, a.q, nullptr, work, true, st, bt, true);
+    const T* u = fr.rows.p + (int64_t)fr.q * sl.ldr;
+    rc = gemm_nt_sub<T>(a.kinv, k.ld, u, sl.ldr, u, sl.ldr, n, n, (int)n, true, st, gemm_batch(fr.bc.batch, k.stride, sl.srows, sl.srows));
     if (rc) return rc;
-    hipLaunchKernelGGL((k_layer_zero<T>), dim3(gn, nb), dim3(256), 0, st, a.kinv, a.ldk, a.sk, a.n);
+    hipLaunchKernelGGL((k_layer_neg_lower<T>), grid, dim3(256), 0, st, a.kinv, k.ld, k.stride, n);
     CIMRGP_LAUNCH_CHECK(fn);
-    GemmBatch gb;
-    gb.count = a.batch;
-    gb.sc = a.sk;
-    gb.sa = gb.sb = sl.srows;
-    const T* u = rows + (int64_t)a.q * sl.ldr;
-    rc = gemm_nt_sub<T>(a.kinv, a.ldk, u, sl.ldr, u, sl.ldr, a.n, a.n, (int)a.n, true, st, gb);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_layer_neg_lower<T>), dim3(gn, nb), dim3(256), 0, st, a.kinv, a.ldk, a.sk, a.n);
-    CIMRGP_LAUNCH_CHECK(fn);
-    return lml_grad_batched_run<T>(a.x, a.starts, a.batch, a.n, a.d, (const T*)a.kinv, a.ldk, a.sk, (const T*)a.k, (const T*)alpha,
-                                   (const T*)z, a.q, a.ell, a.sf2, a.noise, a.out, partial, st, a.cov, fn);
+    return lml_grad_batched_run<T>(fr.tr.x, fr.tr.starts, fr.bc.batch, n, fr.bc.d, (const T*)a.kinv, k.ld, k.stride, (const T*)k.p,
+                                   (const T*)fr.alpha, (const T*)fr.z, fr.q, fr.bc.ell, fr.bc.sf2, fr.noise_fixed, a.out, partial, st,
+                                   fr.bc.cov, fn);
 }
 
 // The targets of ONE block as carried rows and back (cimrgp_block_posterior).
@@ -341,6 +330,10 @@ template int rows_to_z_run<double>(const double*, int64_t, int64_t, int, double*
 template int rows_to_z_run<float>(const float*, int64_t, int64_t, int, float*, float*, hipStream_t, float*);
 template int layer_fit_run<double>(const LayerFit<double>&, hipStream_t);
 template int layer_fit_run<float>(const LayerFit<float>&, hipStream_t);
+template int cross_solve_run<double>(const BatchCov&, const Points<double>&, const Factors<const double>&, const Points<double>&,
+                                     const Arena<double>&, hipStream_t);
+template int cross_solve_run<float>(const BatchCov&, const Points<float>&, const Factors<const float>&, const Points<float>&,
+                                    const Arena<float>&, hipStream_t);
 template int layer_predict_run<double>(const LayerPredict<double>&, hipStream_t);
 template int layer_predict_run<float>(const LayerPredict<float>&, hipStream_t);
 template int layer_lml_grad_run<double>(const LayerLml<double>&, hipStream_t);

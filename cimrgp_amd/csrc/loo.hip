@@ -20,7 +20,6 @@ namespace cimrgp {
 
 namespace {
 
-constexpr int LOO_MAXQ = 8;
 constexpr int LD_ROWS = 32;      // rows per workgroup of k_loo_diag
 
 // ------------------------------------------------------------------- rows of the identity ----
@@ -207,8 +206,8 @@ static int trtri_rows_run(const T* l, int64_t n, int64_t ldl, const T* ws, int64
                           PotrfBatch bt, const char* fn)
 {
     if (n <= 0 || m <= 0) return 0;
-    const int64_t nslab = (n + 63) / 64, npan = (n + CIMRGP_NB - 1) / CIMRGP_NB;
-    const T* invT = ws + nslab * 64 * 64;
+    const int64_t npan = (n + CIMRGP_NB - 1) / CIMRGP_NB;
+    const T* invT = ws + ws_invT_offset(n);
     const unsigned nb = (unsigned)bt.count;
     const bool big = loo_tile128(n, bt.count);
     const int GT = big ? 128 : 64;
@@ -309,10 +308,7 @@ static int kinv_diag_entry(const char* fn, int dtype, const void* l_dev, int64_t
     CIMRGP_REQUIRE(scratch_bytes / (size_t)batch >= (size_t)CIMRGP_NB * row_bytes, fn, "scratch too small");
     int64_t strip = (int64_t)(scratch_bytes / (size_t)batch / row_bytes) / CIMRGP_NB * CIMRGP_NB;
     strip = std::min<int64_t>(strip, loo_round256(n));
-    PotrfBatch bt;
-    bt.count = batch;
-    bt.sk = l_stride;
-    bt.sws = (int64_t)(workspace_stride_bytes / elem_bytes(dtype));
+    const PotrfBatch bt{batch, l_stride, (int64_t)(workspace_stride_bytes / elem_bytes(dtype)), 0};
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         return kinv_diag_run<T>((const T*)l_dev, n, ldl, (const T*)workspace_dev, (T*)scratch_dev, strip, (T*)diag_out_dev,
@@ -343,7 +339,7 @@ static int loo_entry(const char* fn, int dtype, const void* y_dev, const int64_t
     CIMRGP_REQUIRE(mean_out_dev == nullptr || (y_dev && alpha_dev), fn, "null pointer (y or alpha)");
     CIMRGP_REQUIRE(batch >= 1 && batch < 65536, fn, "batch count out of range");
     CIMRGP_REQUIRE(n >= 0 && n < (1ll << 31), fn, "bad dimensions");
-    CIMRGP_REQUIRE(q >= 1 && q <= LOO_MAXQ, fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(q >= 1 && q <= MAXQ, fn, "number of outputs must be in [1, 8]");
     if (n == 0 || (mean_out_dev == nullptr && var_out_dev == nullptr)) return 0;
     const dim3 grid((unsigned)((n + 255) / 256), (unsigned)batch);
     return with_dtype(dtype, fn, [&](auto tag) {

@@ -7,7 +7,6 @@ namespace cimrgp {
 
 namespace {
 
-constexpr int MAXQ = 8;
 
 template <typename T>
 static __device__ __forceinline__ T block_sum_1024(T v, T* red)
@@ -195,12 +194,11 @@ namespace cimrgp {
 namespace {
 
 constexpr int LG_T = 64;
-constexpr int LG_MAXD = 8;
 
 // ARD: one length-scale per input dimension.  The caller passes inputs already divided by their
 // length-scales (so the kernel is evaluated with l = 1) and gets d/dlog l_k = 1/2 sum G K d_k^2 per
 // dimension: partial record = [sf | l_1 .. l_8 | trace] (LG_NP entries) instead of [sf | l | trace].
-constexpr int LG_NP = LG_MAXD + 2;
+constexpr int LG_NP = MAXD + 2;
 
 // BATCHED: blockIdx.y = block b of a layer (cimrgp_layer_lml_grad_cov): x from row starts[b], K^-1 at b * ks, alpha at
 // b * n * q, the partial records at b * gridDim.x.  The single-block instance (BATCHED = false) reads none of these.
@@ -221,7 +219,7 @@ void k_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict
                       double* __restrict__ partial, LgBatch bb)
 {
     CIMRGP_LG_BLOCK(ARD ? LG_NP : 3)
-    __shared__ T sa[LG_T * LG_MAXD], sb[LG_T * LG_MAXD];
+    __shared__ T sa[LG_T * MAXD], sb[LG_T * MAXD];
     __shared__ T aa[LG_T * 8], ab[LG_T * 8];
     __shared__ double red[ARD ? LG_NP : 3][4];
     const int id = blockIdx.x;
@@ -231,8 +229,8 @@ void k_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict
     const int tj = id - ti * (ti + 1) / 2;
     const int row0 = ti * LG_T, col0 = tj * LG_T;
     const int tid = threadIdx.x;
-    for (int e = tid; e < LG_T * LG_MAXD; e += 256) {
-        const int r = e / LG_MAXD, k = e - r * LG_MAXD;
+    for (int e = tid; e < LG_T * MAXD; e += 256) {
+        const int r = e / MAXD, k = e - r * MAXD;
         sa[e] = (k < d && row0 + r < n) ? x[(int64_t)(row0 + r) * d + k] : (T)0;
         sb[e] = (k < d && col0 + r < n) ? x[(int64_t)(col0 + r) * d + k] : (T)0;
         aa[e] = (k < q && row0 + r < n) ? alpha[(int64_t)(row0 + r) * q + k] : (T)0;
@@ -241,18 +239,18 @@ void k_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict
     __syncthreads();
     const int tx = tid & 63, ty = tid >> 6;
     double s_sf = 0.0, s_l = 0.0, s_tr = 0.0;
-    double s_lk[ARD ? LG_MAXD : 1];
+    double s_lk[ARD ? MAXD : 1];
 #pragma unroll
-    for (int k = 0; k < (ARD ? LG_MAXD : 1); ++k) s_lk[k] = 0.0;
+    for (int k = 0; k < (ARD ? MAXD : 1); ++k) s_lk[k] = 0.0;
     const int gc = col0 + tx;
     for (int rr = ty; rr < LG_T; rr += 4) {
         const int gr = row0 + rr;
         if (gr < n && gc < n && gc <= gr) {
             T d2 = (T)0;
-            T dk2[LG_MAXD];
+            T dk2[MAXD];
 #pragma unroll
-            for (int k = 0; k < LG_MAXD; ++k) {
-                const T df = sa[rr * LG_MAXD + k] - sb[tx * LG_MAXD + k];
+            for (int k = 0; k < MAXD; ++k) {
+                const T df = sa[rr * MAXD + k] - sb[tx * MAXD + k];
                 dk2[k] = df * df;
                 d2 += dk2[k];
             }
@@ -265,7 +263,7 @@ void k_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict
             s_sf += wgt * (double)(g * kf);
             if (ARD) {
 #pragma unroll
-                for (int k = 0; k < LG_MAXD; ++k) s_lk[k] += wgt * (double)(g * kf * dk2[k]);
+                for (int k = 0; k < MAXD; ++k) s_lk[k] += wgt * (double)(g * kf * dk2[k]);
             } else {
                 s_l  += wgt * (double)(g * kf * d2 * inv_l2);
             }
@@ -279,14 +277,14 @@ void k_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict
         s_tr += __shfl_xor(s_tr, off, 64);
         if (ARD) {
 #pragma unroll
-            for (int k = 0; k < LG_MAXD; ++k) s_lk[k] += __shfl_xor(s_lk[k], off, 64);
+            for (int k = 0; k < MAXD; ++k) s_lk[k] += __shfl_xor(s_lk[k], off, 64);
         }
     }
     if (ARD) {
         if (tx == 0) {
             red[0][ty] = s_sf;
 #pragma unroll
-            for (int k = 0; k < LG_MAXD; ++k) red[1 + k][ty] = s_lk[k];
+            for (int k = 0; k < MAXD; ++k) red[1 + k][ty] = s_lk[k];
             red[LG_NP - 1][ty] = s_tr;
         }
         __syncthreads();
@@ -309,7 +307,7 @@ static __device__ __forceinline__ void lml_grad_tile(const T* __restrict__ x, in
     static_assert(COV != CIMRGP_COV_RBF, "the RBF gradient is k_lml_grad_tiles");
     (void)inv_l2;
     CIMRGP_LG_BLOCK(ARD ? LG_NP : 3)
-    __shared__ T sa[LG_T * LG_MAXD], sb[LG_T * LG_MAXD];
+    __shared__ T sa[LG_T * MAXD], sb[LG_T * MAXD];
     __shared__ T aa[LG_T * 8], ab[LG_T * 8];
     __shared__ double red[ARD ? LG_NP : 3][4];
     const int id = blockIdx.x;
@@ -319,8 +317,8 @@ static __device__ __forceinline__ void lml_grad_tile(const T* __restrict__ x, in
     const int tj = id - ti * (ti + 1) / 2;
     const int row0 = ti * LG_T, col0 = tj * LG_T;
     const int tid = threadIdx.x;
-    for (int e = tid; e < LG_T * LG_MAXD; e += 256) {
-        const int r = e / LG_MAXD, k = e - r * LG_MAXD;
+    for (int e = tid; e < LG_T * MAXD; e += 256) {
+        const int r = e / MAXD, k = e - r * MAXD;
         sa[e] = (k < d && row0 + r < n) ? x[(int64_t)(row0 + r) * d + k] : (T)0;
         sb[e] = (k < d && col0 + r < n) ? x[(int64_t)(col0 + r) * d + k] : (T)0;
         aa[e] = (k < q && row0 + r < n) ? alpha[(int64_t)(row0 + r) * q + k] : (T)0;
@@ -329,18 +327,18 @@ static __device__ __forceinline__ void lml_grad_tile(const T* __restrict__ x, in
     __syncthreads();
     const int tx = tid & 63, ty = tid >> 6;
     double s_sf = 0.0, s_l = 0.0, s_tr = 0.0;
-    double s_lk[ARD ? LG_MAXD : 1];
+    double s_lk[ARD ? MAXD : 1];
 #pragma unroll
-    for (int k = 0; k < (ARD ? LG_MAXD : 1); ++k) s_lk[k] = 0.0;
+    for (int k = 0; k < (ARD ? MAXD : 1); ++k) s_lk[k] = 0.0;
     const int gc = col0 + tx;
     for (int rr = ty; rr < LG_T; rr += 4) {
         const int gr = row0 + rr;
         if (gr < n && gc < n && gc <= gr) {
             T d2 = (T)0;
-            T dk2[LG_MAXD];
+            T dk2[MAXD];
 #pragma unroll
-            for (int k = 0; k < LG_MAXD; ++k) {
-                const T df = sa[rr * LG_MAXD + k] - sb[tx * LG_MAXD + k];
+            for (int k = 0; k < MAXD; ++k) {
+                const T df = sa[rr * MAXD + k] - sb[tx * MAXD + k];
                 dk2[k] = df * df;
                 d2 += dk2[k];
             }
@@ -350,14 +348,14 @@ static __device__ __forceinline__ void lml_grad_tile(const T* __restrict__ x, in
             const T g = aat - (T)q * kinv[(int64_t)gr * ld + gc];
             const double wgt = (gr == gc) ? 1.0 : 2.0;
             // r from d2 (a sum of squares: exactly 0 on the diagonal); d = 1 takes |df| as the Gram kernels do
-            const T r = d == 1 ? fabs(sa[rr * LG_MAXD] - sb[tx * LG_MAXD]) : sqrt(d2);
+            const T r = d == 1 ? fabs(sa[rr * MAXD] - sb[tx * MAXD]) : sqrt(d2);
             const T t = c * r, v = exp(-t);
             const T kf = sf2 * Cov<COV>::poly(t) * v;
             s_sf += wgt * (double)(g * kf);
             if (ARD) {
                 const T gk = g * Cov<COV>::ard(t, r, v, c, sf2);
 #pragma unroll
-                for (int k = 0; k < LG_MAXD; ++k) s_lk[k] += wgt * (double)(gk * dk2[k]);
+                for (int k = 0; k < MAXD; ++k) s_lk[k] += wgt * (double)(gk * dk2[k]);
             } else {
                 s_l  += wgt * (double)(g * Cov<COV>::dlogl(t, v, sf2));
             }
@@ -371,14 +369,14 @@ static __device__ __forceinline__ void lml_grad_tile(const T* __restrict__ x, in
         s_tr += __shfl_xor(s_tr, off, 64);
         if (ARD) {
 #pragma unroll
-            for (int k = 0; k < LG_MAXD; ++k) s_lk[k] += __shfl_xor(s_lk[k], off, 64);
+            for (int k = 0; k < MAXD; ++k) s_lk[k] += __shfl_xor(s_lk[k], off, 64);
         }
     }
     if (ARD) {
         if (tx == 0) {
             red[0][ty] = s_sf;
 #pragma unroll
-            for (int k = 0; k < LG_MAXD; ++k) red[1 + k][ty] = s_lk[k];
+            for (int k = 0; k < MAXD; ++k) red[1 + k][ty] = s_lk[k];
             red[LG_NP - 1][ty] = s_tr;
         }
         __syncthreads();
@@ -427,8 +425,8 @@ static int lml_grad_run_cov(const T* x, int64_t n, int d, const T* kinv, int64_t
                             const char* fn)
 {
     CIMRGP_REQUIRE(n > 0 && n < (1ll << 30), fn, "bad size");
-    CIMRGP_REQUIRE(d >= 1 && d <= LG_MAXD, fn, "input dimension must be in [1, 8]");
-    CIMRGP_REQUIRE(q >= 1 && q <= 8, fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
+    CIMRGP_REQUIRE(q >= 1 && q <= MAXQ, fn, "number of outputs must be in [1, 8]");
     const int64_t tm = (n + LG_T - 1) / LG_T, tiles = tm * (tm + 1) / 2;
     CIMRGP_REQUIRE(tiles < (1ll << 31), fn, "grid too large");
     if (ard) {
@@ -513,8 +511,8 @@ int lml_grad_batched_run(const T* x, const int64_t* starts, int batch, int64_t n
                          double* partial, hipStream_t st, int cov, const char* fn)
 {
     CIMRGP_REQUIRE(n > 0 && n < (1ll << 30), fn, "bad size");
-    CIMRGP_REQUIRE(d >= 1 && d <= LG_MAXD, fn, "input dimension must be in [1, 8]");
-    CIMRGP_REQUIRE(q >= 1 && q <= 8, fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
+    CIMRGP_REQUIRE(q >= 1 && q <= MAXQ, fn, "number of outputs must be in [1, 8]");
     CIMRGP_REQUIRE(batch >= 1 && batch < 65536, fn, "batch count out of range");
     const int64_t tiles = lml_grad_tiles_count(n);
     CIMRGP_REQUIRE(tiles < (1ll << 31), fn, "grid too large");

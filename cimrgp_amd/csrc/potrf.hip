@@ -818,8 +818,8 @@ static int build_invT(const Problem<T>& p, hipStream_t st)
     T* const ws = p.ws;
     const int64_t n = p.n, ld = p.ld;
     const PotrfBatch& bt = p.bt;
-    const int64_t nslab = (n + SB - 1) / SB, npan = (n + CIMRGP_NB - 1) / CIMRGP_NB;
-    T* invT = ws + nslab * (SB * SB);
+    const int64_t npan = (n + CIMRGP_NB - 1) / CIMRGP_NB;
+    T* invT = ws + ws_invT_offset(n);
     const unsigned nbatch = (unsigned)bt.count;
     // Full panels (round 4): invT_p = I L_pp^-T is the carried rows' panel step applied to the identity -- one launch of
     // k_rows_step for all of them (16 workgroups per panel, ~12 us) instead of k_invT_panel's four dependent sub-steps

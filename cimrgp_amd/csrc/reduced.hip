@@ -12,8 +12,6 @@ namespace cimrgp {
 namespace {
 
 constexpr int RB_MAXM = 64;
-constexpr int RB_MAXQ = 8;
-constexpr int RB_MAXD = 8;
 
 // phi[n][m]: phi_i(x) = prod_k L_k^-1/2 sin(pi (i+1) (x_k + L_k) / (2 L_k))
 template <typename T>
@@ -324,7 +322,7 @@ int laplace_basis_run(const T* x, int64_t n, int d, const double* interval, int 
 {
     const char* fn = "cimrgp_laplace_basis";
     if (n <= 0) return 0;
-    CIMRGP_REQUIRE(d >= 1 && d <= RB_MAXD, fn, "input dimension must be in [1, 8]");
+    CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
     CIMRGP_REQUIRE(m >= 1 && m <= RB_MAXM, fn, "number of basis functions must be in [1, 64]");
     const int64_t total = n * m;
     hipLaunchKernelGGL((k_laplace_basis<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, n, d, interval, m, phi);
@@ -344,8 +342,8 @@ int basis_moments_run(const T* x, int64_t n, int d, const double* interval, int 
 {
     const char* fn = "cimrgp_basis_moments";
     CIMRGP_REQUIRE(n > 0, fn, "empty block");
-    CIMRGP_REQUIRE(d >= 1 && d <= RB_MAXD, fn, "input dimension must be in [1, 8]");
-    CIMRGP_REQUIRE(m >= 1 && m <= RB_MAXM && q >= 1 && q <= RB_MAXQ, fn, "m must be in [1, 64], q in [1, 8]");
+    CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
+    CIMRGP_REQUIRE(m >= 1 && m <= RB_MAXM && q >= 1 && q <= MAXQ, fn, "m must be in [1, 64], q in [1, 8]");
     const int nwg = basis_moments_workgroups(n);
     const int rec = m * q + 2 * m + q + 2;
     const int qt = q_template(q);
@@ -380,8 +378,8 @@ int basis_apply_run(const T* x, int64_t n, int d, const double* interval, int m,
 {
     const char* fn = "cimrgp_basis_apply";
     if (n <= 0) return 0;
-    CIMRGP_REQUIRE(d >= 1 && d <= RB_MAXD, fn, "input dimension must be in [1, 8]");
-    CIMRGP_REQUIRE(m >= 1 && m <= RB_MAXM && q >= 1 && q <= RB_MAXQ, fn, "m must be in [1, 64], q in [1, 8]");
+    CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
+    CIMRGP_REQUIRE(m >= 1 && m <= RB_MAXM && q >= 1 && q <= MAXQ, fn, "m must be in [1, 64], q in [1, 8]");
     const dim3 grid((unsigned)((n + 255) / 256));
     const int qt = q_template(q);
     switch (d_template(d)) {

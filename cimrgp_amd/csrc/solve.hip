@@ -14,7 +14,6 @@ namespace cimrgp {
 namespace {
 
 constexpr int SB   = 64;
-constexpr int MAXQ = 8;
 
 // (n x q) row-major  <->  (q x n)
 template <typename T>
@@ -412,7 +411,7 @@ int potrs_run(const T* l, int64_t n, int64_t ld, const T* ws, T* rhs, int q, T* 
         hipLaunchKernelGGL((k_transpose_nq<T>), dim3(tg, nbatch), dim3(256), 0, st, (const T*)rhs, work, n, q, 1, srhs, sscr);
         CIMRGP_LAUNCH_CHECK(fn);
     }
-    const T* invT = ws + ((n + SB - 1) / SB) * (SB * SB);
+    const T* invT = ws + ws_invT_offset(n);
     for (int64_t k0 = 0; k0 < n && !backward_only; k0 += PW) {
         const int w = (int)((n - k0 < PW) ? (n - k0) : PW);
         const int64_t below = n - (k0 + w);

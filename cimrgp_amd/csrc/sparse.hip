@@ -26,7 +26,6 @@ namespace {
 
 constexpr int WS_GT = 128;                    // output tile edge
 constexpr int WS_GQ = 16;                     // columns of the g operand (one MFMA tile)
-constexpr int WS_MAXQ = 8;
 constexpr int WS_SLICE_ALIGN = 32;            // slices start on multiples of the larger chunk (FP32's)
 constexpr int WS_TARGET_WGS = 1024;           // tiles x S aims at two rounds of two workgroups per compute unit (256 units)
 
@@ -223,11 +222,11 @@ static __device__ __forceinline__ void wsyrk_tile(T* __restrict__ smem, const T*
             for (int rr = 0; rr < 4; ++rr) ctile[(wr * 64 + mi * 16 + X::crow(lane, rr)) * WS_GT + c] = acc[mi][ni][rr];
         }
     }
-    if (do_g && wc == 0 && (lane & 15) < WS_MAXQ) {
+    if (do_g && wc == 0 && (lane & 15) < MAXQ) {
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-            for (int rr = 0; rr < 4; ++rr) gtile[(wr * 64 + mi * 16 + X::crow(lane, rr)) * WS_MAXQ + (lane & 15)] = accg[mi][rr];
+            for (int rr = 0; rr < 4; ++rr) gtile[(wr * 64 + mi * 16 + X::crow(lane, rr)) * MAXQ + (lane & 15)] = accg[mi][rr];
     }
 }
 
@@ -245,7 +244,7 @@ void k_wsyrk_tn(const T* __restrict__ A, int64_t lda, int n, int m, const T* __r
     const int ti = tj + (tile - first);
     const int k0 = slice * slice_len, k1 = min(n, k0 + slice_len);
     T* ctile = cpart + ((int64_t)slice * tiles + tile) * (WS_GT * WS_GT);
-    T* gtile = (r != nullptr && tj == 0) ? gpart + ((int64_t)slice * tiles1d + ti) * (WS_GT * WS_MAXQ) : nullptr;
+    T* gtile = (r != nullptr && tj == 0) ? gpart + ((int64_t)slice * tiles1d + ti) * (WS_GT * MAXQ) : nullptr;
     const bool edge = (ti + 1) * WS_GT > m || (k1 - k0) % G::KC != 0;
     if (edge) wsyrk_tile<T, true>(smem, A, lda, n, m, w, r, q, ti, tj, k0, k1, ctile, gtile);
     else      wsyrk_tile<T, false>(smem, A, lda, n, m, w, r, q, ti, tj, k0, k1, ctile, gtile);
@@ -275,9 +274,9 @@ void k_wsyrk_reduce(const T* __restrict__ cpart, const T* __restrict__ gpart, in
         const int e = ((int)blockIdx.x - tiles * 64) * 256 + tid;
         if (e >= m * q) return;
         const int i = e / q, c = e - i * q;
-        const T* p = gpart + (int64_t)i * WS_MAXQ + c;
+        const T* p = gpart + (int64_t)i * MAXQ + c;
         T s = p[0];
-        for (int sl = 1; sl < slices; ++sl) s += p[(int64_t)sl * tiles1d * (WS_GT * WS_MAXQ)];
+        for (int sl = 1; sl < slices; ++sl) s += p[(int64_t)sl * tiles1d * (WS_GT * MAXQ)];
         g[e] = s;
     }
 }
@@ -346,9 +345,9 @@ void k_sparse_tail(const T* __restrict__ As, const T* __restrict__ Ws, int ns, i
 {
     const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= ns) return;
-    double sa = 0.0, sw = 0.0, acc[WS_MAXQ];
+    double sa = 0.0, sw = 0.0, acc[MAXQ];
 #pragma unroll
-    for (int c = 0; c < WS_MAXQ; ++c) acc[c] = 0.0;
+    for (int c = 0; c < MAXQ; ++c) acc[c] = 0.0;
     const T* wrow = Ws + (int64_t)row * lda;
     for (int j = lane; j < m; j += 64) {
         const double wv = (double)wrow[j];
@@ -359,7 +358,7 @@ void k_sparse_tail(const T* __restrict__ As, const T* __restrict__ Ws, int ns, i
         }
         if (mean) {
 #pragma unroll
-            for (int c = 0; c < WS_MAXQ; ++c)
+            for (int c = 0; c < MAXQ; ++c)
                 if (c < q) acc[c] += wv * (double)gamma[j * q + c];
         }
     }
@@ -368,7 +367,7 @@ void k_sparse_tail(const T* __restrict__ As, const T* __restrict__ Ws, int ns, i
         sa += __shfl_xor(sa, off, 64);
         sw += __shfl_xor(sw, off, 64);
 #pragma unroll
-        for (int c = 0; c < WS_MAXQ; ++c) acc[c] += __shfl_xor(acc[c], off, 64);
+        for (int c = 0; c < MAXQ; ++c) acc[c] += __shfl_xor(acc[c], off, 64);
     }
     if (lane != 0) return;
     if (var) {
@@ -377,7 +376,7 @@ void k_sparse_tail(const T* __restrict__ As, const T* __restrict__ Ws, int ns, i
     }
     if (mean) {
 #pragma unroll
-        for (int c = 0; c < WS_MAXQ; ++c)
+        for (int c = 0; c < MAXQ; ++c)
             if (c < q) mean[(int64_t)row * q + c] = accumulate ? mean[(int64_t)row * q + c] + (T)acc[c] : (T)acc[c];
     }
 }
@@ -386,7 +385,7 @@ static inline bool ws_sizes_ok(int64_t n, int64_t m) { return n >= 1 && n <= CIM
 
 // elements of scratch: the partial tiles, then the partial g
 static inline int64_t ws_cpart_elems(int64_t n, int64_t m) { return ws_slices(n, m) * ws_tiles(m) * (WS_GT * WS_GT); }
-static inline int64_t ws_gpart_elems(int64_t n, int64_t m) { return ws_slices(n, m) * ws_tiles_1d(m) * (WS_GT * WS_MAXQ); }
+static inline int64_t ws_gpart_elems(int64_t n, int64_t m) { return ws_slices(n, m) * ws_tiles_1d(m) * (WS_GT * MAXQ); }
 
 }  // namespace
 
@@ -415,7 +414,7 @@ extern "C" {
 
 size_t cimrgp_wsyrk_tn_scratch_bytes(int dtype, int64_t n, int64_t m, int q)
 {
-    if (!dtype_known(dtype) || !ws_sizes_ok(n, m) || q < 0 || q > WS_MAXQ) return 0;
+    if (!dtype_known(dtype) || !ws_sizes_ok(n, m) || q < 0 || q > MAXQ) return 0;
     return (size_t)(ws_cpart_elems(n, m) + (q > 0 ? ws_gpart_elems(n, m) : 0)) * elem_bytes(dtype);
 }
 
@@ -428,7 +427,7 @@ int cimrgp_wsyrk_tn(int dtype, const void* a_dev, int64_t n, int64_t m, int64_t 
     CIMRGP_REQUIRE(r_dev == nullptr || g_dev != nullptr, fn, "null pointer (g)");
     CIMRGP_REQUIRE(n >= 1 && n <= CIMRGP_WSYRK_MAX_N, fn, "n must be in [1, 16777216]");
     CIMRGP_REQUIRE(m >= 1 && m <= CIMRGP_WSYRK_MAX_M, fn, "m must be in [1, 16384]");
-    CIMRGP_REQUIRE(r_dev == nullptr || (q >= 1 && q <= WS_MAXQ), fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(r_dev == nullptr || (q >= 1 && q <= MAXQ), fn, "number of outputs must be in [1, 8]");
     CIMRGP_REQUIRE(lda >= m && ldc >= m, fn, "leading dimension too small");
     CIMRGP_REQUIRE(lda % elems_per_16_bytes(dtype) == 0, fn, "lda must be a multiple of 16 bytes");
     CIMRGP_REQUIRE(aligned16(a_dev) && aligned16(scratch_dev), fn, "pointers must be 16-byte aligned");
@@ -470,7 +469,7 @@ int cimrgp_sparse_tail(int dtype, const void* astar_dev, const void* wstar_dev, 
     CIMRGP_REQUIRE(var_dev == nullptr || astar_dev, fn, "null pointer (astar)");
     CIMRGP_REQUIRE(mean_dev == nullptr || gamma_dev, fn, "null pointer (gamma)");
     CIMRGP_REQUIRE(ns >= 0 && ns < (1ll << 31) && m >= 1 && m < (1ll << 31) && lda >= m, fn, "bad dimensions");
-    CIMRGP_REQUIRE(mean_dev == nullptr || (q >= 1 && q <= WS_MAXQ), fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(mean_dev == nullptr || (q >= 1 && q <= MAXQ), fn, "number of outputs must be in [1, 8]");
     if (ns == 0 || (mean_dev == nullptr && var_dev == nullptr)) return 0;
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);

@@ -21,10 +21,8 @@ namespace cimrgp {
 namespace {
 
 constexpr int PG_CT = 128;                    // columns of G per workgroup
-constexpr int PG_MAXD = 8;
 constexpr int PG_TARGET_WGS = 1024;           // tiles x S aims at four workgroups per compute unit (256 units)
 constexpr int PG_SLICE_ALIGN = 8;             // rows of G per pass of a workgroup (4 waves x 2 rows in FP32)
-constexpr int SG_MAXQ = 8;
 
 // S(na, nb) and the slice length: a function of na and nb alone (not of the dtype, the device or its load).
 static inline int64_t pg_tiles(int64_t nb) { return (nb + PG_CT - 1) / PG_CT; }
@@ -40,7 +38,7 @@ static inline int64_t pg_slice_len(int64_t na, int64_t nb)
 static inline int64_t pg_slices(int64_t na, int64_t nb) { const int64_t len = pg_slice_len(na, nb); return (na + len - 1) / len; }
 static inline bool pg_sizes_ok(int64_t na, int64_t nb, int d)
 {
-    return na >= 1 && na <= CIMRGP_PAIR_GRAD_MAX_NA && nb >= 1 && nb <= CIMRGP_PAIR_GRAD_MAX_NB && d >= 1 && d <= PG_MAXD;
+    return na >= 1 && na <= CIMRGP_PAIR_GRAD_MAX_NA && nb >= 1 && nb <= CIMRGP_PAIR_GRAD_MAX_NB && d >= 1 && d <= MAXD;
 }
 // doubles of scratch: the partial db, then the partial sums
 static inline int64_t pg_dbpart_elems(int64_t na, int64_t nb, int d) { return pg_slices(na, nb) * pg_tiles(nb) * PG_CT * d; }
@@ -75,7 +73,7 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
     constexpr int LPR = PG_CT / EPL;            // lanes per tile row
     constexpr int RPI = 64 / LPR;               // rows per wave and load instruction
     constexpr int NPH = 4 * RPI;                // row phases of the workgroup
-    constexpr int DD = D ? D : PG_MAXD;
+    constexpr int DD = D ? D : MAXD;
     __shared__ double red[NPH * PG_CT];
     __shared__ double sred[4][2];
     const int slice = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - slice * tiles;
@@ -225,27 +223,27 @@ void k_sparse_grad_rows(const T* __restrict__ V, int64_t ldv, int n, int m, cons
     const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n) return;
     const T* v = V + (int64_t)row * ldv;
-    double sv = 0.0, acc[SG_MAXQ];
+    double sv = 0.0, acc[MAXQ];
 #pragma unroll
-    for (int c = 0; c < SG_MAXQ; ++c) acc[c] = 0.0;
+    for (int c = 0; c < MAXQ; ++c) acc[c] = 0.0;
     for (int j = lane; j < m; j += 64) {
         const double vv = (double)v[j];
         sv += vv * vv;
 #pragma unroll
-        for (int c = 0; c < SG_MAXQ; ++c)
+        for (int c = 0; c < MAXQ; ++c)
             if (c < q) acc[c] += vv * (double)gamma[(int64_t)j * q + c];
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         sv += __shfl_xor(sv, off, 64);
 #pragma unroll
-        for (int c = 0; c < SG_MAXQ; ++c) acc[c] += __shfl_xor(acc[c], off, 64);
+        for (int c = 0; c < MAXQ; ++c) acc[c] += __shfl_xor(acc[c], off, 64);
     }
     if (lane != 0) return;
     const double wi = (double)w[row];
     double bsq = 0.0;
 #pragma unroll
-    for (int c = 0; c < SG_MAXQ; ++c) {
+    for (int c = 0; c < MAXQ; ++c) {
         if (c < q) {
             const double bt = wi * ((double)r[(int64_t)row * q + c] - acc[c]);
             beta[(int64_t)row * q + c] = (T)bt;
@@ -296,16 +294,16 @@ void k_sparse_grad_combine(const T* __restrict__ A, int64_t lda, T* __restrict__
 {
     const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n) return;
-    double bt[SG_MAXQ];
+    double bt[MAXQ];
 #pragma unroll
-    for (int c = 0; c < SG_MAXQ; ++c) bt[c] = c < q ? (double)beta[(int64_t)row * q + c] : 0.0;
+    for (int c = 0; c < MAXQ; ++c) bt[c] = c < q ? (double)beta[(int64_t)row * q + c] : 0.0;
     const double qw = (double)q * (double)w[row], t2 = 2.0 * (double)t[row];
     const T* a = A + (int64_t)row * lda;
     T* y = Y + (int64_t)row * ldy;
     for (int j = lane; j < m; j += 64) {
         double s = 0.0;
 #pragma unroll
-        for (int c = 0; c < SG_MAXQ; ++c)
+        for (int c = 0; c < MAXQ; ++c)
             if (c < q) s += bt[c] * (double)b[(int64_t)j * q + c];
         y[j] = (T)(s - qw * (double)y[j] - t2 * (double)a[j]);
     }
@@ -360,7 +358,7 @@ int cimrgp_cov_pair_grad(int dtype, int cov, const void* xa_dev, int64_t na, con
     CIMRGP_REQUIRE(xa_dev && xb_dev && g_dev && scratch_dev, fn, "null pointer");
     CIMRGP_REQUIRE(na >= 1 && na <= CIMRGP_PAIR_GRAD_MAX_NA, fn, "na must be in [1, 16777216]");
     CIMRGP_REQUIRE(nb >= 1 && nb <= CIMRGP_PAIR_GRAD_MAX_NB, fn, "nb must be in [1, 1048576]");
-    CIMRGP_REQUIRE(d >= 1 && d <= PG_MAXD, fn, "input dimension must be in [1, 8]");
+    CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
     CIMRGP_REQUIRE(ldg >= nb, fn, "leading dimension too small");
     CIMRGP_REQUIRE(ell > 0.0 && sf2 > 0.0, fn, "kernel parameters must be positive");
     CIMRGP_REQUIRE((reinterpret_cast<uintptr_t>(scratch_dev) & 7u) == 0, fn, "scratch must be 8-byte aligned");
@@ -383,7 +381,7 @@ int cimrgp_sparse_grad_rows(int dtype, const void* v_dev, int64_t n, int64_t m, 
     CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(v_dev && gamma_dev && r_dev && w_dev && beta_dev && t_dev && sums_dev, fn, "null pointer");
     CIMRGP_REQUIRE(n >= 1 && n < (1ll << 31) && m >= 1 && m < (1ll << 31) && ldv >= m, fn, "bad dimensions");
-    CIMRGP_REQUIRE(q >= 1 && q <= SG_MAXQ, fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(q >= 1 && q <= MAXQ, fn, "number of outputs must be in [1, 8]");
     CIMRGP_REQUIRE(mode == 0 || mode == 1, fn, "mode must be 0 (FITC) or 1 (VFE)");
     CIMRGP_REQUIRE(noise > 0.0, fn, "noise must be positive");
     return with_dtype(dtype, fn, [&](auto tag) {
@@ -405,7 +403,7 @@ int cimrgp_sparse_grad_combine(int dtype, const void* a_dev, int64_t lda, void* 
     CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(a_dev && y_dev && beta_dev && b_dev && w_dev && t_dev, fn, "null pointer");
     CIMRGP_REQUIRE(n >= 1 && n < (1ll << 31) && m >= 1 && m < (1ll << 31) && lda >= m && ldy >= m, fn, "bad dimensions");
-    CIMRGP_REQUIRE(q >= 1 && q <= SG_MAXQ, fn, "number of outputs must be in [1, 8]");
+    CIMRGP_REQUIRE(q >= 1 && q <= MAXQ, fn, "number of outputs must be in [1, 8]");
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         hipLaunchKernelGGL((k_sparse_grad_combine<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream_of(stream), (const T*)a_dev, lda,

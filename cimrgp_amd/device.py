@@ -255,6 +255,11 @@ def layer_fit(x, y, fbar, train_out, starts, n, ell, sf2, noise_fixed, noise_fra
                                         _p(noise), _p(scratch), _stream()), "cimrgp_layer_fit_cov")
 
 
+def _w_work(batch, ns, ldw, like):
+    """The W work area of a layer call: ``batch`` blocks of ``ns`` rows of pitch ``ldw``, allocated for that call only."""
+    return torch.empty((batch, max(int(ns), 1), ldw), dtype=like.dtype, device=like.device)
+
+
 def layer_predict(x, starts, n, xs, t_starts, ns, ell, sf2, larena, ws_arena, z, bias, noise, mean, var, cov=_lib.COV_RBF):
     """Predictive mean and variance of ``batch`` equal-sized blocks at ``ns`` test points each in ONE call
     (cimrgp_layer_predict_cov): accumulates into mean (N* x q) / var (N*,) at rows t_starts[b] ...; ``noise``
@@ -263,7 +268,7 @@ def layer_predict(x, starts, n, xs, t_starts, ns, ell, sf2, larena, ws_arena, z,
     lib = _lib.load()
     batch = int(larena.shape[0])
     ldw = padded_ld(n)
-    w = torch.empty((batch, max(int(ns), 1), ldw), dtype=x.dtype, device=x.device)
+    w = _w_work(batch, ns, ldw, x)
     _lib.check(lib.cimrgp_layer_predict_cov(_DT[x.dtype], cov, _p(x), _p(starts), int(n), int(x.shape[1]), _p(xs), _p(t_starts),
                                             int(ns), batch, float(ell), float(sf2), _p(larena), larena.stride(1),
                                             larena.stride(0), _p(ws_arena), ws_arena.stride(0), _p(z), int(z.shape[2]), _p(bias),
@@ -296,7 +301,7 @@ def layer_joint_cov(x, starts, n, xs, t_starts, ns, ell, sf2, larena, ws_arena, 
     lib = _lib.load()
     batch = int(larena.shape[0])
     ldw = joint_ld(n, x.dtype)
-    w = torch.empty((batch, max(int(ns), 1), ldw), dtype=x.dtype, device=x.device)
+    w = _w_work(batch, ns, ldw, x)
     _lib.check(lib.cimrgp_layer_joint_cov(_DT[x.dtype], cov, _p(x), _p(starts), int(n), int(x.shape[1]), _p(xs), _p(t_starts),
                                           int(ns), batch, float(ell), float(sf2), _p(larena), larena.stride(1), larena.stride(0),
                                           _p(ws_arena), ws_arena.stride(0), _p(diag), _p(w), ldw, w.stride(0), _p(carena),
@@ -360,7 +365,7 @@ def layer_predict_grad(x, starts, n, xs, t_starts, ns, ell, sf2, larena, ws_aren
     lib = _lib.load()
     batch = int(larena.shape[0])
     ldw = padded_ld(n)
-    w = torch.empty((batch, max(int(ns), 1), ldw), dtype=x.dtype, device=x.device) if var_grad is not None else None
+    w = _w_work(batch, ns, ldw, x) if var_grad is not None else None
     _lib.check(lib.cimrgp_layer_predict_grad_cov(_DT[x.dtype], cov, _p(x), _p(starts), int(n), int(x.shape[1]), _p(xs),
                                                  _p(t_starts), int(ns), batch, float(ell), float(sf2), _p(larena),
                                                  larena.stride(1), larena.stride(0), _p(ws_arena), ws_arena.stride(0),

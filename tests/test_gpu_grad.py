@@ -359,3 +359,31 @@ def test_layer_predict_grad_footprint(dev, cov):
         wm, wv = contract(xb, alphas[b], t, cov, 0.6, 1.2, beta)
         assert rel(got_m[a:a + ns], pre_m[a:a + ns] + wm) < 1e-10
         assert rel(got_v[a:a + ns], pre_v[a:a + ns] + wv) < 1e-10
+
+
+def test_layer_predict_grad_mean_alone_matches_numpy(dev):
+    """The batched call with mean_grad alone: no W is formed, d mean / d xs accumulates at each block's test rows and the
+    rows between the blocks stay as they were."""
+    tdt, nb, n, ns, d, q, cov, ell, sf2 = torch.float64, 2, 65, 33, 1, 3, 2, 0.6, 1.2
+    rng = np.random.default_rng(11)
+    N, Ns = nb * n + 17, nb * ns + 11
+    x = rng.uniform(-1, 1, size=(N, d))
+    xs = rng.uniform(-1, 1, size=(Ns, d))
+    starts, t_starts = np.array([5, 5 + n]), np.array([3, 3 + ns + 2])
+    alpha = rng.normal(size=(nb, n, q))
+    pre = rng.normal(size=(Ns, d, q))
+    T = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=tdt, device="cuda")
+    larena = torch.zeros((nb, n, dev.padded_ld(n)), dtype=tdt, device="cuda")        # not read without var_grad
+    ws_arena = torch.zeros((nb, (dev.potrf_workspace_bytes(n, tdt) + 15) // 16 * 16), dtype=torch.uint8, device="cuda")
+    mg = T(pre)
+    dev.layer_predict_grad(T(x), torch.as_tensor(starts).cuda(), n, T(xs), torch.as_tensor(t_starts).cuda(), ns, ell, sf2, larena,
+                           ws_arena, T(alpha), mg, None, cov=cov)
+    torch.cuda.synchronize()
+    got = mg.cpu().numpy()
+    seen = np.zeros(Ns, dtype=bool)
+    for b in range(nb):
+        a = t_starts[b]
+        wm, _ = contract(x[starts[b]:starts[b] + n], alpha[b], xs[a:a + ns], cov, ell, sf2)
+        assert rel(got[a:a + ns], pre[a:a + ns] + wm) < 1e-10
+        seen[a:a + ns] = True
+    assert np.array_equal(got[~seen], pre[~seen])
