@@ -201,7 +201,7 @@ class DenseMaternKernel(object):
 
     # ---- dense Gram builder (device, HIP) ---------------------------------
     def gram(self, x, x2=None, diag_add=0.0, lower_only=False):
-        """Gram matrix on the GPU (k_cov_gram).  ``x``/``x2``: CUDA tensors (n x d).  Returns a
+        """Gram matrix on the GPU (k_gram).  ``x``/``x2``: CUDA tensors (n x d).  Returns a
         torch view (n x n2) of the padded device buffer."""
         from . import device as dev
         if x2 is None:

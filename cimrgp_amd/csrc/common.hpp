@@ -261,15 +261,67 @@ template <typename F> static inline int with_cov(int cov, F&& f)
     }
 }
 
+// The other run-time -> compile-time dispatches of the covariance code, in the same form.
+// with_dim: the input dimension as D = 1, 2 or 0 (0: run-time d <= MAXD, fully unrolled and predicated loops)
+template <typename F> static inline auto with_dim(int d, F&& f)
+{
+    if (d == 1) return f(std::integral_constant<int, 1>());
+    if (d == 2) return f(std::integral_constant<int, 2>());
+    return f(std::integral_constant<int, 0>());
+}
+// with_q: the number of outputs (right-hand sides) as Q = q exactly, 1 .. MAXQ (validated by the entry points)
+template <typename F> static inline auto with_q(int q, F&& f)
+{
+    switch (q) {
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
+        case 4: return f(std::integral_constant<int, 4>());
+        case 5: return f(std::integral_constant<int, 5>());
+        case 6: return f(std::integral_constant<int, 6>());
+        case 7: return f(std::integral_constant<int, 7>());
+        default: return f(std::integral_constant<int, 8>());
+    }
+}
+// with_q_rounded: Q = q up to 4, then 8 for kernels that guard c < q at run time (half the instances)
+template <typename F> static inline auto with_q_rounded(int q, F&& f)
+{
+    switch (q) {
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
+        case 4: return f(std::integral_constant<int, 4>());
+        default: return f(std::integral_constant<int, 8>());
+    }
+}
+
+// Tile id of the lower triangle (row-major: id = ti (ti + 1) / 2 + tj, tj <= ti) -> (ti, tj)
+static __device__ __forceinline__ void lower_tile_of(int id, int& ti, int& tj)
+{
+    ti = (int)((sqrtf(8.0f * (float)id + 1.0f) - 1.0f) * 0.5f);
+    while (ti * (ti + 1) / 2 > id) --ti;
+    while ((ti + 1) * (ti + 2) / 2 <= id) ++ti;
+    tj = id - ti * (ti + 1) / 2;
+}
+
+// Every policy has value(d2, df0, c, sf2) = k and pair(d2, df0, c, sf2, k, g, dl), what the derivative kernels need of
+// one pair of points: k, g with dk/da_e = -g (a_e - b_e), and dl = dk / dlog l.  df0 is the first difference: the
+// Matern policies take r = |df0| when D = 1.
 template <int COV> struct Cov;
 
 template <> struct Cov<CIMRGP_COV_RBF> {
     template <typename T, int D> static __device__ __forceinline__ T value(T d2, T, T c, T sf2) { return sf2 * exp(d2 * c); }
+    template <typename T, int D> static __device__ __forceinline__ void pair(T d2, T df0, T c, T sf2, T& k, T& g, T& dl)
+    {
+        k = value<T, D>(d2, df0, c, sf2);
+        g = k * ((T)-2 * c);
+        dl = g * d2;
+    }
 };
 
 // Matern policies: value(d2) and, for the gradient of the log marginal likelihood w.r.t. log l,
 //   dlogl = -r dk/dr  (isotropic: d k / d log l)
-//   ard   = -(dk/dr) / r  (per dimension with pre-scaled inputs: d k / d log l_k = ard * (x_k - x'_k)^2)
+//   ard   = -(dk/dr) / r  (per dimension with pre-scaled inputs: d k / d log l_k = ard * (x_k - x'_k)^2; it is also g)
 // both finite at r = 0 except ard for nu = 1/2, which is defined as 0 there (every (x_k - x'_k)^2 is 0 too).
 template <int COV> struct MaternCov {
     template <typename T> static __device__ __forceinline__ T poly(T t)
@@ -296,6 +348,15 @@ template <int COV> struct MaternCov {
         if (COV == CIMRGP_COV_MATERN12) return r > (T)0 ? sf2 * c * v / r : (T)0;
         if (COV == CIMRGP_COV_MATERN32) return c * c * sf2 * v;
         return c * c * sf2 * ((T)1 + t) * v * (T)(1.0 / 3.0);
+    }
+    template <typename T, int D> static __device__ __forceinline__ void pair(T d2, T df0, T c, T sf2, T& k, T& g, T& dl)
+    {
+        const T r = radius<T, D>(d2, df0);
+        const T t = c * r;
+        const T v = exp(-t);
+        k = sf2 * poly(t) * v;
+        g = ard(t, r, v, c, sf2);
+        dl = dlogl(t, v, sf2);
     }
 };
 template <> struct Cov<CIMRGP_COV_MATERN12> : MaternCov<CIMRGP_COV_MATERN12> {};

@@ -162,25 +162,8 @@ void k_rows_lt_update(T* __restrict__ B, int64_t ldb, int m, int c0, int w, cons
         }
 }
 
-// --------------------------------------------------------------------- g(r) per policy ----
-// dk/dx*_e = -g (x*_e - x_e).  c is the policy's scale (cov_scale: RBF -1 / (2 l^2), Matern sqrt(2 nu) / l).
-template <int COV, typename T, int D>
-static __device__ __forceinline__ T grad_g(T d2, T df0, T c, T sf2)
-{
-    if constexpr (COV == CIMRGP_COV_RBF) {
-        return sf2 * exp(d2 * c) * ((T)-2 * c);
-    } else {
-        const T r = D == 1 ? fabs(df0) : sqrt(d2);
-        const T t = c * r;
-        const T v = exp(-t);
-        if constexpr (COV == CIMRGP_COV_MATERN12) return r > (T)0 ? sf2 * c * v / r : (T)0;
-        else if constexpr (COV == CIMRGP_COV_MATERN32) return c * c * sf2 * v;
-        else return c * c * sf2 * ((T)1 + t) * v * (T)(1.0 / 3.0);
-    }
-}
-
 // ------------------------------------------------------------------- the contraction ----
-// 256 threads = 8 test points x 32 phases (32 consecutive lanes per test point: their beta reads are one contiguous
+// dk/dx*_e = -g (x*_e - x_e), g of the policy's pair() (common.hpp; c is the policy's scale, cov_scale).  256 threads = 8 test points x 32 phases (32 consecutive lanes per test point: their beta reads are one contiguous
 // 32-element segment of the row, and the reduction over the phases stays inside half a wave -- shuffles, no LDS).
 // blockIdx.y = block of a batch (starts / t_starts NULL: one block at offset 0).
 constexpr int PG_TS = 8;
@@ -225,7 +208,8 @@ void k_cov_predict_grad(const T* __restrict__ x, const int64_t* __restrict__ sta
             df[k] = (D || k < d) ? xt[k] - x[(int64_t)j * d + k] : (T)0;
             d2 += df[k] * df[k];
         }
-        const T g = grad_g<COV, T, D>(d2, df[0], c, sf2);
+        T kv, g, lv;
+        Cov<COV>::template pair<T, D>(d2, df[0], c, sf2, kv, g, lv);
         if (want_mean) {
 #pragma unroll
             for (int cc = 0; cc < Q; ++cc) {
@@ -309,24 +293,14 @@ static int predict_grad_run_cov(const LayerGrad<T>& a, const T* beta, hipStream_
 {
     if (a.te.n <= 0 || (a.mg == nullptr && a.vg == nullptr)) return 0;
     const dim3 grid((unsigned)((a.te.n + PG_TS - 1) / PG_TS), (unsigned)a.bc.batch);
-    const int d = a.bc.d;
     const T c = (T)cov_scale(COV, a.bc.ell);
-#define CIMRGP_PG_LAUNCH(D_, Q_)                                                                                             \
-    hipLaunchKernelGGL((k_cov_predict_grad<T, COV, D_, Q_>), grid, dim3(256), 0, st, a.tr.x, a.tr.starts, (int)a.tr.n, d, a.alpha, \
-                       a.sa, a.q, a.te.x, a.te.starts, (int)a.te.n, c, (T)a.bc.sf2, beta, a.w.ld, a.w.stride, a.mg, a.vg, a.accumulate)
-#define CIMRGP_PG_D(Q_)                             \
-    { if (d == 1)      CIMRGP_PG_LAUNCH(1, Q_);     \
-      else if (d == 2) CIMRGP_PG_LAUNCH(2, Q_);     \
-      else             CIMRGP_PG_LAUNCH(0, Q_); }
-    switch (a.q) {
-        case 1: CIMRGP_PG_D(1); break;
-        case 2: CIMRGP_PG_D(2); break;
-        case 3: CIMRGP_PG_D(3); break;
-        case 4: CIMRGP_PG_D(4); break;
-        default: CIMRGP_PG_D(8); break;           // 5 .. 8: the run-time guard c < q
-    }
-#undef CIMRGP_PG_D
-#undef CIMRGP_PG_LAUNCH
+    with_q_rounded(a.q, [&](auto qq) {            // 5 .. 8: the run-time guard c < q
+        with_dim(a.bc.d, [&](auto dd) {
+            hipLaunchKernelGGL((k_cov_predict_grad<T, COV, decltype(dd)::value, decltype(qq)::value>), grid, dim3(256), 0, st, a.tr.x,
+                               a.tr.starts, (int)a.tr.n, a.bc.d, a.alpha, a.sa, a.q, a.te.x, a.te.starts, (int)a.te.n, c, (T)a.bc.sf2, beta,
+                               a.w.ld, a.w.stride, a.mg, a.vg, a.accumulate);
+        });
+    });
     CIMRGP_LAUNCH_CHECK(fn);
     return 0;
 }

@@ -188,7 +188,7 @@ CIMRGP_INST(float)
 // matrix is re-evaluated on the fly from X, nothing n x n besides K^-1 is read.  Per-tile
 // partial sums, then a fixed-order final reduction (deterministic).
 // The Matern policies (common.hpp) replace sf E_ij by k_ij and sf E_ij d2_ij / l^2 by their
-// d k / d log l (k_cov_lml_grad_tiles<T, COV, ARD>; the RBF instance keeps its name).
+// d k / d log l: one kernel, k_lml_grad_tiles<T, COV, ARD>, whose RBF arm keeps the expressions above.
 // ---------------------------------------------------------------------------
 namespace cimrgp {
 namespace {
@@ -212,10 +212,11 @@ struct LgBatch { const int64_t* starts; int64_t ks; };
         partial += b_ * (int64_t)gridDim.x * (NP);          \
     }
 
-template <typename T, bool ARD, bool BATCHED = false>
+// c = cov_scale(COV, l); inv_l2 = 1 / l^2 is read by the RBF alone.
+template <typename T, int COV, bool ARD, bool BATCHED = false>
 __global__ __launch_bounds__(256)
 void k_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict__ kinv, int64_t ld,
-                      const T* __restrict__ alpha, int q, T neg_half_inv_l2, T sf2, T inv_l2,
+                      const T* __restrict__ alpha, int q, T c, T sf2, T inv_l2,
                       double* __restrict__ partial, LgBatch bb)
 {
     CIMRGP_LG_BLOCK(ARD ? LG_NP : 3)
@@ -223,10 +224,8 @@ void k_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict
     __shared__ T aa[LG_T * 8], ab[LG_T * 8];
     __shared__ double red[ARD ? LG_NP : 3][4];
     const int id = blockIdx.x;
-    int ti = (int)((sqrtf(8.0f * (float)id + 1.0f) - 1.0f) * 0.5f);
-    while (ti * (ti + 1) / 2 > id) --ti;
-    while ((ti + 1) * (ti + 2) / 2 <= id) ++ti;
-    const int tj = id - ti * (ti + 1) / 2;
+    int ti, tj;
+    lower_tile_of(id, ti, tj);
     const int row0 = ti * LG_T, col0 = tj * LG_T;
     const int tid = threadIdx.x;
     for (int e = tid; e < LG_T * MAXD; e += 256) {
@@ -258,106 +257,28 @@ void k_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict
 #pragma unroll
             for (int k = 0; k < 8; ++k) aat += aa[rr * 8 + k] * ab[tx * 8 + k];
             const T g = aat - (T)q * kinv[(int64_t)gr * ld + gc];
-            const T kf = sf2 * exp(d2 * neg_half_inv_l2);
             const double wgt = (gr == gc) ? 1.0 : 2.0;
-            s_sf += wgt * (double)(g * kf);
-            if (ARD) {
-#pragma unroll
-                for (int k = 0; k < MAXD; ++k) s_lk[k] += wgt * (double)(g * kf * dk2[k]);
+            // kf = k_ij; gk dk2[k] = g dk_ij/dlog l_k (ARD); gl = g dk_ij/dlog l
+            T kf, gk, gl;
+            if constexpr (COV == CIMRGP_COV_RBF) {
+                kf = sf2 * exp(d2 * c);
+                // the RBF's own products, not pair()'s: (g kf) leads, and inv_l2 = 1 / l^2 is a factor rounded on its own
+                gk = g * kf;
+                gl = g * kf * d2 * inv_l2;
             } else {
-                s_l  += wgt * (double)(g * kf * d2 * inv_l2);
+                // r from d2 (a sum of squares: exactly 0 on the diagonal); d = 1 takes |df| as the Gram kernels do
+                const T r = d == 1 ? fabs(sa[rr * MAXD] - sb[tx * MAXD]) : sqrt(d2);
+                const T t = c * r, v = exp(-t);
+                kf = sf2 * Cov<COV>::poly(t) * v;
+                gk = g * Cov<COV>::ard(t, r, v, c, sf2);
+                gl = g * Cov<COV>::dlogl(t, v, sf2);
             }
-            if (gr == gc) s_tr += (double)g;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s_sf += __shfl_xor(s_sf, off, 64);
-        s_l  += __shfl_xor(s_l, off, 64);
-        s_tr += __shfl_xor(s_tr, off, 64);
-        if (ARD) {
-#pragma unroll
-            for (int k = 0; k < MAXD; ++k) s_lk[k] += __shfl_xor(s_lk[k], off, 64);
-        }
-    }
-    if (ARD) {
-        if (tx == 0) {
-            red[0][ty] = s_sf;
-#pragma unroll
-            for (int k = 0; k < MAXD; ++k) red[1 + k][ty] = s_lk[k];
-            red[LG_NP - 1][ty] = s_tr;
-        }
-        __syncthreads();
-        if (tid < LG_NP) partial[(int64_t)id * LG_NP + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
-    } else {
-        if (tx == 0) { red[0][ty] = s_sf; red[1][ty] = s_l; red[2][ty] = s_tr; }
-        __syncthreads();
-        if (tid < 3) partial[(int64_t)id * 3 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
-    }
-}
-
-// The Matern policies' tile: k_lml_grad_tiles' staging and reductions with k_ij and d k_ij / d log l of policy COV.
-// (The RBF kernel above keeps its own body, so that its code -- and its FP32 contraction of d2 -- stays as it was.)
-// c = cov_scale(COV, l); inv_l2 is not read.
-template <typename T, int COV, bool ARD, bool BATCHED>
-static __device__ __forceinline__ void lml_grad_tile(const T* __restrict__ x, int n, int d, const T* __restrict__ kinv, int64_t ld,
-                                                     const T* __restrict__ alpha, int q, T c, T sf2, T inv_l2,
-                                                     double* __restrict__ partial, const LgBatch& bb)
-{
-    static_assert(COV != CIMRGP_COV_RBF, "the RBF gradient is k_lml_grad_tiles");
-    (void)inv_l2;
-    CIMRGP_LG_BLOCK(ARD ? LG_NP : 3)
-    __shared__ T sa[LG_T * MAXD], sb[LG_T * MAXD];
-    __shared__ T aa[LG_T * 8], ab[LG_T * 8];
-    __shared__ double red[ARD ? LG_NP : 3][4];
-    const int id = blockIdx.x;
-    int ti = (int)((sqrtf(8.0f * (float)id + 1.0f) - 1.0f) * 0.5f);
-    while (ti * (ti + 1) / 2 > id) --ti;
-    while ((ti + 1) * (ti + 2) / 2 <= id) ++ti;
-    const int tj = id - ti * (ti + 1) / 2;
-    const int row0 = ti * LG_T, col0 = tj * LG_T;
-    const int tid = threadIdx.x;
-    for (int e = tid; e < LG_T * MAXD; e += 256) {
-        const int r = e / MAXD, k = e - r * MAXD;
-        sa[e] = (k < d && row0 + r < n) ? x[(int64_t)(row0 + r) * d + k] : (T)0;
-        sb[e] = (k < d && col0 + r < n) ? x[(int64_t)(col0 + r) * d + k] : (T)0;
-        aa[e] = (k < q && row0 + r < n) ? alpha[(int64_t)(row0 + r) * q + k] : (T)0;
-        ab[e] = (k < q && col0 + r < n) ? alpha[(int64_t)(col0 + r) * q + k] : (T)0;
-    }
-    __syncthreads();
-    const int tx = tid & 63, ty = tid >> 6;
-    double s_sf = 0.0, s_l = 0.0, s_tr = 0.0;
-    double s_lk[ARD ? MAXD : 1];
-#pragma unroll
-    for (int k = 0; k < (ARD ? MAXD : 1); ++k) s_lk[k] = 0.0;
-    const int gc = col0 + tx;
-    for (int rr = ty; rr < LG_T; rr += 4) {
-        const int gr = row0 + rr;
-        if (gr < n && gc < n && gc <= gr) {
-            T d2 = (T)0;
-            T dk2[MAXD];
-#pragma unroll
-            for (int k = 0; k < MAXD; ++k) {
-                const T df = sa[rr * MAXD + k] - sb[tx * MAXD + k];
-                dk2[k] = df * df;
-                d2 += dk2[k];
-            }
-            T aat = (T)0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) aat += aa[rr * 8 + k] * ab[tx * 8 + k];
-            const T g = aat - (T)q * kinv[(int64_t)gr * ld + gc];
-            const double wgt = (gr == gc) ? 1.0 : 2.0;
-            // r from d2 (a sum of squares: exactly 0 on the diagonal); d = 1 takes |df| as the Gram kernels do
-            const T r = d == 1 ? fabs(sa[rr * MAXD] - sb[tx * MAXD]) : sqrt(d2);
-            const T t = c * r, v = exp(-t);
-            const T kf = sf2 * Cov<COV>::poly(t) * v;
             s_sf += wgt * (double)(g * kf);
             if (ARD) {
-                const T gk = g * Cov<COV>::ard(t, r, v, c, sf2);
 #pragma unroll
                 for (int k = 0; k < MAXD; ++k) s_lk[k] += wgt * (double)(gk * dk2[k]);
             } else {
-                s_l  += wgt * (double)(g * Cov<COV>::dlogl(t, v, sf2));
+                s_l  += wgt * (double)gl;
             }
             if (gr == gc) s_tr += (double)g;
         }
@@ -386,19 +307,6 @@ static __device__ __forceinline__ void lml_grad_tile(const T* __restrict__ x, in
         __syncthreads();
         if (tid < 3) partial[(int64_t)id * 3 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
     }
-}
-
-template <typename T, int COV, bool ARD, bool BATCHED = false>
-__global__ __launch_bounds__(256)
-void k_cov_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict__ kinv, int64_t ld,
-                          const T* __restrict__ alpha, int q, T c, T sf2, T inv_l2, double* __restrict__ partial, LgBatch bb)
-{
-    lml_grad_tile<T, COV, ARD, BATCHED>(x, n, d, kinv, ld, alpha, q, c, sf2, inv_l2, partial, bb);
-}
-
-template <typename T, int COV, bool ARD, bool BATCHED = false> static auto lml_grad_kernel()
-{
-    if constexpr (COV == CIMRGP_COV_RBF) return k_lml_grad_tiles<T, ARD, BATCHED>; else return k_cov_lml_grad_tiles<T, COV, ARD, BATCHED>;
 }
 
 __global__ __launch_bounds__(1024)
@@ -431,12 +339,12 @@ static int lml_grad_run_cov(const T* x, int64_t n, int d, const T* kinv, int64_t
     CIMRGP_REQUIRE(tiles < (1ll << 31), fn, "grid too large");
     if (ard) {
         // inputs are pre-scaled by the length-scales: unit length-scale here; out = [sf | l_1..l_d | noise]
-        hipLaunchKernelGGL((lml_grad_kernel<T, COV, true>()), dim3((unsigned)tiles), dim3(256), 0, st, x, (int)n, d, kinv, ld, alpha, q,
+        hipLaunchKernelGGL((k_lml_grad_tiles<T, COV, true>), dim3((unsigned)tiles), dim3(256), 0, st, x, (int)n, d, kinv, ld, alpha, q,
                            (T)cov_scale(COV, 1.0), (T)sf2, (T)1, scratch, LgBatch{nullptr, 0});
         CIMRGP_LAUNCH_CHECK(fn);
         hipLaunchKernelGGL(k_lml_grad_final, dim3(1), dim3(1024), 0, st, (const double*)scratch, tiles, noise, out3, LG_NP, d + 2);
     } else {
-        hipLaunchKernelGGL((lml_grad_kernel<T, COV, false>()), dim3((unsigned)tiles), dim3(256), 0, st, x, (int)n, d, kinv, ld, alpha, q,
+        hipLaunchKernelGGL((k_lml_grad_tiles<T, COV, false>), dim3((unsigned)tiles), dim3(256), 0, st, x, (int)n, d, kinv, ld, alpha, q,
                            (T)cov_scale(COV, ell), (T)sf2, (T)(1.0 / (ell * ell)), scratch, LgBatch{nullptr, 0});
         CIMRGP_LAUNCH_CHECK(fn);
         hipLaunchKernelGGL(k_lml_grad_final, dim3(1), dim3(1024), 0, st, (const double*)scratch, tiles, noise, out3, 3, 3);
@@ -519,7 +427,7 @@ int lml_grad_batched_run(const T* x, const int64_t* starts, int batch, int64_t n
     const LgBatch bb{starts, ks};
     const int rc = with_cov(cov, [&](auto c) {
         constexpr int COV = decltype(c)::value;
-        hipLaunchKernelGGL((lml_grad_kernel<T, COV, false, true>()), dim3((unsigned)tiles, (unsigned)batch), dim3(256), 0, st, x, (int)n,
+        hipLaunchKernelGGL((k_lml_grad_tiles<T, COV, false, true>), dim3((unsigned)tiles, (unsigned)batch), dim3(256), 0, st, x, (int)n,
                            d, kinv, ld, alpha, q, (T)cov_scale(COV, ell), (T)sf2, (T)(1.0 / (ell * ell)), partial, bb);
         CIMRGP_LAUNCH_CHECK(fn);
         return 0;

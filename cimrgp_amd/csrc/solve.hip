@@ -375,22 +375,10 @@ void k_predict_from_w(const T* __restrict__ W, int ns, int n, int64_t ldw, const
 
 }  // namespace
 
-// Dispatch the run-time number of right-hand sides to a compile-time constant QQ.
-#define CIMRGP_Q_SWITCH(q_, ...)                                   \
-    switch (q_) {                                                  \
-        case 1: { constexpr int QQ = 1; __VA_ARGS__; } break;      \
-        case 2: { constexpr int QQ = 2; __VA_ARGS__; } break;      \
-        case 3: { constexpr int QQ = 3; __VA_ARGS__; } break;      \
-        case 4: { constexpr int QQ = 4; __VA_ARGS__; } break;      \
-        case 5: { constexpr int QQ = 5; __VA_ARGS__; } break;      \
-        case 6: { constexpr int QQ = 6; __VA_ARGS__; } break;      \
-        case 7: { constexpr int QQ = 7; __VA_ARGS__; } break;      \
-        default: { constexpr int QQ = 8; __VA_ARGS__; } break;     \
-    }
-
-template <typename T>
-int potrs_run(const T* l, int64_t n, int64_t ld, const T* ws, T* rhs, int q, T* z_out, T* scratch,
-              bool backward_only, hipStream_t st, PotrfBatch bt, bool work_ready)
+// QQ = q, the number of right-hand sides, at compile time (potrs_run dispatches)
+template <typename T, int QQ>
+static int potrs_run_q(const T* l, int64_t n, int64_t ld, const T* ws, T* rhs, int q, T* z_out, T* scratch,
+                       bool backward_only, hipStream_t st, PotrfBatch bt, bool work_ready)
 {
     const char* fn = "cimrgp_potrs";
     if (n <= 0) return 0;
@@ -416,12 +404,12 @@ int potrs_run(const T* l, int64_t n, int64_t ld, const T* ws, T* rhs, int q, T* 
         const int w = (int)((n - k0 < PW) ? (n - k0) : PW);
         const int64_t below = n - (k0 + w);
         const unsigned grid = (unsigned)((below + FWD_ROWS - 1) / FWD_ROWS);
-        CIMRGP_Q_SWITCH(q, hipLaunchKernelGGL((k_fwd_alpha<T, QQ>), dim3((unsigned)((w + 15) / 16)), dim3(ST), 0, st,
-                                              invT, (int)n, (const T*)work, res, (int)k0, w));
+        hipLaunchKernelGGL((k_fwd_alpha<T, QQ>), dim3((unsigned)((w + 15) / 16)), dim3(ST), 0, st,
+                           invT, (int)n, (const T*)work, res, (int)k0, w);
         CIMRGP_LAUNCH_CHECK(fn);
         if (grid) {
-            CIMRGP_Q_SWITCH(q, hipLaunchKernelGGL((k_fwd_update<T, QQ>), dim3(grid), dim3(ST), 0, st, l, ld, (int)n,
-                                                  work, (const T*)res, (int)k0, w));
+            hipLaunchKernelGGL((k_fwd_update<T, QQ>), dim3(grid), dim3(ST), 0, st, l, ld, (int)n,
+                               work, (const T*)res, (int)k0, w);
             CIMRGP_LAUNCH_CHECK(fn);
         }
     }
@@ -442,38 +430,47 @@ int potrs_run(const T* l, int64_t n, int64_t ld, const T* ws, T* rhs, int q, T* 
     for (int64_t k0 = last; k0 >= 2 * npairs * PW; k0 -= PW) {    // what lies behind the pairs: at most two panels, singly
         const int w = (int)((n - k0 < PW) ? (n - k0) : PW);
         const unsigned grid = (unsigned)((k0 + SB - 1) / SB);
-        CIMRGP_Q_SWITCH(q, hipLaunchKernelGGL((k_bwd_alpha<T, QQ>), dim3((unsigned)((w + 3) / 4), nbatch), dim3(256), 0, st,
-                                              invT, (int)n, (const T*)work, res, (int)k0, w, bt.sws, sscr));
+        hipLaunchKernelGGL((k_bwd_alpha<T, QQ>), dim3((unsigned)((w + 3) / 4), nbatch), dim3(256), 0, st,
+                           invT, (int)n, (const T*)work, res, (int)k0, w, bt.sws, sscr);
         CIMRGP_LAUNCH_CHECK(fn);
         if (grid && narrow) {
-            CIMRGP_Q_SWITCH(q, hipLaunchKernelGGL((k_bwd_update<T, QQ, PW, LINE>), dim3((unsigned)((k0 + LINE - 1) / LINE), nbatch), dim3(ST), 0, st,
-                                                  l, ld, (int)n, work, (const T*)res, (int)k0, w, bt.sk, sscr));
+            hipLaunchKernelGGL((k_bwd_update<T, QQ, PW, LINE>), dim3((unsigned)((k0 + LINE - 1) / LINE), nbatch), dim3(ST), 0, st,
+                               l, ld, (int)n, work, (const T*)res, (int)k0, w, bt.sk, sscr);
             CIMRGP_LAUNCH_CHECK(fn);
         } else if (grid) {
-            CIMRGP_Q_SWITCH(q, hipLaunchKernelGGL((k_bwd_update<T, QQ>), dim3(grid, nbatch), dim3(ST), 0, st, l, ld, (int)n,
-                                                  work, (const T*)res, (int)k0, w, bt.sk, sscr));
+            hipLaunchKernelGGL((k_bwd_update<T, QQ>), dim3(grid, nbatch), dim3(ST), 0, st, l, ld, (int)n,
+                               work, (const T*)res, (int)k0, w, bt.sk, sscr);
             CIMRGP_LAUNCH_CHECK(fn);
         }
     }
     for (int64_t j = npairs - 1; j >= 0; --j) {
         const int64_t k0 = 2 * PW * j;
         const unsigned grid = (unsigned)((k0 + SB - 1) / SB);
-        CIMRGP_Q_SWITCH(q, hipLaunchKernelGGL((k_bwd_alpha2<T, QQ>), dim3(2 * PW / 4, nbatch), dim3(256), 0, st,
-                                              invT, xoff, (int)n, (const T*)work, res, (int)k0, bt.sws, sscr));
+        hipLaunchKernelGGL((k_bwd_alpha2<T, QQ>), dim3(2 * PW / 4, nbatch), dim3(256), 0, st,
+                           invT, xoff, (int)n, (const T*)work, res, (int)k0, bt.sws, sscr);
         CIMRGP_LAUNCH_CHECK(fn);
         if (grid && narrow) {
-            CIMRGP_Q_SWITCH(q, hipLaunchKernelGGL((k_bwd_update<T, QQ, 2 * PW, LINE>), dim3((unsigned)((k0 + LINE - 1) / LINE), nbatch), dim3(ST), 0, st,
-                                                  l, ld, (int)n, work, (const T*)res, (int)k0, 2 * PW, bt.sk, sscr));
+            hipLaunchKernelGGL((k_bwd_update<T, QQ, 2 * PW, LINE>), dim3((unsigned)((k0 + LINE - 1) / LINE), nbatch), dim3(ST), 0, st,
+                               l, ld, (int)n, work, (const T*)res, (int)k0, 2 * PW, bt.sk, sscr);
             CIMRGP_LAUNCH_CHECK(fn);
         } else if (grid) {
-            CIMRGP_Q_SWITCH(q, hipLaunchKernelGGL((k_bwd_update<T, QQ, 2 * PW>), dim3(grid, nbatch), dim3(ST), 0, st, l, ld, (int)n,
-                                                  work, (const T*)res, (int)k0, 2 * PW, bt.sk, sscr));
+            hipLaunchKernelGGL((k_bwd_update<T, QQ, 2 * PW>), dim3(grid, nbatch), dim3(ST), 0, st, l, ld, (int)n,
+                               work, (const T*)res, (int)k0, 2 * PW, bt.sk, sscr);
             CIMRGP_LAUNCH_CHECK(fn);
         }
     }
     hipLaunchKernelGGL((k_transpose_nq<T>), dim3(tg, nbatch), dim3(256), 0, st, (const T*)res, rhs, n, q, 0, sscr, srhs);
     CIMRGP_LAUNCH_CHECK(fn);
     return 0;
+}
+
+template <typename T>
+int potrs_run(const T* l, int64_t n, int64_t ld, const T* ws, T* rhs, int q, T* z_out, T* scratch,
+              bool backward_only, hipStream_t st, PotrfBatch bt, bool work_ready)
+{
+    return with_q(q, [&](auto qq) {
+        return potrs_run_q<T, decltype(qq)::value>(l, n, ld, ws, rhs, q, z_out, scratch, backward_only, st, bt, work_ready);
+    });
 }
 
 template <typename T>
@@ -486,9 +483,10 @@ int predict_from_w_run(const T* w, int64_t ns, int64_t n, int64_t ldw, const T* 
     CIMRGP_REQUIRE(q >= 0 && q <= MAXQ, fn, "number of outputs must be <= 8");
     CIMRGP_REQUIRE(ns < (1ll << 31) && n < (1ll << 31) && batch < 65536, fn, "too many points");
     CIMRGP_REQUIRE(batch == 1 || t_starts != nullptr, fn, "a batch needs the blocks' test offsets");
-    CIMRGP_Q_SWITCH(q > 0 ? q : 1, hipLaunchKernelGGL((k_predict_from_w<T, QQ>), dim3((unsigned)ns, (unsigned)batch), dim3(256), 0, st,
-                                                      w, (int)ns, (int)n, ldw, z, q, (T)(sf2 + extra), extra_dev, bias, mean, var, accumulate,
-                                                      t_starts, sw));
+    with_q(q > 0 ? q : 1, [&](auto qq) {
+        hipLaunchKernelGGL((k_predict_from_w<T, decltype(qq)::value>), dim3((unsigned)ns, (unsigned)batch), dim3(256), 0, st, w, (int)ns,
+                           (int)n, ldw, z, q, (T)(sf2 + extra), extra_dev, bias, mean, var, accumulate, t_starts, sw);
+    });
     CIMRGP_LAUNCH_CHECK(fn);
     return 0;
 }

@@ -44,25 +44,7 @@ static inline bool pg_sizes_ok(int64_t na, int64_t nb, int d)
 static inline int64_t pg_dbpart_elems(int64_t na, int64_t nb, int d) { return pg_slices(na, nb) * pg_tiles(nb) * PG_CT * d; }
 static inline int64_t pg_sumpart_elems(int64_t na, int64_t nb) { return pg_slices(na, nb) * pg_tiles(nb) * 2; }
 
-// k, g (dk/da_e = -g (a_e - b_e)) and dk/dlog l of one pair from the squared distance, in the dtype: the Cov<COV>
-// policies' expressions (common.hpp), and grad.hip's g(r).
-template <int COV, typename T, int D>
-static __device__ __forceinline__ void pair_terms(T d2, T df0, T c, T sf2, T& kv, T& gv, T& lv)
-{
-    if constexpr (COV == CIMRGP_COV_RBF) {
-        kv = Cov<COV>::template value<T, D>(d2, df0, c, sf2);
-        gv = kv * ((T)-2 * c);
-        lv = gv * d2;
-    } else {
-        const T r = Cov<COV>::template radius<T, D>(d2, df0);
-        const T t = c * r;
-        const T v = exp(-t);
-        kv = sf2 * Cov<COV>::poly(t) * v;
-        gv = Cov<COV>::ard(t, r, v, c, sf2);
-        lv = Cov<COV>::dlogl(t, v, sf2);
-    }
-}
-
+// k, g (dk/da_e = -g (a_e - b_e)) and dk/dlog l of one pair: the policy's pair() (common.hpp), in the dtype.
 // blockIdx.x = tile + tiles * slice.
 template <typename T, int COV, int D>
 __global__ __launch_bounds__(256)
@@ -126,7 +108,7 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
                 d2 += df[k] * df[k];
             }
             T kv, gv, lv;
-            pair_terms<COV, T, D>(d2, df[0], c, sf2, kv, gv, lv);
+            Cov<COV>::template pair<T, D>(d2, df[0], c, sf2, kv, gv, lv);
             const double w = (double)gcur[b];
             sk += w * (double)kv;
             sl += w * (double)lv;
@@ -320,13 +302,10 @@ static int pair_grad_run_cov(const T* xa, int64_t na, const T* xb, int64_t nb, i
     double* sumpart = scratch + pg_dbpart_elems(na, nb, d);
     const dim3 grid((unsigned)(tiles * slices));
     const T c = (T)cov_scale(COV, ell);
-#define CIMRGP_PAIR_LAUNCH(D_)                                                                                                  \
-    hipLaunchKernelGGL((k_cov_pair_grad<T, COV, D_>), grid, dim3(256), 0, st, xa, (int)na, xb, (int)nb, d, g, ldg, c, (T)sf2,   \
-                       (int)tiles, (int)len, db != nullptr ? 1 : 0, dbpart, sumpart)
-    if (d == 1)      CIMRGP_PAIR_LAUNCH(1);
-    else if (d == 2) CIMRGP_PAIR_LAUNCH(2);
-    else             CIMRGP_PAIR_LAUNCH(0);
-#undef CIMRGP_PAIR_LAUNCH
+    with_dim(d, [&](auto dd) {
+        hipLaunchKernelGGL((k_cov_pair_grad<T, COV, decltype(dd)::value>), grid, dim3(256), 0, st, xa, (int)na, xb, (int)nb, d, g, ldg, c,
+                           (T)sf2, (int)tiles, (int)len, db != nullptr ? 1 : 0, dbpart, sumpart);
+    });
     CIMRGP_LAUNCH_CHECK(fn);
     const int64_t dblocks = db != nullptr ? (nb * d + 255) / 256 : 0;
     hipLaunchKernelGGL((k_pair_grad_reduce<T>), dim3((unsigned)(dblocks + (sums != nullptr ? 1 : 0))), dim3(256), 0, st,

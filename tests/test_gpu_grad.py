@@ -100,7 +100,7 @@ def test_trsm_rows_lt_batched_equals_single(dev, dt):
 # ---- the contraction ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cov", [0, 1, 2, 3])
 @pytest.mark.parametrize("d", [1, 2, 3])
-@pytest.mark.parametrize("q", [1, 3])
+@pytest.mark.parametrize("q", [1, 3, 4, 5, 8])
 def test_cov_predict_grad_matches_numpy(dev, cov, d, q):
     rng = np.random.default_rng(100 * cov + 10 * d + q)
     n, ns, ell, sf2 = 300, 45, 0.7, 1.3

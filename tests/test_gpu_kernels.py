@@ -271,7 +271,7 @@ def test_potrf_reports_first_bad_pivot(dev):
 
 
 @pytest.mark.parametrize("dt,tol", [("f64", 1e-9), ("f32", 5e-3)])
-@pytest.mark.parametrize("n,q", [(1, 2), (64, 2), (65, 1), (257, 3), (700, 2), (1025, 8)])
+@pytest.mark.parametrize("n,q", [(1, 2), (64, 2), (65, 1), (257, 3), (700, 2), (1025, 8), (300, 4), (300, 5), (300, 6), (300, 7)])
 def test_potrs(dev, dt, tol, n, q):
     x, y = _data(n, 1, seed=n, q=max(q, 2))
     y = y[:, :q]
@@ -320,10 +320,9 @@ def test_trsm_rows_f64(dev, n, m):
     assert _relerr(w[:m, :n].cpu().numpy(), ref) < 1e-9
 
 
-@pytest.mark.parametrize("dt,tol", [("f64", 1e-9), ("f32", 2e-3)])
-@pytest.mark.parametrize("n,ns,d", [(64, 1, 1), (257, 37, 2), (600, 1000, 1)])
-def test_predict_mean_and_variance(dev, dt, tol, n, ns, d):
-    x, y = _data(n, d, seed=n)
+def _check_predict_mean_and_variance(dev, dt, tol, n, ns, d, q=2):
+    x, y = _data(n, d, seed=n, q=max(q, 2))
+    y = y[:, :q]
     xs, _ = _data(ns, d, seed=n + 7)
     ell, sf2, noise = 0.4, 1.3, 0.02
     tdt = getattr(torch, TDT[dt])
@@ -331,23 +330,38 @@ def test_predict_mean_and_variance(dev, dt, tol, n, ns, d):
     alpha = dev.to_device(y, tdt, "cuda")
     z = dev.potrs(kbuf, n, ws, alpha, want_z=True)
     xsd = dev.to_device(xs, tdt, "cuda")
-    bias = dev.to_device(np.array([0.25, -1.5]), tdt, "cuda")
+    b = np.array([0.25, -1.5, 0.5, 2.0, -0.75, 1.25, -2.5, 0.125])[:q]
+    bias = dev.to_device(b, tdt, "cuda")
     fit = oracle.block_fit(x, y, ell, sf2, noise)
     mref, vref = oracle.block_predict(x, fit, xs, ell, sf2, True)
     # D4 fused mean, overwrite then accumulate
     m1 = dev.predict_mean(xd, alpha, xsd, ell, sf2, bias)
-    assert _relerr(m1.double().cpu().numpy(), mref + np.array([0.25, -1.5])) < tol
+    assert _relerr(m1.double().cpu().numpy(), mref + b) < tol
     dev.predict_mean(xd, alpha, xsd, ell, sf2, None, out=m1, accumulate=True)
-    assert _relerr(m1.double().cpu().numpy(), 2 * mref + np.array([0.25, -1.5])) < tol
+    assert _relerr(m1.double().cpu().numpy(), 2 * mref + b) < tol
     # D5 through W = K* L^-T
     w = dev.rbf_cross(xsd, xd, ell, sf2)
     dev.trsm_rows(kbuf, n, ws, w, ns)
-    mean = torch.zeros((ns, 2), dtype=tdt, device="cuda")
+    mean = torch.zeros((ns, q), dtype=tdt, device="cuda")
     var = torch.zeros(ns, dtype=tdt, device="cuda")
     dev.predict_from_w(w, ns, n, z, sf2, 0.0, None, mean, var, accumulate=False)
     assert _relerr(mean.double().cpu().numpy(), mref) < tol
     # variance is a difference of near-equal numbers: compare on the scale of sf2
     assert float(np.max(np.abs(var.double().cpu().numpy() - vref))) / sf2 < tol
+
+
+@pytest.mark.parametrize("dt,tol", [("f64", 1e-9), ("f32", 2e-3)])
+@pytest.mark.parametrize("n,ns,d", [(64, 1, 1), (257, 37, 2), (600, 1000, 1)])
+def test_predict_mean_and_variance(dev, dt, tol, n, ns, d):
+    _check_predict_mean_and_variance(dev, dt, tol, n, ns, d)
+
+
+@pytest.mark.parametrize("dt,tol", [("f64", 1e-9), ("f32", 2e-3)])
+@pytest.mark.parametrize("q", [1, 2, 3, 4, 5, 6, 7, 8])
+@pytest.mark.parametrize("d", [1, 2, 3])
+def test_predict_mean_and_variance_every_d_and_q(dev, dt, tol, d, q):
+    """Every arm of the d (1, 2, >= 3) and q (1 .. 8) dispatch of the fused mean, the solves and the variance tail."""
+    _check_predict_mean_and_variance(dev, dt, tol, 200, 37, d, q)
 
 
 @pytest.mark.parametrize("dt,tol", [("f64", 1e-9), ("f32", 5e-3)])

@@ -37,12 +37,12 @@ def main():
         "commit": commit,
     }
     gram_key = next((k for k in raw if k.startswith("k_rbf_gram<double,symmetric")), None)
-    gram_stat = next((v for k, v in stats.items() if "k_rbf_gram_lower_wide<double" in k or "k_rbf_gram<double, true" in k), None)
+    gram_stat = next((v for k, v in stats.items() if re.search(r"k_rbf_gram_lower_wide<double|k_rbf_gram<double, true|k_gram_lower_wide<double, 0|k_gram<double, 0, true", k)), None)
     if gram_key and gram_stat:
         g = raw[gram_key]
         wbytes = g["WRITE_SIZE"]["mean"] * 1024
         rate = wbytes / (gram_stat["avg_us"] * 1e-6) / 1e9
-        out["gram"] = dict(kernel="k_rbf_gram_lower_wide<double> (D1, lower triangle in 64 x 128 tiles), N=%d" % n, launches=g["WRITE_SIZE"]["launches"],
+        out["gram"] = dict(kernel="k_gram_lower_wide<double, RBF> (D1, lower triangle in 64 x 128 tiles), N=%d" % n, launches=g["WRITE_SIZE"]["launches"],
                            WRITE_SIZE_KB=g["WRITE_SIZE"]["mean"], FETCH_SIZE_KB=g["FETCH_SIZE"]["mean"],
                            algorithmic_write_bytes=n * (n + 1) // 2 * 8, avg_kernel_us=gram_stat["avg_us"],
                            hbm_write_GBps_rocprof=rate, frac_of_8TBps=rate / 8000.0, frac_of_achievable_6p29TBps=rate / 6290.0)

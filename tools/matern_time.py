@@ -1,5 +1,5 @@
 """Matern covariances against the RBF in the same process, alternating, CUDA events after warm-up:
-  * the f64 lower Gram (k_rbf_gram_lower_wide / k_cov_gram_lower_wide) at n = 8192 and 16384, d = 1 and 2
+  * the f64 lower Gram (k_gram_lower_wide) at n = 8192 and 16384, d = 1 and 2
   * cimrgp_layer_fit[_cov] at 64 x 4096 and 128 x 2048 (d = 2, q = 2)
   * one GP_RBF / GP_Matern objective evaluation (LML + gradient: Gram, factorisation, K^-1, gradient) at n = 3000
 One JSON line per case (median milliseconds per covariance and the ratio to the RBF) on stdout, and appended

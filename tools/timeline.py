@@ -20,6 +20,11 @@ def short(name):
     return name.split("(")[0][:48]
 
 
+def is_gram(name):
+    """A Gram build: k_gram* (k_rbf_gram* in traces taken before the kernels took the covariance as a parameter)."""
+    return re.search(r"k_(rbf_)?gram", name) is not None
+
+
 def main():
     root = sys.argv[1]
     files = glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True)
@@ -35,7 +40,7 @@ def main():
     # the last factorisation = from the last Gram build on
     start = 0
     for i, r in enumerate(rows):
-        if "k_rbf_gram" in r["name"]:
+        if is_gram(r["name"]):
             start = i
     if len(sys.argv) > 2 and sys.argv[2] == "boundary":
         # a window around the LAST Gram build (pipelined steps: the previous step's tail and solve stage beside the
@@ -43,7 +48,7 @@ def main():
         # (argv[3] = K: around the K-th symmetric Gram build instead -- the timed steps of bench.py come before its
         # stage and potrf-alone sections, which build Gram matrices too)
         if len(sys.argv) > 3:
-            grams = [r for r in rows if "k_rbf_gram" in r["name"]]
+            grams = [r for r in rows if is_gram(r["name"])]
             big = max(r["wg"] for r in grams)
             sym = [r for r in grams if r["wg"] == big]
             tg = sym[int(sys.argv[3]) - 1]["s"]
