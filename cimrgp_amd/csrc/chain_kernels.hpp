@@ -2,6 +2,7 @@
 // four-wave forms), the links (panel solve of one sub-block beside the factorisation of the next), the panel
 // solves and the update tiles that ride in the chain's launches.  Included by potrf.hip only, which holds the
 // host schedule: the whole factorisation stays one translation unit.
+// Tile traffic: load_tile64 and gload_tile64 (both read through gpiece), swrite_tile64; products: mma_chunk64 / 32.
 #pragma once
 #include "common.hpp"
 #include "gemm_tile.hpp"
@@ -33,23 +34,31 @@ template <typename T> static __device__ __forceinline__ v4u mask_v4u(v4u v, int 
     return o;
 }
 
+// Piece (r, c) -- 16 bytes -- of a 64 x kw strip in global memory (row stride ld elements); rows >= mrows and
+// columns >= kw read as zero.
+template <typename T>
+static __device__ __forceinline__ v4u gpiece(const T* src, int64_t ld, int r, int c, int mrows, int kw)
+{
+    using X = Mx<T>;
+    const int kcol = c * X::EPC;
+    v4u v = v4u_zero();
+    if (r < mrows && kcol < kw) {
+        v = *reinterpret_cast<const v4u*>(src + (int64_t)r * ld + kcol);
+        if (kcol + X::EPC > kw) v = mask_v4u<T>(v, kcol, kw);
+    }
+    return v;
+}
+
 // Cooperative, coalesced load of a 64 x kw strip (row stride ld elements) into a
 // padded LDS tile; rows >= mrows and columns >= kw are zero-filled.
 template <typename T, int ROWS = SB>
 static __device__ __forceinline__ void load_tile64(unsigned char* dst, const T* __restrict__ src, int64_t ld,
                                                     int mrows, int kw)
 {
-    using X = Mx<T>;
     using TL = Tile64<T>;
     for (int e = threadIdx.x; e < ROWS * TL::CPR; e += 256) {
         const int r = e / TL::CPR, c = e - r * TL::CPR;
-        const int kcol = c * X::EPC;
-        v4u v = v4u_zero();
-        if (r < mrows && kcol < kw) {
-            v = *reinterpret_cast<const v4u*>(src + (int64_t)r * ld + kcol);
-            if (kcol + X::EPC > kw) v = mask_v4u<T>(v, kcol, kw);
-        }
-        *reinterpret_cast<v4u*>(dst + r * TL::LROW + c * 16) = v;
+        *reinterpret_cast<v4u*>(dst + r * TL::LROW + c * 16) = gpiece<T>(src, ld, r, c, mrows, kw);
     }
 }
 
@@ -59,29 +68,23 @@ template <typename T, int ROWS>
 static __device__ __forceinline__ void gload_tile64(v4u (&regs)[ROWS * Tile64<T>::CPR / 256], const T* __restrict__ src,
                                                      int64_t ld, int mrows, int kw)
 {
-    using X = Mx<T>;
     using TL = Tile64<T>;
 #pragma unroll
     for (int p = 0; p < ROWS * TL::CPR / 256; ++p) {
         const int e = threadIdx.x + 256 * p;
         const int r = e / TL::CPR, c = e - r * TL::CPR;
-        const int kcol = c * X::EPC;
-        v4u v = v4u_zero();
-        if (r < mrows && kcol < kw) {
-            v = *reinterpret_cast<const v4u*>(src + (int64_t)r * ld + kcol);
-            if (kcol + X::EPC > kw) v = mask_v4u<T>(v, kcol, kw);
-        }
-        regs[p] = v;
+        regs[p] = gpiece<T>(src, ld, r, c, mrows, kw);
     }
 }
 
-template <typename T, int ROWS>
-static __device__ __forceinline__ void swrite_tile64(unsigned char* dst, const v4u (&regs)[ROWS * Tile64<T>::CPR / 256])
+// NT = the threads that share the tile
+template <typename T, int ROWS, int NT = 256>
+static __device__ __forceinline__ void swrite_tile64(unsigned char* dst, const v4u (&regs)[ROWS * Tile64<T>::CPR / NT])
 {
     using TL = Tile64<T>;
 #pragma unroll
-    for (int p = 0; p < ROWS * TL::CPR / 256; ++p) {
-        const int e = threadIdx.x + 256 * p;
+    for (int p = 0; p < ROWS * TL::CPR / NT; ++p) {
+        const int e = threadIdx.x + NT * p;
         const int r = e / TL::CPR, c = e - r * TL::CPR;
         *reinterpret_cast<v4u*>(dst + r * TL::LROW + c * 16) = regs[p];
     }
@@ -1091,11 +1094,7 @@ void k_link(T* __restrict__ A, int64_t ld, int n, int c0, int k0, int wn,
                 const int row = br * 16 + X::crow(lane, r), col = (2 * ch + c) * 16 + fcol;
                 *(reinterpret_cast<T*>(bufA + row * TL::LROW) + col) = pval[c][r] - accT[c][r];
             }
-#pragma unroll
-        for (int p = 0; p < NR; ++p) {
-            const int e = tid + TT * p, r = e / TL::CPR, c = e - r * TL::CPR;
-            *reinterpret_cast<v4u*>(bufB + r * TL::LROW + c * 16) = rI[p];
-        }
+        swrite_tile64<T, SB, TT>(bufB, rI);
     }
     lds_barrier();
     acc_t accX[2];
