@@ -218,3 +218,63 @@ class DenseMaternKernel(object):
         xd = dev.to_device(np.atleast_2d(x), tdt, device)
         x2d = None if x2 is None else dev.to_device(np.atleast_2d(x2), tdt, device)
         return self.gram(xd, x2d).cpu().numpy()
+
+
+class SparseKernel(object):
+    """Marks a layer of ``MultiResolutionGaussianProcess`` as SPARSE: its blocks are inducing-point GPs (``Sparse.SparseBlock``,
+    FITC or VFE / DTC) under the wrapped covariance ``kernel`` (an :class:`RBFKernel` or a :class:`DenseMaternKernel`),
+    n m^2 flop and n m memory per block instead of n^3 / 3 and n^2 ("Sparse layers in the multiresolution
+    model").  ``l``, ``sf``, ``noise``, ``cov`` and ``nu`` are the wrapped kernel's.
+
+    A region of n rows gets m = min(n, ``num_inducing``) inducing inputs, rows of the region's own (normalised, warped)
+    inputs picked by ``inducing``: ``'stride'`` -- rows floor((k + 0.5) n / m), k = 0 .. m - 1 (every row, in order, when
+    m = n) -- or ``'random'`` -- ``numpy.random.RandomState([seed, layer, region]).permutation(n)[:m]``.  Either is a
+    function of (seed, layer, region, n) alone.  ``jitter``: eps of K_uu + eps sf I."""
+    INDUCING = ('stride', 'random')
+
+    def __init__(self, kernel, num_inducing=1000, approximation='fitc', jitter=1e-6, inducing='stride', seed=0):
+        from .Sparse import APPROXIMATIONS
+        if not isinstance(kernel, (RBFKernel, DenseMaternKernel)):
+            raise TypeError('SparseKernel wraps an RBFKernel or a DenseMaternKernel, got %s' % type(kernel).__name__)
+        if int(num_inducing) < 1:
+            raise ValueError('num_inducing must be at least 1')
+        if str(approximation).lower() not in APPROXIMATIONS:
+            raise ValueError("approximation must be one of %s, got %r" % (sorted(APPROXIMATIONS), approximation))
+        if not float(jitter) >= 0:
+            raise ValueError('jitter must not be negative')
+        if inducing not in self.INDUCING:
+            raise ValueError("inducing must be 'stride' or 'random', got %r" % (inducing,))
+        self.kernel = kernel
+        self.num_inducing = int(num_inducing)
+        self.approximation = str(approximation).lower()
+        self.jitter = float(jitter)
+        self.inducing = inducing
+        self.seed = int(seed)
+
+    name = 'Sparse'
+
+    l = property(lambda self: self.kernel.l)
+    sf = property(lambda self: self.kernel.sf)
+    noise = property(lambda self: self.kernel.noise)
+    cov = property(lambda self: self.kernel.cov)
+
+    @property
+    def nu(self):
+        return self.kernel.nu          # AttributeError for an RBF base, as on the base itself
+
+    def rewrap(self, kernel):
+        """A SparseKernel with these settings around another base kernel."""
+        return SparseKernel(kernel, self.num_inducing, self.approximation, self.jitter, self.inducing, self.seed)
+
+    def with_noise(self, noise):
+        """The same sparse layer with fixed noise variance ``noise``."""
+        return self.rewrap(self.kernel.with_noise(noise))
+
+    def inducing_rows(self, layer, region, n):
+        """Row numbers (int64, length min(n, num_inducing)) of the inducing inputs of region ``region`` of layer ``layer``
+        with ``n`` rows."""
+        n = int(n)
+        m = min(n, self.num_inducing)
+        if self.inducing == 'stride':
+            return ((2 * np.arange(m, dtype=np.int64) + 1) * n) // (2 * m)
+        return np.random.RandomState([self.seed, int(layer), int(region)]).permutation(n)[:m].astype(np.int64)

@@ -28,8 +28,9 @@ import torch
 from . import device as dev
 from . import dist
 from .Inputs import Inputs
-from .KernelClass import RBFKernel, DenseMaternKernel
+from .KernelClass import RBFKernel, DenseMaternKernel, SparseKernel
 from .Posteriors import DensePosterior
+from .Sparse import SparsePosterior
 
 
 class DenseStats(object):
@@ -101,7 +102,11 @@ class MultiResolutionGaussianProcess(object):
         """``optimize_hyperparameters=True``: before each layer is fitted, its (variance, length-scale, noise) are learned
         by L-BFGS-B on the sum over its regions of the log marginal likelihood of the layer's residual targets (see
         :meth:`_learn_layer`); at most ``max_iters`` iterations per layer.  Only for the dense blocks (no
-        ``basis_function_obj``)."""
+        ``basis_function_obj``).
+
+        A layer whose entry of ``spectral_density_obj`` is a ``SparseKernel`` is SPARSE: its blocks are inducing-point GPs
+        (``Sparse.SparsePosterior``; DESIGN.md, "Sparse layers in the multiresolution model"), mixed freely with exact
+        layers in the one residual chain.  FP64 only."""
         if optimize_hyperparameters and basis_function_obj is not None:
             raise TypeError('not yet supported')
         if int(max_iters) < 1:
@@ -145,11 +150,14 @@ class MultiResolutionGaussianProcess(object):
         else:
             self.spectral_density_obj = [spectral_density_obj] * self.n_layers
         for k in self.spectral_density_obj:
-            if not isinstance(k, (RBFKernel, DenseMaternKernel)):
+            if not isinstance(k, (RBFKernel, DenseMaternKernel, SparseKernel)):
                 # a spectral density without a basis-function object (MaternKernel: general nu, no closed form):
                 # neither path applies
                 raise TypeError('spectral_density_obj must be an RBFKernel or a DenseMaternKernel (nu = 1/2, 3/2, 5/2) '
                                 'when basis_function_obj is None')
+            if isinstance(k, SparseKernel) and dev.as_torch_dtype(dtype) != torch.float64:
+                # cond(K_uu + eps sf I) ~ m / eps exceeds what FP32 holds at eps = 1e-6
+                raise TypeError('not yet supported')
         if snr_ratio is not None:
             # reference: initial noise variance of layer 0 from an SNR (MRGP.py:196-199,966-971)
             self.spectral_density_obj = list(self.spectral_density_obj)
@@ -173,9 +181,7 @@ class MultiResolutionGaussianProcess(object):
         # nested ownership: layers >= self._first_local exchange nothing during the fit (dist.plan_layers)
         self.owner, self._first_local = dist.plan_layers(index_set_obj.bounds, self.world_size)
 
-        self.posterior_obj = [DensePosterior(self.n_regions[j], self.dy, self.spectral_density_obj[j],
-                                             noise_region_specific, bias_region_specific)
-                              for j in range(self.n_layers)]
+        self.posterior_obj = [self._new_posterior(j) for j in range(self.n_layers)]
         self.stats_obj = [DenseStats(self, j) for j in range(self.n_layers)]
         self._f_bar_layers = [None] * self.n_layers
         self._fitted = False
@@ -184,6 +190,24 @@ class MultiResolutionGaussianProcess(object):
         self.lower_bound_layer = [[] for _ in range(self.n_layers)]
 
     # ------------------------------------------------------------------ helpers
+    def _new_posterior(self, j):
+        """The layer object of layer j: sparse if its kernel is a ``SparseKernel``, else dense."""
+        k = self.spectral_density_obj[j]
+        if isinstance(k, SparseKernel):
+            return SparsePosterior(self.n_regions[j], self.dy, k, j, self.n_samps[j], self.noise_region_specific,
+                                   self.bias_region_specific)
+        return DensePosterior(self.n_regions[j], self.dy, k, self.noise_region_specific, self.bias_region_specific)
+
+    def _is_sparse(self, j):
+        return isinstance(self.posterior_obj[j], SparsePosterior)
+
+    def _refuse_sparse(self, index_set):
+        """TypeError if a layer that serves test points under ``index_set`` (None: layer 0 alone) is sparse: for results
+        the sparse blocks do not give yet.  Host only, the same on every rank."""
+        serving = 1 if index_set is None else min(self.n_layers, index_set.get_n_resolutions() + 1)
+        if any(self._is_sparse(j) for j in range(serving)):
+            raise TypeError('not yet supported')
+
     def _normalize_inputs(self, x_train, full_x):
         x = x_train if full_x is None else np.asarray(full_x, dtype=np.float64)
         if self.standard_normalized_inputs is True:
@@ -248,7 +272,9 @@ class MultiResolutionGaussianProcess(object):
         """L-BFGS-B (SciPy) on -sum_l LML_l over theta = (log sf, log l, log noise) of layer j, from the constructor's
         kernel (noise: its own, else NOISE_FRACTION * sf); the layer is then fitted with a NEW kernel object of the
         same class holding the learned values (the noise fixed and shared by the layer's regions).  A non-PD trial
-        point scores (1e100, 0), as in GP_RBF.  With several ranks every evaluation costs one small all-reduce."""
+        point scores (1e100, 0), as in GP_RBF.  With several ranks every evaluation costs one small all-reduce.
+        A sparse layer learns its base kernel's values (the inducing inputs stay where the layer's rule puts them) and
+        the learned kernel is wrapped in a ``SparseKernel`` with the same settings."""
         from scipy.optimize import minimize
         from .Posteriors import NOISE_FRACTION
         k0 = self.spectral_density_obj[j]
@@ -264,10 +290,13 @@ class MultiResolutionGaussianProcess(object):
 
         res = minimize(objective, theta0, jac=True, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
         sf, ell, noise = (float(v) for v in np.exp(res.x))
-        if isinstance(k0, DenseMaternKernel):
-            kernel = DenseMaternKernel(nu=k0.nu, l=ell, sf=sf, noise=noise)
+        base = k0.kernel if isinstance(k0, SparseKernel) else k0
+        if isinstance(base, DenseMaternKernel):
+            kernel = DenseMaternKernel(nu=base.nu, l=ell, sf=sf, noise=noise)
         else:
             kernel = RBFKernel(l=ell, sf=sf, noise=noise)
+        if isinstance(k0, SparseKernel):
+            kernel = k0.rewrap(kernel)
         self.optimizer_results[j] = res
         self.posterior_obj[j].kernel = kernel
 
@@ -431,20 +460,41 @@ class MultiResolutionGaussianProcess(object):
     def _predict(self, test_x, index_set, want_var, include_noise=True):
         xs = self._test_points(test_x)
         ns = xs.shape[0]
-        # fused [mean | var] buffer: one collective for the sum over resolutions
+        layers = self._test_layers(index_set, ns, include_noise)
+        if self.world_size > 1:
+            return self._predict_ranks(xs, index_set, layers, want_var)
+        # fused [mean | var] buffer
         fused = torch.zeros((self.dy + 1, ns), dtype=self.dtype, device=self.device)
         mean = torch.zeros((ns, self.dy), dtype=self.dtype, device=self.device)
         var = fused[self.dy] if want_var else None
         # blocks of a layer write disjoint test ranges: equal-sized ones in ONE batched call, the others in flight
         # together on the stream pool; layers accumulate into the same ranges and follow one another
-        for j, bounds, add_noise, owned in self._test_layers(index_set, ns, include_noise):
+        for j, bounds, add_noise, owned in layers:
             self.posterior_obj[j].predict_layer(self._x_dev, xs, bounds, owned, mean, var, add_noise)
-        if self.world_size > 1:
-            fused[:self.dy] = mean.t()
-            dist.allreduce_sum_(fused, self.group)
-            mean = fused[:self.dy].t()
         mean_np = mean.double().cpu().numpy()
         var_np = fused[self.dy].double().cpu().numpy() if want_var else None
+        return mean_np, var_np
+
+    def _predict_ranks(self, xs, index_set, layers, want_var):
+        """:meth:`_predict` with several ranks: every serving layer has a zero [mean | var] slab of its own, into which
+        this rank's blocks of that layer write; ONE collective sums the slabs over the ranks -- a test row of a layer is
+        served by one block, so every element has one non-zero term and the sum is exact -- and the layers' slabs are then
+        added in layer order, which is the order a single rank accumulates in: the prediction does not depend on the rank
+        count or on ownership, bit for bit."""
+        ns, q = xs.shape[0], self.dy
+        serving = 1 if index_set is None else index_set.get_n_resolutions() + 1
+        slab = ns * (q + 1)
+        fused = torch.zeros(serving * slab, dtype=self.dtype, device=self.device)
+        for j, bounds, add_noise, owned in layers:
+            part = fused[j * slab:(j + 1) * slab]
+            self.posterior_obj[j].predict_layer(self._x_dev, xs, bounds, owned, part[:ns * q].view(ns, q),
+                                                part[ns * q:] if want_var else None, add_noise)
+        dist.allreduce_sum_(fused, self.group)
+        total = torch.zeros(slab, dtype=self.dtype, device=self.device)
+        for j in range(serving):
+            total = total + fused[j * slab:(j + 1) * slab]
+        mean_np = total[:ns * q].view(ns, q).double().cpu().numpy()
+        var_np = total[ns * q:].double().cpu().numpy() if want_var else None
         return mean_np, var_np
 
     def get_predicted_mean(self, test_x, index_set_obj=None, number_of_regions=None):
@@ -474,6 +524,9 @@ class MultiResolutionGaussianProcess(object):
         ``adaptive_inputs`` (the warp's Jacobian is not built)."""
         if self.adaptive_inputs is True:
             raise TypeError('not yet supported')
+        if index_set_obj is not None:
+            self._check_index_set(index_set_obj, number_of_regions)
+        self._refuse_sparse(index_set_obj)
         xs = self._test_points(test_x, index_set_obj, number_of_regions)
         ns, d = int(xs.shape[0]), int(xs.shape[1])
         q = self.dy
@@ -520,7 +573,11 @@ class MultiResolutionGaussianProcess(object):
         by all outputs: the sum over the layers of each region's K(X*, X*) - W W^T, W = K(X*, X) L^-T, entries between
         test points of different regions of a layer being 0.  ``include_noise``: the finest layer's block
         noise on the diagonal, as in :meth:`get_predicted_mean_and_var`, whose variance is this matrix's diagonal.
-        Assembled on the device from the blocks' lower triangles: memory is N*^2 elements."""
+        Assembled on the device from the blocks' lower triangles: memory is N*^2 elements.  Not with a sparse layer among
+        those that serve the test points."""
+        if index_set_obj is not None:
+            self._check_index_set(index_set_obj, number_of_regions)
+        self._refuse_sparse(index_set_obj)
         xs = self._test_points(test_x, index_set_obj, number_of_regions)
         cov = self._joint(xs, index_set_obj, include_noise, xs.shape[0], sampling=False)
         cov = torch.tril(cov) + torch.tril(cov, -1).t()
@@ -533,7 +590,11 @@ class MultiResolutionGaussianProcess(object):
         c = sample * dy + output (include/cimrgp_joint.h).  Outputs are independent; a request for fewer samples gives a
         prefix of a longer one, whatever the rank count.  A block whose factorisation fails is retried with 10x the
         jitter (at most 4 times), then numpy.linalg.LinAlgError names the layer and region;
-        ``self.last_joint_jitter[j]``: the largest relative jitter the owned blocks of layer j needed."""
+        ``self.last_joint_jitter[j]``: the largest relative jitter the owned blocks of layer j needed.  Not with a sparse
+        layer among those that serve the test points."""
+        if index_set_obj is not None:
+            self._check_index_set(index_set_obj, number_of_regions)
+        self._refuse_sparse(index_set_obj)
         if index_set_obj is not None:
             self._check_index_set(index_set_obj, number_of_regions)
         if int(size) < 1:
@@ -567,6 +628,8 @@ class MultiResolutionGaussianProcess(object):
         j = self.n_layers - 1 if layer is None else int(layer)
         if not 0 <= j < self.n_layers:
             raise ValueError('layer must be in [0, %d), got %r' % (self.n_layers, layer))
+        if self._is_sparse(j):
+            raise TypeError('not yet supported')
         n, q = self._y.shape
         fused = torch.zeros(n * q + n + 2, dtype=self.dtype, device=self.device)
         mean, var = fused[:n * q].view(n, q), fused[n * q:n * q + n]

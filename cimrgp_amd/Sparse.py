@@ -14,6 +14,9 @@ cimrgp_cov_gram, cimrgp_potrf, cimrgp_cov_cross, cimrgp_trsm_rows, cimrgp_sparse
 cimrgp_logdet_half and cimrgp_sparse_tail.  torch holds the buffers and adds up the two O(n q) scalars of the LML.
 ``SparseBlock.lml_grad`` adds the analytic gradient w.r.t. (log sf, log l, log s2) and Z: cimrgp_trsm_rows_lt,
 cimrgp_sparse_grad_rows, cimrgp_sparse_grad_combine and cimrgp_cov_pair_grad on the n x m side, torch on the m x m side.
+``SparsePosterior`` makes such blocks a layer of ``MultiResolutionGaussianProcess`` (``KernelClass.SparseKernel``; DESIGN.md,
+"Sparse layers in the multiresolution model"): ``SparseBlock.fit_layer`` / ``predict_layer`` take the noise and the bias
+from device scalars (cimrgp_sparse_lambda_dev, cimrgp_sparse_tail_dev) and read nothing back.
 """
 import numpy as np
 import torch
@@ -29,13 +32,14 @@ PREDICT_BUDGET_BYTES = 1 << 30
 class SparseBlock(object):
     """Device-resident state of one inducing-point block: L_u and L_B with their workspaces, and gamma."""
 
-    def __init__(self, x, z, kernel, approximation='fitc', jitter=1e-6):
+    def __init__(self, x, z, kernel, approximation='fitc', jitter=1e-6, device_noise=False):
         """``x`` (n x d), ``z`` (m x d): device tensors in the same units; ``kernel``: an ``RBFKernel`` /
-        ``DenseMaternKernel`` with its ``noise`` set."""
+        ``DenseMaternKernel`` with its ``noise`` set.  ``device_noise``: the block is a model layer's, fitted by
+        :meth:`fit_layer` with its noise variance in a device scalar; ``kernel.noise`` may then be None."""
         key = str(approximation).lower()
         if key not in APPROXIMATIONS:
             raise ValueError("approximation must be 'fitc' or 'vfe', got %r" % (approximation,))
-        if kernel.noise is None or not kernel.noise > 0:
+        if not device_noise and (kernel.noise is None or not kernel.noise > 0):
             raise ValueError('a sparse block needs a positive noise variance')
         if not jitter >= 0:
             raise ValueError('jitter must not be negative')
@@ -51,15 +55,20 @@ class SparseBlock(object):
         self.lb = self.ws_b = self.info_b = None
         self.gamma = None
         self._terms = None               # device scalars of the LML
+        self.bias = self.noise = self.sums = None        # a layer's block (fit_layer): device (q,), (1,) and float64 (3,)
 
-    def _enqueue_fit(self, r):
-        """The fit's device calls, nothing read back: (A, w, lambda sums).  A (n x m) is the caller's to free."""
+    def _enqueue_fit(self, r, noise_dev=None):
+        """The fit's device calls, nothing read back: (A, w, lambda sums).  A (n x m) is the caller's to free.
+        ``noise_dev``: the noise variance as a device scalar, in place of ``kernel.noise``."""
         k, n, m = self.kernel, self.n, self.m
         self.lu = dev.rbf_gram(self.z, k.l, k.sf, self.jitter * k.sf, lower_only=True, cov=k.cov)
         self.ws_u, self.info_u = dev.potrf(self.lu, m)
         a = dev.rbf_cross(self.x, self.z, k.l, k.sf, cov=k.cov)
         dev.trsm_rows(self.lu, m, self.ws_u, a, n)
-        _, w, sums = dev.sparse_lambda(a, n, m, k.sf, k.noise, self.mode)
+        if noise_dev is not None:
+            _, w, sums = dev.sparse_lambda_dev(a, n, m, k.sf, noise_dev, self.mode)
+        else:
+            _, w, sums = dev.sparse_lambda(a, n, m, k.sf, k.noise, self.mode)
         return a, w, sums
 
     def _enqueue_solve(self, r, c, w, sums):
@@ -89,6 +98,43 @@ class SparseBlock(object):
         self._enqueue_solve(r, c, w, sums)
         self._raise_if_failed(self.info_u, sums[2].item(), self.info_b)
         return self
+
+    def fit_layer(self, y, f_bar, train_out, shared_bias=None, shared_noise=None, noise_fraction=0.01, noise_floor=1e-8):
+        """The enqueue-only fit of a model layer's block: NOTHING is read back (``info_u``, ``info_b`` and ``sums[2]``,
+        the count of non-positive lambda_i, stay on the device for :meth:`SparsePosterior.failure_flag`).  Targets, bias
+        and noise follow ``DenseBlock.fit``: bias = the column means of ``y - f_bar`` (both n x q device views) or
+        ``shared_bias``; noise = ``kernel.noise``, else ``shared_noise``, else
+        max(noise_fraction var(r), noise_floor sf), a device scalar.  While A is alive the block's training-point
+        prediction A b + bias, b = L_B^-T gamma (what cimrgp_potrs leaves in c), is added into ``train_out`` (n x q) by
+        cimrgp_sparse_tail_dev with A as W*; then A is released.  What stays -- L_u, L_B, their workspaces, gamma, bias,
+        noise -- is m x m or smaller, whatever the model's ``keep_factors`` says."""
+        k, n, m = self.kernel, self.n, self.m
+        q = int(y.shape[1])
+        stats = None
+        if shared_bias is None or (shared_noise is None and k.noise is None):
+            stats = dev.block_stats(y, f_bar)
+        self.bias = stats[:q] if shared_bias is None else shared_bias
+        if k.noise is not None:
+            self.noise = torch.full((1,), k.noise, dtype=y.dtype, device=y.device)
+        elif shared_noise is not None:
+            self.noise = shared_noise
+        else:
+            self.noise = dev.noise_from_stats(stats, q, noise_fraction, noise_floor * k.sf)
+        r = dev.residual(y, f_bar, self.bias)
+        a, w, self.sums = self._enqueue_fit(r, self.noise)
+        self.lb, c = dev.wsyrk_tn(a, n, m, w, r, diag_add=1.0)
+        self.ws_b, self.info_b = dev.potrf(self.lb, m)
+        self.gamma = dev.potrs(self.lb, m, self.ws_b, c, want_z=True)
+        dev.sparse_tail_dev(None, a, n, m, c, k.sf, bias=self.bias, mean_out=train_out, accumulate=True)
+        del a
+        return self
+
+    def hand_over_to(self, stream):
+        """The block was fitted on a pool stream; its tensors are used on ``stream`` from now on."""
+        for t in (self.z, self.lu, self.ws_u, self.info_u, self.lb, self.ws_b, self.info_b, self.gamma, self.bias, self.noise,
+                  self.sums):
+            if t is not None:
+                t.record_stream(stream)
 
     def _lml_from(self, s0, s1, half_logdet_b, rwr, gg, q):
         lml = (-0.5 * self.n * q * np.log(2 * np.pi) - 0.5 * q * s0 - q * float(half_logdet_b)
@@ -183,9 +229,18 @@ class SparseBlock(object):
         if self.gamma is None:
             raise RuntimeError('call fit() before predict()')
         k, m = self.kernel, self.m
+        extra = k.noise if include_noise else 0.0
+        for s0, s1, astar, wstar in self._star_chunks(xs, budget_bytes):
+            dev.sparse_tail(astar if var is not None else None, wstar, s1 - s0, m, self.gamma if mean is not None else None, k.sf,
+                            extra, None if mean is None else mean[s0:s1], None if var is None else var[s0:s1])
+        return mean, var
+
+    def _star_chunks(self, xs, budget_bytes=None):
+        """(s0, s1, A*, W*) of every chunk of ``chunk_rows(budget_bytes)`` test rows: A* = K(xs[s0:s1], Z) L_u^-T and
+        W* = A* L_B^-T in two work buffers that the next chunk overwrites."""
+        k, m = self.kernel, self.m
         ns = int(xs.shape[0])
         step = self.chunk_rows(budget_bytes)
-        extra = k.noise if include_noise else 0.0
         astar = wstar = None
         for s0 in range(0, ns, step):
             s1 = min(ns, s0 + step)
@@ -197,6 +252,188 @@ class SparseBlock(object):
             dev.trsm_rows(self.lu, m, self.ws_u, astar, rows)
             wstar[:rows].copy_(astar[:rows])
             dev.trsm_rows(self.lb, m, self.ws_b, wstar, rows)
-            dev.sparse_tail(astar if var is not None else None, wstar, rows, m, self.gamma if mean is not None else None, k.sf,
-                            extra, None if mean is None else mean[s0:s1], None if var is None else var[s0:s1])
-        return mean, var
+            yield s0, s1, astar, wstar
+
+    def predict_layer(self, xs, mean, var=None, add_noise=False, budget_bytes=None):
+        """A model layer's block (:meth:`fit_layer`): ``mean`` (ns x q) += W* gamma + bias and, with ``var`` (ns,),
+        var += sf - sum A*^2 + sum W*^2 (+ the block's noise, read on the device, with ``add_noise``), in the chunks of
+        :meth:`predict`.  The mean alone takes the same route: weights L_u^-T b for the fused cross-covariance product
+        would be of size ~ 1 / jitter and lose digits."""
+        if self.gamma is None:
+            raise RuntimeError('call fit_layer() before predict_layer()')
+        for s0, s1, astar, wstar in self._star_chunks(xs, budget_bytes):
+            dev.sparse_tail_dev(astar if var is not None else None, wstar, s1 - s0, self.m, self.gamma, self.kernel.sf,
+                                bias=self.bias, extra_var_dev=self.noise if (add_noise and var is not None) else None,
+                                mean_out=mean[s0:s1], var_out=None if var is None else var[s0:s1], accumulate=True)
+
+
+def equivalent_exact_rows(n, m):
+    """The size of the exact block that costs the flops of a sparse block, n_eq^3 / 3 = n m^2: what the stream pool's rule
+    (``Posteriors.block_streams``, written for exact blocks) is asked with."""
+    return int(round((3.0 * n * m * m) ** (1.0 / 3.0)))
+
+
+class SparsePosterior(object):
+    """One resolution of ``MultiResolutionGaussianProcess`` whose blocks are inducing-point GPs (:class:`SparseBlock`), the
+    sparse twin of ``Posteriors.DensePosterior`` with the members the model uses ("Sparse layers in the
+    multiresolution model").  ``kernel``: a ``KernelClass.SparseKernel``; ``layer``: the layer's number (it enters the
+    draw of ``inducing='random'``); ``n_rows[l]``: rows of region l.  The blocks of a layer run on the stream pool; there is
+    no batched C call for equal-sized sparse blocks."""
+
+    def __init__(self, n_regions, dy, kernel, layer, n_rows, noise_region_specific=True, bias_region_specific=True):
+        self.n_regions = int(n_regions)
+        self.dy = int(dy)
+        self.kernel = kernel
+        self.layer = int(layer)
+        self.n_rows = [int(n) for n in n_rows]
+        self.noise_region_specific = noise_region_specific
+        self.bias_region_specific = bias_region_specific
+        self.blocks = [None] * self.n_regions
+        self._z = {}                     # region -> (key of its inputs, Z on the device)
+
+    def needs_whole_layer(self):
+        """As ``DensePosterior.needs_whole_layer``: a shared bias, or a shared noise taken from the targets."""
+        return not (self.bias_region_specific and (self.noise_region_specific or self.kernel.noise is not None))
+
+    def inducing_rows(self, region):
+        """Row numbers, within region ``region``, of its inducing inputs: a function of the kernel's (inducing, seed), the
+        layer, the region and its number of rows alone -- never of the rank count or of ownership."""
+        return self.kernel.inducing_rows(self.layer, region, self.n_rows[region])
+
+    def _inducing_inputs(self, l, x_l):
+        """Z of region l: the rows :meth:`inducing_rows` of its inputs ``x_l``, gathered once and kept (the inputs of a
+        model do not change; the learned hyper-parameters leave Z where it is)."""
+        rows = self.inducing_rows(l)
+        key = (x_l.data_ptr(), tuple(x_l.shape), x_l.dtype, rows.tobytes())
+        if l not in self._z or self._z[l][0] != key:
+            if int(x_l.shape[0]) != self.n_rows[l]:
+                raise ValueError('region %d of layer %d has %d rows, not %d' % (l, self.layer, x_l.shape[0], self.n_rows[l]))
+            idx = torch.as_tensor(rows).to(x_l.device)
+            self._z[l] = (key, x_l.index_select(0, idx).contiguous())
+        return self._z[l][1]
+
+    def _block(self, l, x_l, z, kernel=None):
+        k = self.kernel
+        return SparseBlock(x_l, z, k.kernel if kernel is None else kernel, k.approximation, k.jitter, device_noise=kernel is None)
+
+    def _fan(self, device, items):
+        """The stream pool for blocks of (n, m) in ``items``."""
+        from .Posteriors import _Fanout
+        return _Fanout(device, len(items), max(equivalent_exact_rows(n, m) for n, m in items))
+
+    def update_scale_given_axis(self, y_mean, x, f_bar, train_out, owned=None, keep_factors=True):
+        """Fit the ``owned`` regions (default all) on ``y_mean - f_bar`` and add their training-point predictions into
+        ``train_out`` (lists indexed by region of device views, as for ``DensePosterior``), each by
+        :meth:`SparseBlock.fit_layer` on a stream of the pool: enqueue-only, nothing is read back.  ``keep_factors`` changes
+        nothing here: what a sparse block keeps is m x m (L_u, L_B, their workspaces) or smaller; the n x m matrix A is
+        released at the end of every block's fit."""
+        from .Posteriors import DensePosterior, NOISE_FRACTION, NOISE_FLOOR
+        regions = list(range(self.n_regions) if owned is None else owned)
+        shared_bias = shared_noise = None
+        if self.needs_whole_layer():
+            stats = dev.block_stats(DensePosterior._whole_layer(y_mean), DensePosterior._whole_layer(f_bar))
+            if not self.bias_region_specific:
+                shared_bias = stats[:self.dy]
+            if not self.noise_region_specific and self.kernel.noise is None:
+                shared_noise = dev.noise_from_stats(stats, self.dy, NOISE_FRACTION, NOISE_FLOOR * self.kernel.sf)
+        if not regions:
+            return
+        zs = {l: self._inducing_inputs(l, x[l]) for l in regions}        # on the caller's stream, before the fan-out
+        fan = self._fan(y_mean[regions[0]].device, [(int(x[l].shape[0]), int(zs[l].shape[0])) for l in regions])
+        for l in regions:
+            with torch.cuda.stream(fan.stream()):
+                blk = self._block(l, x[l], zs[l])
+                blk.fit_layer(y_mean[l], f_bar[l], train_out[l], shared_bias, shared_noise, NOISE_FRACTION, NOISE_FLOOR)
+                if fan.pool:
+                    blk.hand_over_to(fan.main)
+            self.blocks[l] = blk
+        fan.join()
+
+    def predict_layer(self, x_all, xs, test_bounds, owned, mean, var, add_noise):
+        """Accumulate the layer's predictive mean and (``var`` not None) variance at the test points: test block l = rows
+        test_bounds[l] of ``xs``, served by training block l (:meth:`SparseBlock.predict_layer`), the owned blocks with
+        test rows in flight together on the stream pool."""
+        rest = []
+        for l in sorted(owned):
+            a, b = (int(v) for v in test_bounds[l])
+            if b > a:
+                rest.append((l, a, b))
+        if not rest:
+            return
+        fan = self._fan(xs.device, [(b - a, self.blocks[l].m) for l, a, b in rest])
+        for l, a, b in rest:
+            with torch.cuda.stream(fan.stream()):
+                self.blocks[l].predict_layer(xs[a:b], mean[a:b], None if var is None else var[a:b], add_noise)
+        fan.join()
+
+    def layer_objective(self, ell, sf2, noise, y_mean, x, f_bar, owned=None):
+        """As ``DensePosterior.layer_objective``: (lml, grad w.r.t. (log sf2, log ell, log noise), failure) of the layer's
+        residual targets under (ell, sf2, noise), the sum of :meth:`SparseBlock.lml_grad` (``want_z=False``) over the
+        ``owned`` regions; Z follows the layer's rule and stays fixed.  failure: 0, else 1 (a factor not positive definite
+        or a non-positive lambda_i) or the watchdog code; lml and grad are meaningless when it is not 0."""
+        from .Posteriors import DensePosterior
+        from .KernelClass import DenseMaternKernel, RBFKernel
+        regions = list(range(self.n_regions) if owned is None else owned)
+        q = self.dy
+        base = self.kernel.kernel
+        if isinstance(base, DenseMaternKernel):
+            trial = DenseMaternKernel(nu=base.nu, l=ell, sf=sf2, noise=noise)
+        else:
+            trial = RBFKernel(l=ell, sf=sf2, noise=noise)
+        shared_bias = None
+        if not self.bias_region_specific:
+            shared_bias = dev.block_stats(DensePosterior._whole_layer(y_mean), DensePosterior._whole_layer(f_bar))[:q]
+        lml, grad, failure = 0.0, np.zeros(3), 0.0
+        for l in regions:
+            bias = shared_bias if shared_bias is not None else dev.block_stats(y_mean[l], f_bar[l])[:q]
+            r = dev.residual(y_mean[l], f_bar[l], bias)
+            blk = self._block(l, x[l], self._inducing_inputs(l, x[l]), kernel=trial)
+            try:
+                a, g, _ = blk.lml_grad(r, want_z=False)
+            except np.linalg.LinAlgError:
+                failure = max(failure, 1.0)
+                continue
+            except RuntimeError as e:
+                if 'schedule watchdog' not in str(e):
+                    raise
+                failure = max(failure, float(dev.INFO_WATCHDOG))
+                continue
+            lml, grad = lml + a, grad + g
+        return lml, grad, failure
+
+    def _status(self, l):
+        """Device float64 (3,): info_u, the count of non-positive lambda_i, info_b of block l; None if it has none."""
+        blk = self.blocks[l]
+        if blk is None or blk.info_u is None or blk.info_b is None or blk.sums is None:
+            return None
+        return torch.cat([blk.info_u.reshape(1).double(), blk.sums[2:3], blk.info_b.reshape(1).double()])
+
+    def failure_flag(self, regions, out):
+        """out[0] = the largest of info_u, info_b and the count of non-positive lambda_i over ``regions``: 0 = every block
+        is fine, non-zero = failed, and a watchdog code (the largest value an ``info`` takes) stays recognisable.  Written
+        on the device without a host synchronisation."""
+        status = [s for s in (self._status(l) for l in regions) if s is not None]
+        if status:
+            out.copy_(torch.cat(status).max().to(out.dtype).reshape(1))
+        return out
+
+    def check(self, regions=None):
+        """Raise for the first failed block of ``regions``, saying which of the three it was: ``numpy.linalg.LinAlgError``
+        for K_uu + jitter sf I or B not positive definite or a non-positive lambda_i, RuntimeError for a watchdog code."""
+        for l in (range(self.n_regions) if regions is None else regions):
+            s = self._status(l)
+            if s is None:
+                continue
+            info_u, bad, info_b = s.cpu().numpy()
+            where = 'sparse layer %d, region %d' % (self.layer, l)
+            for code, what in ((info_u, 'K_uu + jitter sf I'), (info_b, 'B = I + A^T Lambda^-1 A')):
+                if dev.is_watchdog(code):
+                    raise RuntimeError('cimrgp_potrf: schedule watchdog (%s, factor of %s)' % (where, what))
+            if info_u != 0:
+                raise np.linalg.LinAlgError('%s: K_uu + jitter sf I is not positive definite (leading minor of order %d)'
+                                            % (where, int(info_u)))
+            if bad > 0:
+                raise np.linalg.LinAlgError('%s: %d of the lambda_i = sf - q_i + noise are not positive' % (where, int(bad)))
+            if info_b != 0:
+                raise np.linalg.LinAlgError('%s: B = I + A^T Lambda^-1 A is not positive definite (leading minor of order %d)'
+                                            % (where, int(info_b)))

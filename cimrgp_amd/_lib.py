@@ -132,6 +132,12 @@ SPARSE_GRAD_SIGNATURES = {
     "cimrgp_sparse_grad_combine": (_i32, [_i32, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/cimrgp_sparse_layer.h (sparse layers of the model)
+SPARSE_LAYER_SIGNATURES = {
+    "cimrgp_sparse_lambda_dev": (_i32, [_i32, _vp, _i64, _i64, _i64, _dbl, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "cimrgp_sparse_tail_dev": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _i32, _vp]),
+}
+
 _lib = None
 
 
@@ -153,7 +159,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + \
             list(JOINT_SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(LOO_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items()) + \
-            list(SPARSE_GRAD_SIGNATURES.items()):
+            list(SPARSE_GRAD_SIGNATURES.items()) + list(SPARSE_LAYER_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if a symbol is missing
         fn.restype = res
         fn.argtypes = args

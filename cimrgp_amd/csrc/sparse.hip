@@ -1,4 +1,5 @@
-// Inducing-point (sparse) GP regression: the three calls of include/cimrgp_sparse.h.
+// Inducing-point (sparse) GP regression: the three calls of include/cimrgp_sparse.h and their two twins of
+// include/cimrgp_sparse_layer.h, which read the noise, a bias and an extra variance from the device (same kernel bodies).
 //   wsyrk_tn       lower(C) = diag_add I + A^T diag(w) A and g = A^T diag(w) r for A (n x m, row-major), n >> m:
 //                    k_wsyrk_tn       one 128 x 128 output tile and one slice of K = n per workgroup, on the matrix cores
 //                                     (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32, Mx<T> in common.hpp); the partial
@@ -284,11 +285,11 @@ void k_wsyrk_reduce(const T* __restrict__ cpart, const T* __restrict__ gpart, in
 // --------------------------------------------------------------------- lambda ----
 // A wave per row (4 rows per workgroup): lane l adds the squares of columns l, l + 64, .. in FP64, then the 64 partial
 // sums are added pairwise (xor 32, 16, .. 1): a fixed order.  lam <- lambda_i, dtmp <- sf2 - q_i (k_sparse_sums turns
-// it into w).
+// it into w).  noise_dev != nullptr: the noise is that element on the device, not the argument.
 template <typename T>
 __global__ __launch_bounds__(256)
-void k_sparse_rowsq(const T* __restrict__ A, int64_t lda, int n, int m, double sf2, double noise, int mode, T* __restrict__ lam,
-                    T* __restrict__ dtmp)
+void k_sparse_rowsq(const T* __restrict__ A, int64_t lda, int n, int m, double sf2, double noise, const T* __restrict__ noise_dev,
+                    int mode, T* __restrict__ lam, T* __restrict__ dtmp)
 {
     const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n) return;
@@ -301,6 +302,7 @@ void k_sparse_rowsq(const T* __restrict__ A, int64_t lda, int n, int m, double s
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
     if (lane == 0) {
+        if (noise_dev) noise = (double)noise_dev[0];
         const double d = sf2 - s;
         lam[row] = (T)(mode == 0 ? d + noise : noise);
         dtmp[row] = (T)d;
@@ -338,10 +340,13 @@ void k_sparse_sums(const T* __restrict__ lam, T* __restrict__ w, int n, double* 
 }
 
 // ----------------------------------------------------------------------- tail ----
+// bias (q elements) and extra (one element) may be nullptr: then they add nothing and the result is that of the call
+// without them, bit for bit.  Both are added in FP64 before the one rounding to T.
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_sparse_tail(const T* __restrict__ As, const T* __restrict__ Ws, int ns, int m, int64_t lda, const T* __restrict__ gamma, int q,
-                   double base, T* __restrict__ mean, T* __restrict__ var, int accumulate)
+                   double base, const T* __restrict__ bias, const T* __restrict__ extra, T* __restrict__ mean, T* __restrict__ var,
+                   int accumulate)
 {
     const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= ns) return;
@@ -371,13 +376,17 @@ void k_sparse_tail(const T* __restrict__ As, const T* __restrict__ Ws, int ns, i
     }
     if (lane != 0) return;
     if (var) {
+        if (extra) base += (double)extra[0];
         const T v = (T)(base - sa + sw);
         var[row] = accumulate ? var[row] + v : v;
     }
     if (mean) {
 #pragma unroll
         for (int c = 0; c < MAXQ; ++c)
-            if (c < q) mean[(int64_t)row * q + c] = accumulate ? mean[(int64_t)row * q + c] + (T)acc[c] : (T)acc[c];
+            if (c < q) {
+                const T v = bias ? (T)(acc[c] + (double)bias[c]) : (T)acc[c];
+                mean[(int64_t)row * q + c] = accumulate ? mean[(int64_t)row * q + c] + v : v;
+            }
     }
 }
 
@@ -440,18 +449,19 @@ int cimrgp_wsyrk_tn(int dtype, const void* a_dev, int64_t n, int64_t m, int64_t 
     });
 }
 
-int cimrgp_sparse_lambda(int dtype, const void* a_dev, int64_t n, int64_t m, int64_t lda, double sf2, double noise, int mode,
-                         void* lam_dev, void* w_dev, double* sums_dev, void* stream)
+// cimrgp_sparse_lambda and cimrgp_sparse_lambda_dev: `dev_entry` says which; the first takes `noise`, the second noise_dev.
+static int sparse_lambda_impl(const char* fn, bool dev_entry, int dtype, const void* a_dev, int64_t n, int64_t m, int64_t lda, double sf2,
+                              double noise, const void* noise_dev, int mode, void* lam_dev, void* w_dev, double* sums_dev, void* stream)
 {
-    const char* fn = "cimrgp_sparse_lambda";
     CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(a_dev && lam_dev && w_dev && sums_dev, fn, "null pointer");
+    CIMRGP_REQUIRE(!dev_entry || noise_dev, fn, "null pointer (noise)");
     CIMRGP_REQUIRE(n >= 1 && n < (1ll << 31) && m >= 1 && m < (1ll << 31) && lda >= m, fn, "bad dimensions");
     CIMRGP_REQUIRE(mode == 0 || mode == 1, fn, "mode must be 0 (FITC) or 1 (VFE)");
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         hipLaunchKernelGGL((k_sparse_rowsq<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream_of(stream), (const T*)a_dev, lda, (int)n,
-                           (int)m, sf2, noise, mode, (T*)lam_dev, (T*)w_dev);
+                           (int)m, sf2, noise, (const T*)noise_dev, mode, (T*)lam_dev, (T*)w_dev);
         CIMRGP_LAUNCH_CHECK(fn);
         hipLaunchKernelGGL((k_sparse_sums<T>), dim3(1), dim3(1024), 0, stream_of(stream), (const T*)lam_dev, (T*)w_dev, (int)n, sums_dev);
         CIMRGP_LAUNCH_CHECK(fn);
@@ -459,11 +469,11 @@ int cimrgp_sparse_lambda(int dtype, const void* a_dev, int64_t n, int64_t m, int
     });
 }
 
-int cimrgp_sparse_tail(int dtype, const void* astar_dev, const void* wstar_dev, int64_t ns, int64_t m, int64_t lda,
-                       const void* gamma_dev, int q, double sf2, double extra_var, void* mean_dev, void* var_dev, int accumulate,
-                       void* stream)
+// cimrgp_sparse_tail (bias_dev and extra_var_dev nullptr) and cimrgp_sparse_tail_dev.
+static int sparse_tail_impl(const char* fn, int dtype, const void* astar_dev, const void* wstar_dev, int64_t ns, int64_t m, int64_t lda,
+                            const void* gamma_dev, int q, double sf2, double extra_var, const void* bias_dev, const void* extra_var_dev,
+                            void* mean_dev, void* var_dev, int accumulate, void* stream)
 {
-    const char* fn = "cimrgp_sparse_tail";
     CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(wstar_dev, fn, "null pointer");
     CIMRGP_REQUIRE(var_dev == nullptr || astar_dev, fn, "null pointer (astar)");
@@ -474,11 +484,41 @@ int cimrgp_sparse_tail(int dtype, const void* astar_dev, const void* wstar_dev, 
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         hipLaunchKernelGGL((k_sparse_tail<T>), dim3((unsigned)((ns + 3) / 4)), dim3(256), 0, stream_of(stream), (const T*)astar_dev,
-                           (const T*)wstar_dev, (int)ns, (int)m, lda, (const T*)gamma_dev, q, sf2 + extra_var, (T*)mean_dev, (T*)var_dev,
-                           accumulate);
+                           (const T*)wstar_dev, (int)ns, (int)m, lda, (const T*)gamma_dev, q, sf2 + extra_var, (const T*)bias_dev,
+                           (const T*)extra_var_dev, (T*)mean_dev, (T*)var_dev, accumulate);
         CIMRGP_LAUNCH_CHECK(fn);
         return 0;
     });
+}
+
+int cimrgp_sparse_lambda(int dtype, const void* a_dev, int64_t n, int64_t m, int64_t lda, double sf2, double noise, int mode,
+                         void* lam_dev, void* w_dev, double* sums_dev, void* stream)
+{
+    return sparse_lambda_impl("cimrgp_sparse_lambda", false, dtype, a_dev, n, m, lda, sf2, noise, nullptr, mode, lam_dev, w_dev, sums_dev,
+                              stream);
+}
+
+int cimrgp_sparse_lambda_dev(int dtype, const void* a_dev, int64_t n, int64_t m, int64_t lda, double sf2, const void* noise_dev, int mode,
+                             void* lam_dev, void* w_dev, double* sums_dev, void* stream)
+{
+    return sparse_lambda_impl("cimrgp_sparse_lambda_dev", true, dtype, a_dev, n, m, lda, sf2, 0.0, noise_dev, mode, lam_dev, w_dev,
+                              sums_dev, stream);
+}
+
+int cimrgp_sparse_tail(int dtype, const void* astar_dev, const void* wstar_dev, int64_t ns, int64_t m, int64_t lda,
+                       const void* gamma_dev, int q, double sf2, double extra_var, void* mean_dev, void* var_dev, int accumulate,
+                       void* stream)
+{
+    return sparse_tail_impl("cimrgp_sparse_tail", dtype, astar_dev, wstar_dev, ns, m, lda, gamma_dev, q, sf2, extra_var, nullptr, nullptr,
+                            mean_dev, var_dev, accumulate, stream);
+}
+
+int cimrgp_sparse_tail_dev(int dtype, const void* astar_dev, const void* wstar_dev, int64_t ns, int64_t m, int64_t lda,
+                           const void* gamma_dev, int q, double sf2, double extra_var, const void* bias_dev, const void* extra_var_dev,
+                           void* mean_dev, void* var_dev, int accumulate, void* stream)
+{
+    return sparse_tail_impl("cimrgp_sparse_tail_dev", dtype, astar_dev, wstar_dev, ns, m, lda, gamma_dev, q, sf2, extra_var, bias_dev,
+                            extra_var_dev, mean_dev, var_dev, accumulate, stream);
 }
 
 }  // extern "C"

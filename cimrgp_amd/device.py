@@ -484,6 +484,40 @@ def sparse_tail(astar, wstar, ns, m, gamma, sf2, extra_var=0.0, mean_out=None, v
                "cimrgp_sparse_tail")
 
 
+def sparse_lambda_dev(abuf, n, m, sf2, noise_dev, mode, lam=None, w=None, sums=None):
+    """:func:`sparse_lambda` with the noise variance a device scalar ``noise_dev`` (one element of abuf's dtype), read by
+    the kernel: nothing comes back to the host (cimrgp_sparse_lambda_dev, include/cimrgp_sparse_layer.h)."""
+    lib = _lib.load()
+    if noise_dev.dtype != abuf.dtype or noise_dev.numel() < 1:
+        raise ValueError("noise_dev must hold one element of the matrix's dtype")
+    if lam is None:
+        lam = torch.empty(int(n), dtype=abuf.dtype, device=abuf.device)
+    if w is None:
+        w = torch.empty(int(n), dtype=abuf.dtype, device=abuf.device)
+    if sums is None:
+        sums = torch.empty(3, dtype=torch.float64, device=abuf.device)
+    _lib.check(lib.cimrgp_sparse_lambda_dev(_DT[abuf.dtype], _p(abuf), int(n), int(m), abuf.stride(0), float(sf2), _p(noise_dev),
+                                            int(mode), _p(lam), _p(w), _p(sums), _stream()), "cimrgp_sparse_lambda_dev")
+    return lam, w, sums
+
+
+def sparse_tail_dev(astar, wstar, ns, m, gamma, sf2, extra_var=0.0, bias=None, extra_var_dev=None, mean_out=None, var_out=None,
+                    accumulate=False):
+    """:func:`sparse_tail` with a device bias (q,) added to every row of the mean and a device scalar ``extra_var_dev``
+    added to the variance, either None (cimrgp_sparse_tail_dev, include/cimrgp_sparse_layer.h)."""
+    lib = _lib.load()
+    if astar is not None and astar.stride(0) != wstar.stride(0):
+        raise ValueError("astar and wstar must have the same row pitch")
+    q = 0 if gamma is None else int(gamma.shape[1])
+    if bias is not None and (bias.dtype != wstar.dtype or bias.numel() < q):
+        raise ValueError("bias must hold q elements of the matrices' dtype")
+    if extra_var_dev is not None and (extra_var_dev.dtype != wstar.dtype or extra_var_dev.numel() < 1):
+        raise ValueError("extra_var_dev must hold one element of the matrices' dtype")
+    _lib.check(lib.cimrgp_sparse_tail_dev(_DT[wstar.dtype], _p(astar), _p(wstar), int(ns), int(m), wstar.stride(0), _p(gamma), q,
+                                          float(sf2), float(extra_var), _p(bias), _p(extra_var_dev), _p(mean_out), _p(var_out),
+                                          int(bool(accumulate)), _stream()), "cimrgp_sparse_tail_dev")
+
+
 def cov_pair_grad_scratch_bytes(na, nb, d):
     return int(_lib.load().cimrgp_cov_pair_grad_scratch_bytes(int(na), int(nb), int(d)))
 

@@ -481,4 +481,9 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
  * row-wise calls: include/cimrgp_sparse_grad.h. */
 #include "cimrgp_sparse_grad.h"
 
+/* Sparse layers of the multiresolution model: cimrgp_sparse_lambda and cimrgp_sparse_tail with the noise, a bias and an
+ * extra variance read from the device, so that a layer's fit and prediction read nothing back:
+ * include/cimrgp_sparse_layer.h. */
+#include "cimrgp_sparse_layer.h"
+
 #endif /* CIMRGP_H */
