@@ -378,11 +378,17 @@ class SparseGP(RegressionMethod):
     learns Z, as GPy's ``SparseGPRegression`` does: the parameter vector is [log sf, log l, log noise, Z.ravel()] with Z in
     the z-scored units of the fit.  After the fit ``inducing_inputs`` holds Z in the caller's units.  With a Matern 1/2
     covariance the objective has a kink wherever an inducing input sits on a training input or on another inducing input
-    (Z drawn from the data starts there); the gradient takes dk/dz = 0 at r = 0 and the combination is not refused."""
+    (Z drawn from the data starts there); the gradient takes dk/dz = 0 at r = 0 and the combination is not refused.
+    ``ARD=True``: one length-scale per input dimension, as the reference's sparse plugins have it (gpflow's and GPy's
+    ``RBF(d, ARD=True)``; DESIGN.md, "ARD length-scales for the sparse GP").  ``lengthscale`` is then a scalar (every
+    dimension) or a length-d sequence; after the fit ``lengthscales`` holds the (d,) vector in z-scored input units and
+    ``kernel.l`` is 1.0, as for ``GP_RBF(ARD=True)``.  ``ell=`` of :meth:`log_marginal_likelihood` and
+    :meth:`log_marginal_likelihood_grad` takes a scalar or a (d,) vector, and the optimisers' parameter vector is
+    [log sf, log l_1 .. log l_d, log noise, (Z.ravel())]."""
     name = 'SparseGP'
 
     def __init__(self, num_inducing=1000, approximation='fitc', lengthscale=1., variance=1., nu=None, Z=None, seed=0, jitter=1e-6,
-                 dtype='f64', device=None, optimize=False, max_iters=200, jac='2-point', optimize_inducing=False):
+                 dtype='f64', device=None, optimize=False, max_iters=200, jac='2-point', optimize_inducing=False, ARD=False):
         super(SparseGP, self).__init__()
         from .Sparse import APPROXIMATIONS
         if str(approximation).lower() not in APPROXIMATIONS:
@@ -399,8 +405,21 @@ class SparseGP(RegressionMethod):
         self.num_inducing = int(num_inducing)
         self.approximation = str(approximation).lower()
         self.nu = None if nu is None else float(nu)
-        self._initial = (float(lengthscale), float(variance))
-        self.kernel = self._make_kernel(lengthscale, variance)          # ValueError for an unsupported nu
+        self.ARD = bool(ARD)
+        self.lengthscales = None             # ARD: (d,) vector after fit
+        if np.ndim(lengthscale) > 0:
+            if not self.ARD:
+                raise ValueError('a sequence of length-scales needs ARD=True')
+            if np.ndim(lengthscale) != 1:
+                raise ValueError('lengthscale must be a scalar or a sequence with one entry per input dimension')
+            self._initial = (np.array(lengthscale, dtype=np.float64), float(variance))
+        else:
+            self._initial = (float(lengthscale), float(variance))
+        if self.ARD:                         # the kernel is built at l = 1 and cannot refuse these itself
+            ls = np.atleast_1d(self._initial[0])
+            if ls.size == 0 or not (np.isfinite(ls).all() and (ls > 0).all()):
+                raise ValueError('lengthscale must be positive and finite in every entry, got %r' % (lengthscale,))
+        self.kernel = self._make_kernel(1.0 if self.ARD else lengthscale, variance)      # ValueError for an unsupported nu
         self.Z = None if Z is None else np.atleast_2d(np.asarray(Z, dtype=np.float64))
         self.seed = seed
         self.jitter = float(jitter)
@@ -432,8 +451,32 @@ class SparseGP(RegressionMethod):
         return (self.Z - self.data_mean) / self.data_std if self.preprocess else self.Z
 
     def _block(self, ell, sf, noise):
+        """The block at (ell, sf, noise); ARD: ``ell`` is the (d,) vector and the kernel's own length-scale 1."""
         from .Sparse import SparseBlock
+        if self.ARD:
+            return SparseBlock(self._x, self._z, self._make_kernel(1.0, sf, noise), self.approximation, self.jitter,
+                               lengthscales=ell)
         return SparseBlock(self._x, self._z, self._make_kernel(ell, sf, noise), self.approximation, self.jitter)
+
+    def _ell(self, ell):
+        """The ``ell=`` argument of the two objective calls: the fitted value by default; ARD: a scalar stands for all
+        dimensions."""
+        if not self.ARD:
+            return self.kernel.l if ell is None else float(ell)
+        if ell is None:
+            return self.lengthscales
+        return np.full(self.lengthscales.shape[0], float(ell)) if np.ndim(ell) == 0 else np.asarray(ell, dtype=np.float64)
+
+    def _start(self, noise0):
+        """The optimisers' starting point [log sf, log l (ARD: one per dimension), log noise]."""
+        ells = list(self.lengthscales) if self.ARD else [self.kernel.l]
+        return np.log([self.kernel.sf] + ells + [noise0])
+
+    def _unpack(self, theta):
+        """(ell, sf, noise) of an optimiser's parameter vector; what follows them is Z."""
+        nl = self.lengthscales.shape[0] if self.ARD else 1
+        vals = np.exp(theta[:nl + 2])
+        return (vals[1:-1].copy() if self.ARD else float(vals[1])), float(vals[0]), float(vals[-1])
 
     def log_marginal_likelihood(self, ell=None, sf=None, noise=None):
         """The FITC marginal likelihood / the VFE bound of the fitted data at (ell, sf, noise); the fitted values by
@@ -443,37 +486,38 @@ class SparseGP(RegressionMethod):
         if ell is None and sf is None and noise is None:
             return self.block.log_marginal_likelihood()
         k = self.kernel
-        blk = self._block(k.l if ell is None else float(ell), k.sf if sf is None else float(sf),
-                          k.noise if noise is None else float(noise))
+        blk = self._block(self._ell(ell), k.sf if sf is None else float(sf), k.noise if noise is None else float(noise))
         return blk.fit(self._y).log_marginal_likelihood()
 
     def log_marginal_likelihood_grad(self, ell=None, sf=None, noise=None, want_z=True):
         """``(lml, dtheta, dZ)`` of the fitted data at (ell, sf, noise), the fitted values by default: the objective of
-        :meth:`log_marginal_likelihood`, its gradient w.r.t. (log sf, log ell, log noise) as a (3,) array and, with
-        ``want_z``, w.r.t. the inducing inputs in the (z-scored) units of the fit as an (m, d) array, else None.
+        :meth:`log_marginal_likelihood`, its gradient w.r.t. (log sf, log ell, log noise) as a (3,) array (ARD: one entry
+        per length-scale, (d + 2,)) and, with ``want_z``, w.r.t. the inducing inputs in the (z-scored) units of the fit as
+        an (m, d) array, else None.
         Raises as :meth:`log_marginal_likelihood` does."""
         if self.block is None:
             raise RuntimeError('call fit() before log_marginal_likelihood_grad()')
         k = self.kernel
-        blk = self._block(k.l if ell is None else float(ell), k.sf if sf is None else float(sf),
-                          k.noise if noise is None else float(noise))
+        blk = self._block(self._ell(ell), k.sf if sf is None else float(sf), k.noise if noise is None else float(noise))
         lml, dtheta, dz = blk.lml_grad(self._y, want_z=want_z)
         return lml, dtheta, None if dz is None else dz.double().cpu().numpy()
 
     def _optimize_analytic(self, noise0):
-        """L-BFGS-B on the analytic gradient over [log sf, log l, log noise] and, with ``optimize_inducing``, Z."""
+        """L-BFGS-B on the analytic gradient over [log sf, log l (ARD: one per dimension), log noise] and, with
+        ``optimize_inducing``, Z."""
         from scipy.optimize import minimize
-        theta0 = np.log([self.kernel.sf, self.kernel.l, noise0])
+        theta0 = self._start(noise0)
+        nt = theta0.shape[0]
         zshape = tuple(self._z.shape)
         if self.optimize_inducing:
             theta0 = np.concatenate([theta0, self._z.double().cpu().numpy().ravel()])
 
         def objective(theta):
-            sf, ell, noise = np.exp(theta[:3])
+            ell, sf, noise = self._unpack(theta)
             if self.optimize_inducing:
-                self._z = dev.to_device(theta[3:].reshape(zshape), self.dtype, self._x.device)
+                self._z = dev.to_device(theta[nt:].reshape(zshape), self.dtype, self._x.device)
             try:
-                lml, dtheta, dz = self._block(float(ell), float(sf), float(noise)).lml_grad(self._y, want_z=self.optimize_inducing)
+                lml, dtheta, dz = self._block(ell, sf, noise).lml_grad(self._y, want_z=self.optimize_inducing)
             except np.linalg.LinAlgError:
                 return 1e100, np.zeros(theta.shape[0])
             grad = dtheta if dz is None else np.concatenate([dtheta, dz.double().cpu().numpy().ravel()])
@@ -481,17 +525,17 @@ class SparseGP(RegressionMethod):
 
         res = minimize(objective, theta0, jac=True, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
         if self.optimize_inducing:
-            self._z = dev.to_device(res.x[3:].reshape(zshape), self.dtype, self._x.device)
+            self._z = dev.to_device(res.x[nt:].reshape(zshape), self.dtype, self._x.device)
         return res
 
     def _optimize(self, noise0):
         from scipy.optimize import minimize
-        theta0 = np.log([self.kernel.sf, self.kernel.l, noise0])
+        theta0 = self._start(noise0)
 
         def objective(theta):
-            sf, ell, noise = np.exp(theta)
+            ell, sf, noise = self._unpack(theta)
             try:
-                return -self._block(float(ell), float(sf), float(noise)).fit(self._y).log_marginal_likelihood()
+                return -self._block(ell, sf, noise).fit(self._y).log_marginal_likelihood()
             except np.linalg.LinAlgError:
                 return 1e100
 
@@ -500,23 +544,31 @@ class SparseGP(RegressionMethod):
         else:
             res = minimize(objective, theta0, jac=None, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
         self.optimizer_result = res
-        sf, ell, noise = np.exp(res.x[:3])
-        return float(ell), float(sf), float(noise)
+        return self._unpack(res.x)
 
     def _fit(self, train_data):
         inputs, labels = train_data
+        d = np.atleast_2d(np.asarray(inputs)).shape[1]
+        if self.ARD and np.ndim(self._initial[0]) > 0 and self._initial[0].shape[0] != d:
+            raise ValueError('lengthscale has %d entries, the inputs have %d dimensions' % (self._initial[0].shape[0], d))
         device = dev.require_gpu(self.device)
         inputs = np.atleast_2d(np.asarray(inputs, dtype=np.float64))
         labels = np.atleast_2d(np.asarray(labels, dtype=np.float64))
         self.block = None
-        self.kernel = self._make_kernel(self._initial[0], self._initial[1], float(labels.var()) * NOISE_FRACTION)
+        if self.ARD:
+            self.lengthscales = np.full(d, self._initial[0]) if np.ndim(self._initial[0]) == 0 else self._initial[0].copy()
+            self.kernel = self._make_kernel(1.0, self._initial[1], float(labels.var()) * NOISE_FRACTION)
+        else:
+            self.kernel = self._make_kernel(self._initial[0], self._initial[1], float(labels.var()) * NOISE_FRACTION)
         self._x = dev.to_device(inputs, self.dtype, device)
         self._y = dev.to_device(labels, self.dtype, device)
         self._z = dev.to_device(self._inducing_inputs(inputs), self.dtype, device)
         if self.optimize:
             ell, sf, noise = self._optimize(self.kernel.noise)
+            if self.ARD:
+                self.lengthscales, ell = ell, 1.0
             self.kernel = self._make_kernel(ell, sf, noise)
-        self.block = self._block(self.kernel.l, self.kernel.sf, self.kernel.noise).fit(self._y)
+        self.block = self._block(self.lengthscales if self.ARD else self.kernel.l, self.kernel.sf, self.kernel.noise).fit(self._y)
         z = self._z.double().cpu().numpy()
         self.inducing_inputs = z * self.data_std + self.data_mean if self.preprocess else z
         return True
@@ -550,9 +602,9 @@ class SGP_FITC(SparseGP):
     name = 'SGP_FITC'
 
     def __init__(self, num_inducing=1000, lengthscale=1., variance=1., nu=None, Z=None, seed=0, jitter=1e-6, dtype='f64',
-                 device=None, optimize=False, max_iters=200, jac='2-point', optimize_inducing=False):
+                 device=None, optimize=False, max_iters=200, jac='2-point', optimize_inducing=False, ARD=False):
         super(SGP_FITC, self).__init__(num_inducing, 'fitc', lengthscale, variance, nu, Z, seed, jitter, dtype, device, optimize,
-                                       max_iters, jac, optimize_inducing)
+                                       max_iters, jac, optimize_inducing, ARD)
 
 
 class SparseGP_RBF(SparseGP):
@@ -561,6 +613,6 @@ class SparseGP_RBF(SparseGP):
     name = 'SparseGP_RBF'
 
     def __init__(self, num_inducing=1000, lengthscale=1., variance=1., nu=None, Z=None, seed=0, jitter=1e-6, dtype='f64',
-                 device=None, optimize=False, max_iters=200, jac='2-point', optimize_inducing=False):
+                 device=None, optimize=False, max_iters=200, jac='2-point', optimize_inducing=False, ARD=False):
         super(SparseGP_RBF, self).__init__(num_inducing, 'vfe', lengthscale, variance, nu, Z, seed, jitter, dtype, device, optimize,
-                                           max_iters, jac, optimize_inducing)
+                                           max_iters, jac, optimize_inducing, ARD)

@@ -17,6 +17,9 @@ cimrgp_sparse_grad_rows, cimrgp_sparse_grad_combine and cimrgp_cov_pair_grad on 
 ``SparsePosterior`` makes such blocks a layer of ``MultiResolutionGaussianProcess`` (``KernelClass.SparseKernel``; DESIGN.md,
 "Sparse layers in the multiresolution model"): ``SparseBlock.fit_layer`` / ``predict_layer`` take the noise and the bias
 from device scalars (cimrgp_sparse_lambda_dev, cimrgp_sparse_tail_dev) and read nothing back.
+``SparseBlock(..., lengthscales=)`` gives every input dimension its own length-scale (ARD; DESIGN.md, "ARD length-scales for
+the sparse GP"): the block works on x / l and z / l with a unit length-scale, and ``lml_grad`` takes the d derivatives w.r.t.
+log l_e from cimrgp_cov_pair_grad_ard.
 """
 import numpy as np
 import torch
@@ -32,10 +35,13 @@ PREDICT_BUDGET_BYTES = 1 << 30
 class SparseBlock(object):
     """Device-resident state of one inducing-point block: L_u and L_B with their workspaces, and gamma."""
 
-    def __init__(self, x, z, kernel, approximation='fitc', jitter=1e-6, device_noise=False):
+    def __init__(self, x, z, kernel, approximation='fitc', jitter=1e-6, device_noise=False, lengthscales=None):
         """``x`` (n x d), ``z`` (m x d): device tensors in the same units; ``kernel``: an ``RBFKernel`` /
         ``DenseMaternKernel`` with its ``noise`` set.  ``device_noise``: the block is a model layer's, fitted by
-        :meth:`fit_layer` with its noise variance in a device scalar; ``kernel.noise`` may then be None."""
+        :meth:`fit_layer` with its noise variance in a device scalar; ``kernel.noise`` may then be None.
+        ``lengthscales``: a (d,) array of positive length-scales, one per input dimension (ARD), in the units of ``x``;
+        ``kernel.l`` must then be 1.0, as ``GP_RBF(ARD=True)`` builds its kernel.  The block computes on x / l and z / l;
+        ``x``, ``z``, the test inputs of :meth:`predict` and the dZ of :meth:`lml_grad` stay in the caller's units."""
         key = str(approximation).lower()
         if key not in APPROXIMATIONS:
             raise ValueError("approximation must be 'fitc' or 'vfe', got %r" % (approximation,))
@@ -46,6 +52,19 @@ class SparseBlock(object):
         if x.shape[1] != z.shape[1] or x.dtype != z.dtype:
             raise ValueError('inducing inputs must have the dimension and dtype of the training inputs')
         self.x, self.z = x, z.contiguous()
+        self.lengthscales = self._scale = None
+        self._xs, self._zs = self.x, self.z              # what the covariance calls take: x / l and z / l with lengthscales
+        if lengthscales is not None:
+            ls = np.asarray(lengthscales, dtype=np.float64)
+            if ls.shape != (int(x.shape[1]),) or not (np.isfinite(ls).all() and (ls > 0).all()):
+                raise ValueError('lengthscales must be %d positive numbers, one per input dimension' % int(x.shape[1]))
+            if kernel.l != 1.0:
+                raise ValueError('with lengthscales the kernel must have l = 1.0, got %r' % (kernel.l,))
+            if device_noise:
+                raise ValueError('lengthscales are not available to a model layer (device_noise=True)')
+            self.lengthscales = ls.copy()
+            self._scale = torch.as_tensor(1.0 / ls, dtype=x.dtype, device=x.device)
+            self._xs, self._zs = (self.x * self._scale).contiguous(), (self.z * self._scale).contiguous()
         self.n, self.m = int(x.shape[0]), int(z.shape[0])
         self.kernel = kernel
         self.approximation = 'fitc' if key == 'fitc' else 'vfe'
@@ -61,9 +80,9 @@ class SparseBlock(object):
         """The fit's device calls, nothing read back: (A, w, lambda sums).  A (n x m) is the caller's to free.
         ``noise_dev``: the noise variance as a device scalar, in place of ``kernel.noise``."""
         k, n, m = self.kernel, self.n, self.m
-        self.lu = dev.rbf_gram(self.z, k.l, k.sf, self.jitter * k.sf, lower_only=True, cov=k.cov)
+        self.lu = dev.rbf_gram(self._zs, k.l, k.sf, self.jitter * k.sf, lower_only=True, cov=k.cov)
         self.ws_u, self.info_u = dev.potrf(self.lu, m)
-        a = dev.rbf_cross(self.x, self.z, k.l, k.sf, cov=k.cov)
+        a = dev.rbf_cross(self._xs, self._zs, k.l, k.sf, cov=k.cov)
         dev.trsm_rows(self.lu, m, self.ws_u, a, n)
         if noise_dev is not None:
             _, w, sums = dev.sparse_lambda_dev(a, n, m, k.sf, noise_dev, self.mode)
@@ -154,7 +173,9 @@ class SparseBlock(object):
         """Fit on ``r`` (n x q, device) and return ``(lml, dtheta, dZ)``: the objective :meth:`log_marginal_likelihood`
         returns (bit for bit), its gradient w.r.t. (log sf, log l, log noise) as a NumPy (3,) array and, with ``want_z``,
         w.r.t. the inducing inputs as a device tensor (m x d), else None ("Gradients of the sparse
-        objective").  The failure rules are :meth:`fit`'s.  A stays alive for the length of the call beside ONE more
+        objective").  With ``lengthscales`` the gradient is w.r.t. (log sf, log l_1 .. log l_d, log noise), a (d + 2,) array
+        (cimrgp_cov_pair_grad_ard in place of cimrgp_cov_pair_grad), and dZ is w.r.t. ``z`` in the caller's units.
+        The failure rules are :meth:`fit`'s.  A stays alive for the length of the call beside ONE more
         n x m buffer (V, Y, G_A and G_fu in place of one another); one host read-back at the end (the info words, the
         lambda count and the scalars).  g of Matern 1/2 is taken as 0 at r = 0 (an inducing input on a training input or
         on another inducing input, where the objective has a kink): such pairs contribute nothing to dZ."""
@@ -200,21 +221,26 @@ class SparseBlock(object):
         dev.trsm_rows_lt(self.lu, m, self.ws_u, guu, m)
         guu[:m, :m] = -0.25 * (guu[:m, :m] + guu[:m, :m].t())
         # sum G o K, sum G o dK/dlog l and dZ: K_fu's pairs, then K_uu's added (G_uu symmetric: scale 2 = -2 x -1)
-        psums, dz = dev.cov_pair_grad(self.x, self.z, y, k.l, k.sf, want_db=want_z, cov=k.cov)
-        dev.cov_pair_grad(self.z, self.z, guu, k.l, k.sf, scale=2.0, accumulate=True, sums=psums, db=dz, want_db=want_z, cov=k.cov)
+        # with lengthscales: [sum G o K, sum G o dK/dlog l_e for every e] on the scaled inputs, and dZ of the scaled Z
+        pair_grad = dev.cov_pair_grad if self._scale is None else dev.cov_pair_grad_ard
+        psums, dz = pair_grad(self._xs, self._zs, y, k.l, k.sf, want_db=want_z, cov=k.cov)
+        pair_grad(self._zs, self._zs, guu, k.l, k.sf, scale=2.0, accumulate=True, sums=psums, db=dz, want_db=want_z, cov=k.cov)
         del y
+        if dz is not None and self._scale is not None:
+            dz = dz * self._scale                        # d / dz_je = (d / d(z_je / l_e)) / l_e
         _, half_logdet_b, rwr, gg, _ = self._terms
         host = torch.cat([self.info_u.double(), self.info_b.double(), sums, half_logdet_b.reshape(1), rwr.reshape(1), gg.reshape(1),
                           gsums, psums, torch.diagonal(mm).double().sum().reshape(1),
                           torch.diagonal(guu[:m, :m]).double().sum().reshape(1)]).cpu().numpy()
-        info_u, info_b, s0, s1, bad, hld, rwr_h, gg_h, sum_h, sum_t, gk, gl, tr_m, tr_guu = host
+        info_u, info_b, s0, s1, bad, hld, rwr_h, gg_h, sum_h, sum_t, gk = host[:11]
+        gl, (tr_m, tr_guu) = host[11:-2], host[-2:]      # gl: one entry, or one per length-scale
         self._raise_if_failed(info_u, bad, info_b)
         lml = self._lml_from(s0, s1, hld, rwr_h, gg_h, q)
         dsf = 0.5 * tr_m + k.sf * sum_t
         dnoise = k.noise * (sum_h + (0.5 * q / k.noise ** 2 * s1 if self.mode == 1 else 0.0))
         #: the pairwise form of d F / d log sf, which the closed form above must equal (checked by the GPU tests)
         self.grad_check = dict(closed=float(dsf), pairwise=float(gk + self.jitter * k.sf * tr_guu + k.sf * sum_t))
-        return lml, np.array([dsf, gl, dnoise]), dz
+        return lml, np.concatenate([[dsf], gl, [dnoise]]), dz
 
     def chunk_rows(self, budget_bytes=None):
         """Test rows per pass of ``predict``: A* and W* (pitch padded_ld(m)) within ``budget_bytes``, a multiple of 256."""
@@ -248,7 +274,8 @@ class SparseBlock(object):
             if astar is None:
                 astar = dev.alloc_matrix(min(step, ns), m, xs.dtype, xs.device)
                 wstar = torch.empty_like(astar)
-            dev.rbf_cross(xs[s0:s1], self.z, k.l, k.sf, out=astar, cov=k.cov)
+            xc = xs[s0:s1] if self._scale is None else (xs[s0:s1] * self._scale).contiguous()
+            dev.rbf_cross(xc, self._zs, k.l, k.sf, out=astar, cov=k.cov)
             dev.trsm_rows(self.lu, m, self.ws_u, astar, rows)
             wstar[:rows].copy_(astar[:rows])
             dev.trsm_rows(self.lb, m, self.ws_b, wstar, rows)

@@ -138,6 +138,13 @@ SPARSE_LAYER_SIGNATURES = {
     "cimrgp_sparse_tail_dev": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _i32, _vp]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/cimrgp_sparse_ard.h (ARD length-scales of the sparse GP)
+SPARSE_ARD_SIGNATURES = {
+    "cimrgp_cov_pair_grad_ard_scratch_bytes": (_sz, [_i64, _i64, _i32]),
+    "cimrgp_cov_pair_grad_ard": (_i32, [_i32, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp, _sz,
+                                        _vp]),
+}
+
 _lib = None
 
 
@@ -159,7 +166,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + \
             list(JOINT_SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(LOO_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items()) + \
-            list(SPARSE_GRAD_SIGNATURES.items()) + list(SPARSE_LAYER_SIGNATURES.items()):
+            list(SPARSE_GRAD_SIGNATURES.items()) + list(SPARSE_LAYER_SIGNATURES.items()) + list(SPARSE_ARD_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if a symbol is missing
         fn.restype = res
         fn.argtypes = args

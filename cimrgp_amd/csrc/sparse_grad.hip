@@ -1,8 +1,11 @@
-// Gradients of the sparse (inducing-point) objective: the three calls of include/cimrgp_sparse_grad.h.
+// Gradients of the sparse (inducing-point) objective: the three calls of include/cimrgp_sparse_grad.h and the ARD twin of
+// the first (include/cimrgp_sparse_ard.h).
 //   cov_pair_grad        k_cov_pair_grad    one tile of 128 columns of G and one slice of its rows per workgroup: k, g and
 //                                           dk/dlog l recomputed per pair, the products with G and every sum in FP64;
 //                                           the partial db and the two partial scalar sums go to scratch
 //                        k_pair_grad_reduce adds the partials in slice (and tile) order, applies scale / accumulate
+//   cov_pair_grad_ard    the ARD arm of k_cov_pair_grad: 1 + d scalar sums (sum G k, then sum G g (xa_e - xb_e)^2 per
+//                                           dimension e) in place of the two; the same reduce kernel
 //   sparse_grad_rows     k_sparse_grad_rows (a wave per row: V_i gamma, |V_i|^2 -> beta_i, h_i) and k_sparse_grad_sums
 //                                           (one workgroup: the two sums in a fixed order, t)
 //   sparse_grad_combine  k_sparse_grad_combine (a wave per row, in place on Y)
@@ -14,6 +17,9 @@
 // point of xa is the same address for every lane of the row (one request).  The next row's G chunk and xa point are
 // loaded before the current row's exponentials.  A chunk that straddles column nb, or is not 16-byte aligned, is read
 // element by element: no column >= nb and no row >= na of G is read.
+// The ARD arm keeps d more FP64 sums per lane, sum G g df_e^2 (= sum G dk/dlog l_e at equal length-scales), in place of
+// sum G dk/dlog l: the product wg df_e that db adds is multiplied by df_e once more.  k, g and db are the same
+// instructions in both arms.
 #include "abi.hpp"
 
 namespace cimrgp {
@@ -42,11 +48,13 @@ static inline bool pg_sizes_ok(int64_t na, int64_t nb, int d)
 }
 // doubles of scratch: the partial db, then the partial sums
 static inline int64_t pg_dbpart_elems(int64_t na, int64_t nb, int d) { return pg_slices(na, nb) * pg_tiles(nb) * PG_CT * d; }
-static inline int64_t pg_sumpart_elems(int64_t na, int64_t nb) { return pg_slices(na, nb) * pg_tiles(nb) * 2; }
+static inline int64_t pg_sumpart_elems(int64_t na, int64_t nb, int nsums) { return pg_slices(na, nb) * pg_tiles(nb) * nsums; }
+static inline int pg_nsums(int d, bool ard) { return ard ? 1 + d : 2; }
 
 // k, g (dk/da_e = -g (a_e - b_e)) and dk/dlog l of one pair: the policy's pair() (common.hpp), in the dtype.
-// blockIdx.x = tile + tiles * slice.
-template <typename T, int COV, int D>
+// blockIdx.x = tile + tiles * slice.  A workgroup's scalar sums: [sum G k, sum G dk/dlog l], or with ARD
+// [sum G k, sum G g df_0^2, .., sum G g df_{d-1}^2].
+template <typename T, int COV, int D, bool ARD>
 __global__ __launch_bounds__(256)
 void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb, int nb, int d, const T* __restrict__ G, int64_t ldg,
                      T c, T sf2, int tiles, int slice_len, int want_db, double* __restrict__ dbpart, double* __restrict__ sumpart)
@@ -56,8 +64,9 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
     constexpr int RPI = 64 / LPR;               // rows per wave and load instruction
     constexpr int NPH = 4 * RPI;                // row phases of the workgroup
     constexpr int DD = D ? D : MAXD;
+    constexpr int NS = ARD ? 1 + DD : 2;        // scalar sums of a lane
     __shared__ double red[NPH * PG_CT];
-    __shared__ double sred[4][2];
+    __shared__ double sred[4][NS];
     const int slice = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - slice * tiles;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cx = (lane % LPR) * EPL;          // first column of this lane inside the tile
@@ -87,11 +96,13 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
         for (int k = 0; k < DD; ++k) xr[k] = (D || k < d) ? xa[(int64_t)i * d + k] : (T)0;
     };
 
-    double acc[EPL][DD], sk = 0.0, sl = 0.0;
+    double acc[EPL][DD], sk = 0.0, sl = 0.0, sd[DD];    // sl: not ARD; sd: ARD
 #pragma unroll
     for (int b = 0; b < EPL; ++b)
 #pragma unroll
         for (int k = 0; k < DD; ++k) acc[b][k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < DD; ++k) sd[k] = 0.0;
 
     T gcur[EPL], xcur[DD], gnext[EPL], xnext[DD];
     int i = r0 + phase;
@@ -111,10 +122,13 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
             Cov<COV>::template pair<T, D>(d2, df[0], c, sf2, kv, gv, lv);
             const double w = (double)gcur[b];
             sk += w * (double)kv;
-            sl += w * (double)lv;
+            if constexpr (!ARD) sl += w * (double)lv;
             const double wg = w * (double)gv;
 #pragma unroll
-            for (int k = 0; k < DD; ++k) acc[b][k] += wg * (double)df[k];
+            for (int k = 0; k < DD; ++k) {
+                acc[b][k] += wg * (double)df[k];
+                if constexpr (ARD) sd[k] += (wg * (double)df[k]) * (double)df[k];
+            }
         }
         if (more) {
 #pragma unroll
@@ -124,15 +138,27 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
         }
     }
 
-    // the two scalar sums: pairwise over the lanes of a wave, then the four waves in order
+    // the scalar sums: pairwise over the lanes of a wave, then the four waves in order
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         sk += __shfl_xor(sk, off, 64);
-        sl += __shfl_xor(sl, off, 64);
+        if constexpr (!ARD) sl += __shfl_xor(sl, off, 64);
+        if constexpr (ARD) {
+#pragma unroll
+            for (int k = 0; k < DD; ++k) sd[k] += __shfl_xor(sd[k], off, 64);
+        }
     }
-    if (lane == 0) { sred[wave][0] = sk; sred[wave][1] = sl; }
+    if (lane == 0) {
+        sred[wave][0] = sk;
+        if constexpr (!ARD) sred[wave][1] = sl;
+        if constexpr (ARD) {
+#pragma unroll
+            for (int k = 0; k < DD; ++k) sred[wave][1 + k] = sd[k];
+        }
+    }
     __syncthreads();
-    if (tid < 2) sumpart[(int64_t)blockIdx.x * 2 + tid] = ((sred[0][tid] + sred[1][tid]) + sred[2][tid]) + sred[3][tid];
+    const int ns = ARD ? 1 + d : 2;             // the sums of the dimensions >= d (all 0) are not written
+    if (tid < ns) sumpart[(int64_t)blockIdx.x * ns + tid] = ((sred[0][tid] + sred[1][tid]) + sred[2][tid]) + sred[3][tid];
     if (!want_db) return;
     // db: per dimension, the NPH row phases of a column are added in phase order
     double* out = dbpart + (int64_t)blockIdx.x * PG_CT * d;
@@ -152,13 +178,13 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
     }
 }
 
-// blockIdx.x < dblocks: 256 elements of db, each the sum of its S partials in slice order; the last workgroup (sums
-// wanted): thread t adds the partials t, t + 256, .. of both scalar sums (tile-major within a slice), then the 256
+// blockIdx.x < dblocks: 256 elements of db, each the sum of its S partials in slice order; workgroup dblocks + c (sums
+// wanted, c < nsums): thread t adds the partials t, t + 256, .. of scalar sum c (tile-major within a slice), then the 256
 // partial sums are added pairwise in LDS.
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_pair_grad_reduce(const double* __restrict__ dbpart, const double* __restrict__ sumpart, int nb, int d, int tiles, int slices,
-                        int dblocks, double scale, int accumulate, T* __restrict__ db, double* __restrict__ sums)
+                        int dblocks, int nsums, double scale, int accumulate, T* __restrict__ db, double* __restrict__ sums)
 {
     const int tid = threadIdx.x;
     if ((int)blockIdx.x < dblocks) {
@@ -173,24 +199,18 @@ void k_pair_grad_reduce(const double* __restrict__ dbpart, const double* __restr
         db[e] = accumulate ? (T)((double)db[e] + s) : (T)s;
         return;
     }
-    __shared__ double red[2][256];
+    __shared__ double red[256];
+    const int c = (int)blockIdx.x - dblocks;
     const int64_t parts = (int64_t)tiles * slices;
-    double s0 = 0.0, s1 = 0.0;
-    for (int64_t p = tid; p < parts; p += 256) {
-        s0 += sumpart[2 * p];
-        s1 += sumpart[2 * p + 1];
-    }
-    red[0][tid] = s0;
-    red[1][tid] = s1;
+    double s = 0.0;
+    for (int64_t p = tid; p < parts; p += 256) s += sumpart[nsums * p + c];
+    red[tid] = s;
     __syncthreads();
     for (int half = 128; half > 0; half >>= 1) {
-        if (tid < half) {
-            red[0][tid] += red[0][tid + half];
-            red[1][tid] += red[1][tid + half];
-        }
+        if (tid < half) red[tid] += red[tid + half];
         __syncthreads();
     }
-    if (tid < 2) sums[tid] = accumulate ? sums[tid] + red[tid][0] : red[tid][0];
+    if (tid == 0) sums[c] = accumulate ? sums[c] + red[0] : red[0];
 }
 
 // ----------------------------------------------------------------------- rows ----
@@ -293,7 +313,7 @@ void k_sparse_grad_combine(const T* __restrict__ A, int64_t lda, T* __restrict__
 
 }  // namespace
 
-template <typename T, int COV>
+template <typename T, int COV, bool ARD>
 static int pair_grad_run_cov(const T* xa, int64_t na, const T* xb, int64_t nb, int d, const T* g, int64_t ldg, double ell, double sf2,
                              double scale, int accumulate, double* sums, T* db, double* scratch, hipStream_t st, const char* fn)
 {
@@ -303,35 +323,30 @@ static int pair_grad_run_cov(const T* xa, int64_t na, const T* xb, int64_t nb, i
     const dim3 grid((unsigned)(tiles * slices));
     const T c = (T)cov_scale(COV, ell);
     with_dim(d, [&](auto dd) {
-        hipLaunchKernelGGL((k_cov_pair_grad<T, COV, decltype(dd)::value>), grid, dim3(256), 0, st, xa, (int)na, xb, (int)nb, d, g, ldg, c,
-                           (T)sf2, (int)tiles, (int)len, db != nullptr ? 1 : 0, dbpart, sumpart);
+        hipLaunchKernelGGL((k_cov_pair_grad<T, COV, decltype(dd)::value, ARD>), grid, dim3(256), 0, st, xa, (int)na, xb, (int)nb, d, g, ldg,
+                           c, (T)sf2, (int)tiles, (int)len, db != nullptr ? 1 : 0, dbpart, sumpart);
     });
     CIMRGP_LAUNCH_CHECK(fn);
     const int64_t dblocks = db != nullptr ? (nb * d + 255) / 256 : 0;
-    hipLaunchKernelGGL((k_pair_grad_reduce<T>), dim3((unsigned)(dblocks + (sums != nullptr ? 1 : 0))), dim3(256), 0, st,
-                       (const double*)dbpart, (const double*)sumpart, (int)nb, d, (int)tiles, (int)slices, (int)dblocks, scale, accumulate,
-                       db, sums);
+    const int nsums = pg_nsums(d, ARD);
+    hipLaunchKernelGGL((k_pair_grad_reduce<T>), dim3((unsigned)(dblocks + (sums != nullptr ? nsums : 0))), dim3(256), 0, st,
+                       (const double*)dbpart, (const double*)sumpart, (int)nb, d, (int)tiles, (int)slices, (int)dblocks, nsums, scale,
+                       accumulate, db, sums);
     CIMRGP_LAUNCH_CHECK(fn);
     return 0;
 }
 
-}  // namespace cimrgp
-
-using namespace cimrgp;
-
-extern "C" {
-
-size_t cimrgp_cov_pair_grad_scratch_bytes(int64_t na, int64_t nb, int d)
+static size_t pair_grad_scratch_bytes(int64_t na, int64_t nb, int d, bool ard)
 {
     if (!pg_sizes_ok(na, nb, d)) return 0;
-    return (size_t)(pg_dbpart_elems(na, nb, d) + pg_sumpart_elems(na, nb)) * sizeof(double);
+    return (size_t)(pg_dbpart_elems(na, nb, d) + pg_sumpart_elems(na, nb, pg_nsums(d, ard))) * sizeof(double);
 }
 
-int cimrgp_cov_pair_grad(int dtype, int cov, const void* xa_dev, int64_t na, const void* xb_dev, int64_t nb, int d, const void* g_dev,
-                         int64_t ldg, double ell, double sf2, double scale, int accumulate, double* sums_dev, void* db_dev,
-                         void* scratch_dev, size_t scratch_bytes, void* stream)
+// The entry point of both contractions: `ard` selects the arm (sums_dev: 2 or 1 + d doubles), fn names it in errors.
+static int pair_grad_entry(const char* fn, bool ard, int dtype, int cov, const void* xa_dev, int64_t na, const void* xb_dev, int64_t nb,
+                           int d, const void* g_dev, int64_t ldg, double ell, double sf2, double scale, int accumulate, double* sums_dev,
+                           void* db_dev, void* scratch_dev, size_t scratch_bytes, void* stream)
 {
-    const char* fn = "cimrgp_cov_pair_grad";
     CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
     CIMRGP_REQUIRE(xa_dev && xb_dev && g_dev && scratch_dev, fn, "null pointer");
@@ -341,16 +356,43 @@ int cimrgp_cov_pair_grad(int dtype, int cov, const void* xa_dev, int64_t na, con
     CIMRGP_REQUIRE(ldg >= nb, fn, "leading dimension too small");
     CIMRGP_REQUIRE(ell > 0.0 && sf2 > 0.0, fn, "kernel parameters must be positive");
     CIMRGP_REQUIRE((reinterpret_cast<uintptr_t>(scratch_dev) & 7u) == 0, fn, "scratch must be 8-byte aligned");
-    CIMRGP_REQUIRE(scratch_bytes >= cimrgp_cov_pair_grad_scratch_bytes(na, nb, d), fn, "scratch too small");
+    CIMRGP_REQUIRE(scratch_bytes >= pair_grad_scratch_bytes(na, nb, d, ard), fn, "scratch too small");
     if (sums_dev == nullptr && db_dev == nullptr) return 0;
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         return with_cov(cov, [&](auto cv) {
-            return pair_grad_run_cov<T, decltype(cv)::value>((const T*)xa_dev, na, (const T*)xb_dev, nb, d, (const T*)g_dev, ldg, ell, sf2,
-                                                              scale, accumulate, sums_dev, (T*)db_dev, (double*)scratch_dev,
-                                                              stream_of(stream), fn);
+            constexpr int COV = decltype(cv)::value;
+            auto run = ard ? pair_grad_run_cov<T, COV, true> : pair_grad_run_cov<T, COV, false>;
+            return run((const T*)xa_dev, na, (const T*)xb_dev, nb, d, (const T*)g_dev, ldg, ell, sf2, scale, accumulate, sums_dev,
+                       (T*)db_dev, (double*)scratch_dev, stream_of(stream), fn);
         });
     });
+}
+
+}  // namespace cimrgp
+
+using namespace cimrgp;
+
+extern "C" {
+
+size_t cimrgp_cov_pair_grad_scratch_bytes(int64_t na, int64_t nb, int d) { return pair_grad_scratch_bytes(na, nb, d, false); }
+
+int cimrgp_cov_pair_grad(int dtype, int cov, const void* xa_dev, int64_t na, const void* xb_dev, int64_t nb, int d, const void* g_dev,
+                         int64_t ldg, double ell, double sf2, double scale, int accumulate, double* sums_dev, void* db_dev,
+                         void* scratch_dev, size_t scratch_bytes, void* stream)
+{
+    return pair_grad_entry("cimrgp_cov_pair_grad", false, dtype, cov, xa_dev, na, xb_dev, nb, d, g_dev, ldg, ell, sf2, scale, accumulate,
+                           sums_dev, db_dev, scratch_dev, scratch_bytes, stream);
+}
+
+size_t cimrgp_cov_pair_grad_ard_scratch_bytes(int64_t na, int64_t nb, int d) { return pair_grad_scratch_bytes(na, nb, d, true); }
+
+int cimrgp_cov_pair_grad_ard(int dtype, int cov, const void* xa_dev, int64_t na, const void* xb_dev, int64_t nb, int d, const void* g_dev,
+                             int64_t ldg, double ell, double sf2, double scale, int accumulate, double* sums_dev, void* db_dev,
+                             void* scratch_dev, size_t scratch_bytes, void* stream)
+{
+    return pair_grad_entry("cimrgp_cov_pair_grad_ard", true, dtype, cov, xa_dev, na, xb_dev, nb, d, g_dev, ldg, ell, sf2, scale, accumulate,
+                           sums_dev, db_dev, scratch_dev, scratch_bytes, stream);
 }
 
 int cimrgp_sparse_grad_rows(int dtype, const void* v_dev, int64_t n, int64_t m, int64_t ldv, const void* gamma_dev, const void* r_dev,

@@ -522,26 +522,44 @@ def cov_pair_grad_scratch_bytes(na, nb, d):
     return int(_lib.load().cimrgp_cov_pair_grad_scratch_bytes(int(na), int(nb), int(d)))
 
 
-def cov_pair_grad(xa, xb, gbuf, ell, sf2, scale=1.0, accumulate=False, sums=None, db=None, want_sums=True, want_db=True,
-                  cov=_lib.COV_RBF, scratch=None):
-    """sums (device float64[2]) (+)= [sum G o K, sum G o dK/dlog l] and db (nb x d) (+)= scale sum_i G_ij g(r_ij) (xa_i - xb_j)
-    for G = gbuf[:na, :nb] and the pairs (xa_i, xb_j) (cimrgp_cov_pair_grad, include/cimrgp_sparse_grad.h).  Returns
-    (sums, db); an output that is wanted and not given is allocated, the scratch for this call only if None."""
+def cov_pair_grad_ard_scratch_bytes(na, nb, d):
+    return int(_lib.load().cimrgp_cov_pair_grad_ard_scratch_bytes(int(na), int(nb), int(d)))
+
+
+def _pair_grad(name, nsums, scratch_bytes, xa, xb, gbuf, ell, sf2, scale, accumulate, sums, db, want_sums, want_db, cov, scratch):
+    """The one call of the two pair contractions: the C function ``name`` with ``nsums`` scalar sums."""
     cov = _cov_id(cov)             # an unknown id is refused before any allocation
     lib = _lib.load()
     na, d = xa.shape
     nb = xb.shape[0]
     if want_sums and sums is None:
-        sums = torch.zeros(2, dtype=torch.float64, device=xa.device)
+        sums = torch.zeros(nsums, dtype=torch.float64, device=xa.device)
     if want_db and db is None:
         db = torch.zeros((int(nb), int(d)), dtype=xa.dtype, device=xa.device)
-    nbytes = cov_pair_grad_scratch_bytes(na, nb, d)
+    nbytes = scratch_bytes(na, nb, d)
     if scratch is None:
         scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=xa.device)
-    _lib.check(lib.cimrgp_cov_pair_grad(_DT[xa.dtype], cov, _p(xa), int(na), _p(xb), int(nb), int(d), _p(gbuf), gbuf.stride(0),
-                                        float(ell), float(sf2), float(scale), int(bool(accumulate)), _p(sums if want_sums else None),
-                                        _p(db if want_db else None), _p(scratch), scratch.numel(), _stream()), "cimrgp_cov_pair_grad")
+    _lib.check(getattr(lib, name)(_DT[xa.dtype], cov, _p(xa), int(na), _p(xb), int(nb), int(d), _p(gbuf), gbuf.stride(0),
+                                  float(ell), float(sf2), float(scale), int(bool(accumulate)), _p(sums if want_sums else None),
+                                  _p(db if want_db else None), _p(scratch), scratch.numel(), _stream()), name)
     return sums, db
+
+
+def cov_pair_grad(xa, xb, gbuf, ell, sf2, scale=1.0, accumulate=False, sums=None, db=None, want_sums=True, want_db=True,
+                  cov=_lib.COV_RBF, scratch=None):
+    """sums (device float64[2]) (+)= [sum G o K, sum G o dK/dlog l] and db (nb x d) (+)= scale sum_i G_ij g(r_ij) (xa_i - xb_j)
+    for G = gbuf[:na, :nb] and the pairs (xa_i, xb_j) (cimrgp_cov_pair_grad, include/cimrgp_sparse_grad.h).  Returns
+    (sums, db); an output that is wanted and not given is allocated, the scratch for this call only if None."""
+    return _pair_grad("cimrgp_cov_pair_grad", 2, cov_pair_grad_scratch_bytes, xa, xb, gbuf, ell, sf2, scale, accumulate, sums, db,
+                      want_sums, want_db, cov, scratch)
+
+
+def cov_pair_grad_ard(xa, xb, gbuf, ell, sf2, scale=1.0, accumulate=False, sums=None, db=None, want_sums=True, want_db=True,
+                      cov=_lib.COV_RBF, scratch=None):
+    """The ARD twin of :func:`cov_pair_grad`: sums (device float64[1 + d]) (+)= [sum G o K, sum G g (xa_e - xb_e)^2 for
+    e = 0 .. d - 1], db as there (cimrgp_cov_pair_grad_ard, include/cimrgp_sparse_ard.h).  Returns (sums, db)."""
+    return _pair_grad("cimrgp_cov_pair_grad_ard", 1 + int(xa.shape[1]), cov_pair_grad_ard_scratch_bytes, xa, xb, gbuf, ell, sf2,
+                      scale, accumulate, sums, db, want_sums, want_db, cov, scratch)
 
 
 def sparse_grad_rows(vbuf, n, m, gamma, r, w, mode, noise, beta=None, t=None, sums=None):

@@ -486,4 +486,8 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
  * include/cimrgp_sparse_layer.h. */
 #include "cimrgp_sparse_layer.h"
 
+/* Per-dimension (ARD) length-scale sums of the pair contraction, for the sparse objective with one length-scale per
+ * input dimension: include/cimrgp_sparse_ard.h. */
+#include "cimrgp_sparse_ard.h"
+
 #endif /* CIMRGP_H */
