@@ -39,6 +39,10 @@ class RBFKernel(object):
         """The same covariance with fixed noise variance ``noise``."""
         return RBFKernel(self.l, self.sf, noise)
 
+    def with_values(self, l, sf, noise):
+        """The same covariance class with other values."""
+        return RBFKernel(l, sf, noise)
+
     # ---- scalar-distance protocol (host, NumPy) ---------------------------
     def log_kernel(self, r):
         r = np.asarray(r, dtype=np.float64)
@@ -171,6 +175,10 @@ class DenseMaternKernel(object):
         """The same covariance with fixed noise variance ``noise``."""
         return DenseMaternKernel(self.nu, self.l, self.sf, noise)
 
+    def with_values(self, l, sf, noise):
+        """The same covariance class (and nu) with other values."""
+        return DenseMaternKernel(self.nu, l, sf, noise)
+
     # ---- scalar-distance protocol (host, NumPy) ---------------------------
     def _log_poly(self, t):
         if self.nu == 0.5:
@@ -269,6 +277,10 @@ class SparseKernel(object):
     def with_noise(self, noise):
         """The same sparse layer with fixed noise variance ``noise``."""
         return self.rewrap(self.kernel.with_noise(noise))
+
+    def with_values(self, l, sf, noise):
+        """The same sparse layer around the base covariance with other values."""
+        return self.rewrap(self.kernel.with_values(l, sf, noise))
 
     def inducing_rows(self, layer, region, n):
         """Row numbers (int64, length min(n, num_inducing)) of the inducing inputs of region ``region`` of layer ``layer``

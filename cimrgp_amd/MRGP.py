@@ -27,9 +27,10 @@ import torch
 
 from . import device as dev
 from . import dist
+from .Hyper import minimize_lml, pack_theta, unpack_theta
 from .Inputs import Inputs
 from .KernelClass import RBFKernel, DenseMaternKernel, SparseKernel
-from .Posteriors import DensePosterior
+from .Posteriors import DensePosterior, NOISE_FRACTION
 from .Sparse import SparsePosterior
 
 
@@ -271,34 +272,21 @@ class MultiResolutionGaussianProcess(object):
     def _learn_layer(self, j, f_bar):
         """L-BFGS-B (SciPy) on -sum_l LML_l over theta = (log sf, log l, log noise) of layer j, from the constructor's
         kernel (noise: its own, else NOISE_FRACTION * sf); the layer is then fitted with a NEW kernel object of the
-        same class holding the learned values (the noise fixed and shared by the layer's regions).  A non-PD trial
-        point scores (1e100, 0), as in GP_RBF.  With several ranks every evaluation costs one small all-reduce.
+        same class holding the learned values (the noise fixed and shared by the layer's regions).  A trial point at
+        which a block is not positive definite is a failed point of ``Hyper.minimize_lml``.  With several ranks every
+        evaluation costs one small all-reduce.
         A sparse layer learns its base kernel's values (the inducing inputs stay where the layer's rule puts them) and
         the learned kernel is wrapped in a ``SparseKernel`` with the same settings."""
-        from scipy.optimize import minimize
-        from .Posteriors import NOISE_FRACTION
         k0 = self.spectral_density_obj[j]
-        noise0 = k0.noise if k0.noise is not None else NOISE_FRACTION * k0.sf
-        theta0 = np.log([k0.sf, k0.l, noise0])
 
         def objective(theta):
-            sf, ell, noise = np.exp(theta)
-            lml, grad, failure = self._layer_objective(j, f_bar, ell, sf, noise)
-            if failure != 0.0:
-                return 1e100, np.zeros(3)
-            return -lml, -grad
+            lml, grad, failure = self._layer_objective(j, f_bar, *unpack_theta(theta))
+            return None if failure != 0.0 else (lml, grad)
 
-        res = minimize(objective, theta0, jac=True, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
-        sf, ell, noise = (float(v) for v in np.exp(res.x))
-        base = k0.kernel if isinstance(k0, SparseKernel) else k0
-        if isinstance(base, DenseMaternKernel):
-            kernel = DenseMaternKernel(nu=base.nu, l=ell, sf=sf, noise=noise)
-        else:
-            kernel = RBFKernel(l=ell, sf=sf, noise=noise)
-        if isinstance(k0, SparseKernel):
-            kernel = k0.rewrap(kernel)
+        theta0 = pack_theta(k0.sf, k0.l, k0.noise if k0.noise is not None else NOISE_FRACTION * k0.sf)
+        res = minimize_lml(objective, theta0, self.max_iters)
         self.optimizer_results[j] = res
-        self.posterior_obj[j].kernel = kernel
+        self.posterior_obj[j].kernel = k0.with_values(*unpack_theta(res.x))
 
     def _fit(self):
         n, q = self._y.shape

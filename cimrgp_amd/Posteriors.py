@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import device as dev
+from .Hyper import sum_block_objectives
 
 NOISE_FRACTION = 0.01    # RegressionInput.py:62: labels.var() * 0.01
 NOISE_FLOOR = 1e-8       # x sf: keeps a constant-target block positive definite
@@ -80,6 +81,24 @@ class _Fanout(object):
             self.main.wait_stream(s)
 
 
+def block_targets(kernel, y, f_bar, shared_bias, shared_noise, noise_fraction=NOISE_FRACTION, noise_floor=NOISE_FLOOR):
+    """``(bias, noise, r)`` of one block, exact or sparse, fitted on ``y - f_bar`` (both (n x q) device views): bias (q,) =
+    the column means of ``y - f_bar`` or ``shared_bias``; noise (1,) = ``kernel.noise``, else ``shared_noise``, else
+    max(noise_fraction var(y - f_bar - bias), noise_floor sf); r = y - f_bar - bias.  All on the device, nothing read back."""
+    q = int(y.shape[1])
+    stats = None
+    if shared_bias is None or (shared_noise is None and kernel.noise is None):
+        stats = dev.block_stats(y, f_bar)
+    bias = stats[:q] if shared_bias is None else shared_bias
+    if kernel.noise is not None:
+        noise = torch.full((1,), kernel.noise, dtype=y.dtype, device=y.device)
+    elif shared_noise is not None:
+        noise = shared_noise
+    else:
+        noise = dev.noise_from_stats(stats, q, noise_fraction, noise_floor * kernel.sf)
+    return bias, noise, dev.residual(y, f_bar, bias)
+
+
 class DenseBlock(object):
     """Device-resident state of one (resolution, region) block."""
 
@@ -103,17 +122,7 @@ class DenseBlock(object):
         block's training-point prediction into ``train_out`` (n x q)."""
         q = y.shape[1]
         k = self.kernel
-        stats = None
-        if shared_bias is None or (shared_noise is None and k.noise is None):
-            stats = dev.block_stats(y, f_bar)
-        self.bias = stats[:q] if shared_bias is None else shared_bias
-        if k.noise is not None:
-            self.noise = torch.full((1,), k.noise, dtype=y.dtype, device=y.device)
-        elif shared_noise is not None:
-            self.noise = shared_noise
-        else:
-            self.noise = dev.noise_from_stats(stats, q, NOISE_FRACTION, NOISE_FLOOR * k.sf)
-        self.r = dev.residual(y, f_bar, self.bias)
+        self.bias, self.noise, self.r = block_targets(k, y, f_bar, shared_bias, shared_noise)
         self.lbuf = dev.rbf_gram(self.x, k.l, k.sf, 0.0, lower_only=True, cov=k.cov)
         dev.add_diag(self.lbuf, self.n, self.noise)
         # the targets ride through the factorisation as q extra rows: z = L^-1 r comes out of the
@@ -513,7 +522,7 @@ class DensePosterior(object):
         grad are meaningless when it is not 0.  Equal-sized blocks whose views are slices of one layer array go
         through ONE C call per sub-batch (cimrgp_layer_lml_grad_cov, one host read-back of its results); the others
         (larger than BATCH_MAX_N, or not slices) through the single-block composition
-        (RegressionInput.log_marginal_likelihood)."""
+        (RegressionInput.log_marginal_likelihood), summed with the failure codes of Hyper.sum_block_objectives."""
         from .RegressionInput import log_marginal_likelihood
         regions = list(range(self.n_regions) if owned is None else owned)
         q = self.dy
@@ -521,26 +530,18 @@ class DensePosterior(object):
         shared_bias = None
         if not self.bias_region_specific:
             shared_bias = dev.block_stats(self._whole_layer(y_mean), self._whole_layer(f_bar))[:q]
+
+        def single(l):
+            bias = shared_bias if shared_bias is not None else dev.block_stats(y_mean[l], f_bar[l])[:q]
+            return log_marginal_likelihood(x[l], dev.residual(y_mean[l], f_bar[l], bias), ell, sf2, noise, cov)
+
         lml, grad, failure = 0.0, np.zeros(3), 0.0
         for n_l, group, sliced in _groups_by_size(x, regions, (y_mean, x, f_bar)):
             if n_l <= BATCH_MAX_N and sliced:
                 a, g, f = self._objective_batched(group, ell, sf2, noise, y_mean, x, f_bar, shared_bias)
-                lml, grad, failure = lml + a, grad + g, max(failure, f)
-                continue
-            for l in group:
-                bias = shared_bias if shared_bias is not None else dev.block_stats(y_mean[l], f_bar[l])[:q]
-                r = dev.residual(y_mean[l], f_bar[l], bias)
-                try:
-                    a, g = log_marginal_likelihood(x[l], r, ell, sf2, noise, cov)
-                except np.linalg.LinAlgError:
-                    failure = max(failure, 1.0)
-                    continue
-                except RuntimeError as e:
-                    if 'schedule watchdog' not in str(e):
-                        raise
-                    failure = max(failure, float(dev.INFO_WATCHDOG))
-                    continue
-                lml, grad = lml + a, grad + g
+            else:
+                a, g, f = sum_block_objectives(group, single)
+            lml, grad, failure = lml + a, grad + g, max(failure, f)
         return lml, grad, failure
 
     def _objective_batched(self, group, ell, sf2, noise, y_mean, x, f_bar, shared_bias):

@@ -25,6 +25,7 @@ import torch
 
 from . import device as dev
 from ._lib import COV_RBF
+from .Hyper import minimize_lml, pack_theta, scaled, unit_lengthscale, unpack_theta
 from .KernelClass import RBFKernel, DenseMaternKernel
 from .Posteriors import DenseBlock, NOISE_FRACTION, joint_run
 
@@ -32,9 +33,13 @@ from .Posteriors import DenseBlock, NOISE_FRACTION, joint_run
 def log_marginal_likelihood(x, y, ell, sf, noise, cov=COV_RBF, want_grad=True):
     """One block's LML of targets y (device, n x q) under K = k_cov(x, x) (length-scale ell, variance sf) + noise I, and
     its gradient w.r.t. (log sf, log ell, log noise) as a NumPy (3,) array: Gram, factorisation, solve, log-determinant,
-    K^-1 = L^-T L^-1 (row-wise solve of the identity, SYRK) and the fused gradient reduction.  Raises LinAlgError if K
-    is not PD.  ``GP_RBF.log_marginal_likelihood`` and the MRGP layer objective for blocks the batched call
-    (cimrgp_layer_lml_grad_cov) cannot take both run this."""
+    K^-1 = L^-T L^-1 (row-wise solve of the identity, SYRK) and the fused gradient reduction.  ``ell`` a (d,) vector (ARD):
+    the same on x / ell at unit length-scale, and the gradient is w.r.t. (log sf, log l_1 .. log l_d, log noise), (d + 2,).
+    Raises LinAlgError if K is not PD.  ``GP_RBF.log_marginal_likelihood`` and the MRGP layer objective for blocks the
+    batched call (cimrgp_layer_lml_grad_cov) cannot take both run this."""
+    ard = np.ndim(ell) > 0
+    if ard:
+        x, ell = unit_lengthscale(x, ell)[1], 1.0
     n, q = y.shape
     kbuf = dev.rbf_gram(x, ell, sf, noise, lower_only=True, cov=cov)
     ws, info = dev.potrf(kbuf, n)
@@ -55,8 +60,11 @@ def log_marginal_likelihood(x, y, ell, sf, noise, cov=COV_RBF, want_grad=True):
     kinv.zero_()
     dev.syrk_lower(kinv, u, n, n)            # lower(kinv) = -K^-1
     kinv.neg_()
-    grad = dev.lml_grad(x, kinv, n, alpha, ell, sf, noise, cov=cov).cpu().numpy()
-    return lml, grad
+    if ard:
+        grad = dev.lml_grad_ard(x, kinv, n, alpha, sf, noise, cov=cov)
+    else:
+        grad = dev.lml_grad(x, kinv, n, alpha, ell, sf, noise, cov=cov)
+    return lml, grad.cpu().numpy()
 
 
 class RegressionMethod(object):
@@ -135,67 +143,29 @@ class GP_RBF(RegressionMethod):
     # ---- log marginal likelihood and its gradient, on the GPU ----------------------------
     def log_marginal_likelihood(self, x, y, ell, sf, noise, want_grad=True):
         """LML of targets y (device, n x q) under K = sf E(ell) + noise I, and its gradient
-        w.r.t. (log sf, log ell, log noise).  Raises LinAlgError if K is not PD."""
+        w.r.t. (log sf, log ell, log noise); ``ell`` a (d,) vector: ARD.  Raises LinAlgError if K is not PD."""
         return log_marginal_likelihood(x, y, ell, sf, noise, self.kernel.cov, want_grad)
 
     def log_marginal_likelihood_ard(self, x, y, ells, sf, noise):
         """ARD twin of :meth:`log_marginal_likelihood`: ``ells`` (d,) length-scales; gradient w.r.t.
         (log sf, log l_1 .. log l_d, log noise)."""
-        scale = torch.as_tensor(1.0 / np.asarray(ells, dtype=np.float64), dtype=x.dtype, device=x.device)
-        xs = (x * scale).contiguous()
-        n, q = y.shape
-        cov = self.kernel.cov
-        kbuf = dev.rbf_gram(xs, 1.0, sf, noise, lower_only=True, cov=cov)
-        ws, info = dev.potrf(kbuf, n)
-        alpha = y.clone()
-        dev.potrs(kbuf, n, ws, alpha)
-        dev.raise_if_not_pd(info)
-        half_logdet = float(dev.logdet_half(kbuf, n).item())
-        lml = -0.5 * float((y * alpha).sum().item()) - q * half_logdet - 0.5 * n * q * np.log(2 * np.pi)
-        u = dev.alloc_matrix(n, n, x.dtype, x.device)
-        u.zero_()
-        u[:n, :n].fill_diagonal_(1.0)
-        dev.trsm_rows(kbuf, n, ws, u, n)
-        kinv = dev.alloc_matrix(n, n, x.dtype, x.device)
-        kinv.zero_()
-        dev.syrk_lower(kinv, u, n, n)
-        kinv.neg_()
-        return lml, dev.lml_grad_ard(xs, kinv, n, alpha, sf, noise, cov=cov).cpu().numpy()
-
-    def _optimize_ard(self, x, y, noise0):
-        from scipy.optimize import minimize
-        d = x.shape[1]
-        theta0 = np.log([self.kernel.sf] + [self.kernel.l] * d + [noise0])
-
-        def objective(theta):
-            sf, ells, noise = np.exp(theta[0]), np.exp(theta[1:1 + d]), np.exp(theta[-1])
-            try:
-                lml, grad = self.log_marginal_likelihood_ard(x, y, ells, sf, noise)
-            except np.linalg.LinAlgError:
-                return 1e100, np.zeros(d + 2)
-            return -lml, -grad
-
-        res = minimize(objective, theta0, jac=True, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
-        self.optimizer_result = res
-        self.lengthscales = np.exp(res.x[1:1 + d])
-        self.kernel = self._make_kernel(1.0, float(np.exp(res.x[0])), float(np.exp(res.x[-1])))
+        return self.log_marginal_likelihood(x, y, np.asarray(ells, dtype=np.float64), sf, noise)
 
     def _optimize(self, x, y, noise0):
-        from scipy.optimize import minimize
-        theta0 = np.log([self.kernel.sf, self.kernel.l, noise0])
+        """L-BFGS-B over [log sf, log l (ARD: one per dimension), log noise] from the kernel's values; sets
+        ``optimizer_result``, ``kernel`` (ARD: at l = 1.0) and, under ARD, ``lengthscales``."""
+        n_ell = int(x.shape[1]) if self.ARD else None
+        theta0 = pack_theta(self.kernel.sf, [self.kernel.l] * n_ell if self.ARD else self.kernel.l, noise0)
 
         def objective(theta):
-            sf, ell, noise = np.exp(theta)
-            try:
-                lml, grad = self.log_marginal_likelihood(x, y, ell, sf, noise)
-            except np.linalg.LinAlgError:
-                return 1e100, np.zeros(3)
-            return -lml, -grad
+            return self.log_marginal_likelihood(x, y, *unpack_theta(theta, n_ell))
 
-        res = minimize(objective, theta0, jac=True, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
+        res = minimize_lml(objective, theta0, self.max_iters)
         self.optimizer_result = res
-        sf, ell, noise = np.exp(res.x)
-        self.kernel = self._make_kernel(float(ell), float(sf), float(noise))
+        ell, sf, noise = unpack_theta(res.x, n_ell)
+        if self.ARD:
+            self.lengthscales, ell = ell, 1.0
+        self.kernel = self._make_kernel(ell, sf, noise)
 
     def _fit(self, train_data):
         inputs, labels = train_data
@@ -208,16 +178,13 @@ class GP_RBF(RegressionMethod):
         self.kernel.noise = float(labels.var()) * NOISE_FRACTION
         x = dev.to_device(inputs, self.dtype, device)
         y = dev.to_device(labels, self.dtype, device)
-        if self.ARD:
-            if self.optimize:
-                self._optimize_ard(x, y, self.kernel.noise)
-            else:
-                self.lengthscales = np.full(x.shape[1], self.kernel.l)
-                self.kernel = self._make_kernel(1.0, self.kernel.sf, self.kernel.noise)
-            self._scale = torch.as_tensor(1.0 / self.lengthscales, dtype=self.dtype, device=device)
-            x = (x * self._scale).contiguous()           # unit length-scale from here on
-        elif self.optimize:
+        if self.optimize:
             self._optimize(x, y, self.kernel.noise)
+        elif self.ARD:
+            self.lengthscales = np.full(x.shape[1], self.kernel.l)
+            self.kernel = self._make_kernel(1.0, self.kernel.sf, self.kernel.noise)
+        if self.ARD:
+            self._scale, x = unit_lengthscale(x, self.lengthscales)          # unit length-scale from here on
         self.block = DenseBlock(x, self.kernel)
         zero_bias = torch.zeros(y.shape[1], dtype=self.dtype, device=device)
         sink = torch.zeros_like(y)
@@ -232,9 +199,7 @@ class GP_RBF(RegressionMethod):
     def _test_inputs(self, test_data):
         """The (preprocessed) test inputs on the block's device, in the block's units (ARD: divided by the length-scales)."""
         xs = dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, self.block.x.device)
-        if self.ARD:
-            xs = (xs * self._scale).contiguous()
-        return xs
+        return scaled(xs, self._scale) if self.ARD else xs
 
     def _predict_mean_var(self, test_data, want_var):
         blk = self.block
@@ -467,17 +432,6 @@ class SparseGP(RegressionMethod):
             return self.lengthscales
         return np.full(self.lengthscales.shape[0], float(ell)) if np.ndim(ell) == 0 else np.asarray(ell, dtype=np.float64)
 
-    def _start(self, noise0):
-        """The optimisers' starting point [log sf, log l (ARD: one per dimension), log noise]."""
-        ells = list(self.lengthscales) if self.ARD else [self.kernel.l]
-        return np.log([self.kernel.sf] + ells + [noise0])
-
-    def _unpack(self, theta):
-        """(ell, sf, noise) of an optimiser's parameter vector; what follows them is Z."""
-        nl = self.lengthscales.shape[0] if self.ARD else 1
-        vals = np.exp(theta[:nl + 2])
-        return (vals[1:-1].copy() if self.ARD else float(vals[1])), float(vals[0]), float(vals[-1])
-
     def log_marginal_likelihood(self, ell=None, sf=None, noise=None):
         """The FITC marginal likelihood / the VFE bound of the fitted data at (ell, sf, noise); the fitted values by
         default.  Raises LinAlgError if a factorisation fails or a lambda_i is not positive."""
@@ -502,49 +456,32 @@ class SparseGP(RegressionMethod):
         lml, dtheta, dz = blk.lml_grad(self._y, want_z=want_z)
         return lml, dtheta, None if dz is None else dz.double().cpu().numpy()
 
-    def _optimize_analytic(self, noise0):
-        """L-BFGS-B on the analytic gradient over [log sf, log l (ARD: one per dimension), log noise] and, with
-        ``optimize_inducing``, Z."""
-        from scipy.optimize import minimize
-        theta0 = self._start(noise0)
+    def _optimize(self, noise0):
+        """L-BFGS-B over [log sf, log l (ARD: one per dimension), log noise] and, with ``optimize_inducing``, Z: on the
+        analytic gradient (``jac='analytic'``) or on SciPy's two-point differences of the objective.  Returns the
+        optimum's (ell, sf, noise)."""
+        analytic, learn_z = self.jac == 'analytic', self.optimize_inducing
+        n_ell = self.lengthscales.shape[0] if self.ARD else None
+        theta0 = pack_theta(self.kernel.sf, self.lengthscales if self.ARD else self.kernel.l, noise0)
         nt = theta0.shape[0]
         zshape = tuple(self._z.shape)
-        if self.optimize_inducing:
+        if learn_z:
             theta0 = np.concatenate([theta0, self._z.double().cpu().numpy().ravel()])
 
         def objective(theta):
-            ell, sf, noise = self._unpack(theta)
-            if self.optimize_inducing:
+            if learn_z:
                 self._z = dev.to_device(theta[nt:].reshape(zshape), self.dtype, self._x.device)
-            try:
-                lml, dtheta, dz = self._block(ell, sf, noise).lml_grad(self._y, want_z=self.optimize_inducing)
-            except np.linalg.LinAlgError:
-                return 1e100, np.zeros(theta.shape[0])
-            grad = dtheta if dz is None else np.concatenate([dtheta, dz.double().cpu().numpy().ravel()])
-            return -lml, -grad
+            blk = self._block(*unpack_theta(theta, n_ell))
+            if not analytic:
+                return blk.fit(self._y).log_marginal_likelihood()
+            lml, dtheta, dz = blk.lml_grad(self._y, want_z=learn_z)
+            return lml, dtheta if dz is None else np.concatenate([dtheta, dz.double().cpu().numpy().ravel()])
 
-        res = minimize(objective, theta0, jac=True, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
-        if self.optimize_inducing:
+        res = minimize_lml(objective, theta0, self.max_iters, jac=True if analytic else None)
+        if learn_z:
             self._z = dev.to_device(res.x[nt:].reshape(zshape), self.dtype, self._x.device)
-        return res
-
-    def _optimize(self, noise0):
-        from scipy.optimize import minimize
-        theta0 = self._start(noise0)
-
-        def objective(theta):
-            ell, sf, noise = self._unpack(theta)
-            try:
-                return -self._block(ell, sf, noise).fit(self._y).log_marginal_likelihood()
-            except np.linalg.LinAlgError:
-                return 1e100
-
-        if self.jac == 'analytic':
-            res = self._optimize_analytic(noise0)
-        else:
-            res = minimize(objective, theta0, jac=None, method='L-BFGS-B', options=dict(maxiter=self.max_iters))
         self.optimizer_result = res
-        return self._unpack(res.x)
+        return unpack_theta(res.x, n_ell)
 
     def _fit(self, train_data):
         inputs, labels = train_data

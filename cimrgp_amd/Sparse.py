@@ -25,6 +25,8 @@ import numpy as np
 import torch
 
 from . import device as dev
+from .Hyper import scaled, sum_block_objectives, unit_lengthscale
+from .Posteriors import DensePosterior, NOISE_FRACTION, NOISE_FLOOR, _Fanout, block_targets
 
 APPROXIMATIONS = {'fitc': 0, 'vfe': 1, 'dtc': 1}
 
@@ -63,8 +65,8 @@ class SparseBlock(object):
             if device_noise:
                 raise ValueError('lengthscales are not available to a model layer (device_noise=True)')
             self.lengthscales = ls.copy()
-            self._scale = torch.as_tensor(1.0 / ls, dtype=x.dtype, device=x.device)
-            self._xs, self._zs = (self.x * self._scale).contiguous(), (self.z * self._scale).contiguous()
+            self._scale, self._xs = unit_lengthscale(self.x, ls)
+            self._zs = scaled(self.z, self._scale)
         self.n, self.m = int(x.shape[0]), int(z.shape[0])
         self.kernel = kernel
         self.approximation = 'fitc' if key == 'fitc' else 'vfe'
@@ -118,28 +120,16 @@ class SparseBlock(object):
         self._raise_if_failed(self.info_u, sums[2].item(), self.info_b)
         return self
 
-    def fit_layer(self, y, f_bar, train_out, shared_bias=None, shared_noise=None, noise_fraction=0.01, noise_floor=1e-8):
+    def fit_layer(self, y, f_bar, train_out, shared_bias=None, shared_noise=None, noise_fraction=NOISE_FRACTION,
+                  noise_floor=NOISE_FLOOR):
         """The enqueue-only fit of a model layer's block: NOTHING is read back (``info_u``, ``info_b`` and ``sums[2]``,
         the count of non-positive lambda_i, stay on the device for :meth:`SparsePosterior.failure_flag`).  Targets, bias
-        and noise follow ``DenseBlock.fit``: bias = the column means of ``y - f_bar`` (both n x q device views) or
-        ``shared_bias``; noise = ``kernel.noise``, else ``shared_noise``, else
-        max(noise_fraction var(r), noise_floor sf), a device scalar.  While A is alive the block's training-point
+        and noise are ``DenseBlock.fit``'s (``Posteriors.block_targets``).  While A is alive the block's training-point
         prediction A b + bias, b = L_B^-T gamma (what cimrgp_potrs leaves in c), is added into ``train_out`` (n x q) by
         cimrgp_sparse_tail_dev with A as W*; then A is released.  What stays -- L_u, L_B, their workspaces, gamma, bias,
         noise -- is m x m or smaller, whatever the model's ``keep_factors`` says."""
         k, n, m = self.kernel, self.n, self.m
-        q = int(y.shape[1])
-        stats = None
-        if shared_bias is None or (shared_noise is None and k.noise is None):
-            stats = dev.block_stats(y, f_bar)
-        self.bias = stats[:q] if shared_bias is None else shared_bias
-        if k.noise is not None:
-            self.noise = torch.full((1,), k.noise, dtype=y.dtype, device=y.device)
-        elif shared_noise is not None:
-            self.noise = shared_noise
-        else:
-            self.noise = dev.noise_from_stats(stats, q, noise_fraction, noise_floor * k.sf)
-        r = dev.residual(y, f_bar, self.bias)
+        self.bias, self.noise, r = block_targets(k, y, f_bar, shared_bias, shared_noise, noise_fraction, noise_floor)
         a, w, self.sums = self._enqueue_fit(r, self.noise)
         self.lb, c = dev.wsyrk_tn(a, n, m, w, r, diag_add=1.0)
         self.ws_b, self.info_b = dev.potrf(self.lb, m)
@@ -274,7 +264,7 @@ class SparseBlock(object):
             if astar is None:
                 astar = dev.alloc_matrix(min(step, ns), m, xs.dtype, xs.device)
                 wstar = torch.empty_like(astar)
-            xc = xs[s0:s1] if self._scale is None else (xs[s0:s1] * self._scale).contiguous()
+            xc = xs[s0:s1] if self._scale is None else scaled(xs[s0:s1], self._scale)
             dev.rbf_cross(xc, self._zs, k.l, k.sf, out=astar, cov=k.cov)
             dev.trsm_rows(self.lu, m, self.ws_u, astar, rows)
             wstar[:rows].copy_(astar[:rows])
@@ -345,7 +335,6 @@ class SparsePosterior(object):
 
     def _fan(self, device, items):
         """The stream pool for blocks of (n, m) in ``items``."""
-        from .Posteriors import _Fanout
         return _Fanout(device, len(items), max(equivalent_exact_rows(n, m) for n, m in items))
 
     def update_scale_given_axis(self, y_mean, x, f_bar, train_out, owned=None, keep_factors=True):
@@ -354,7 +343,6 @@ class SparsePosterior(object):
         :meth:`SparseBlock.fit_layer` on a stream of the pool: enqueue-only, nothing is read back.  ``keep_factors`` changes
         nothing here: what a sparse block keeps is m x m (L_u, L_B, their workspaces) or smaller; the n x m matrix A is
         released at the end of every block's fit."""
-        from .Posteriors import DensePosterior, NOISE_FRACTION, NOISE_FLOOR
         regions = list(range(self.n_regions) if owned is None else owned)
         shared_bias = shared_noise = None
         if self.needs_whole_layer():
@@ -398,35 +386,19 @@ class SparsePosterior(object):
         residual targets under (ell, sf2, noise), the sum of :meth:`SparseBlock.lml_grad` (``want_z=False``) over the
         ``owned`` regions; Z follows the layer's rule and stays fixed.  failure: 0, else 1 (a factor not positive definite
         or a non-positive lambda_i) or the watchdog code; lml and grad are meaningless when it is not 0."""
-        from .Posteriors import DensePosterior
-        from .KernelClass import DenseMaternKernel, RBFKernel
         regions = list(range(self.n_regions) if owned is None else owned)
         q = self.dy
-        base = self.kernel.kernel
-        if isinstance(base, DenseMaternKernel):
-            trial = DenseMaternKernel(nu=base.nu, l=ell, sf=sf2, noise=noise)
-        else:
-            trial = RBFKernel(l=ell, sf=sf2, noise=noise)
+        trial = self.kernel.kernel.with_values(ell, sf2, noise)
         shared_bias = None
         if not self.bias_region_specific:
             shared_bias = dev.block_stats(DensePosterior._whole_layer(y_mean), DensePosterior._whole_layer(f_bar))[:q]
-        lml, grad, failure = 0.0, np.zeros(3), 0.0
-        for l in regions:
+
+        def block(l):
             bias = shared_bias if shared_bias is not None else dev.block_stats(y_mean[l], f_bar[l])[:q]
-            r = dev.residual(y_mean[l], f_bar[l], bias)
             blk = self._block(l, x[l], self._inducing_inputs(l, x[l]), kernel=trial)
-            try:
-                a, g, _ = blk.lml_grad(r, want_z=False)
-            except np.linalg.LinAlgError:
-                failure = max(failure, 1.0)
-                continue
-            except RuntimeError as e:
-                if 'schedule watchdog' not in str(e):
-                    raise
-                failure = max(failure, float(dev.INFO_WATCHDOG))
-                continue
-            lml, grad = lml + a, grad + g
-        return lml, grad, failure
+            return blk.lml_grad(dev.residual(y_mean[l], f_bar[l], bias), want_z=False)[:2]
+
+        return sum_block_objectives(regions, block)
 
     def _status(self, l):
         """Device float64 (3,): info_u, the count of non-positive lambda_i, info_b of block l; None if it has none."""
