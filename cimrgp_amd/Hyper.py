@@ -56,12 +56,13 @@ def minimize_lml(objective, theta0, max_iters, jac=True):
     return minimize(negated, theta0, jac=jac, method='L-BFGS-B', options=dict(maxiter=max_iters))
 
 
-def sum_block_objectives(regions, evaluate):
-    """``(lml, grad, failure)``: the sums of ``evaluate(l)`` -> ``(lml, grad (3,))`` over ``regions``, in their order.  A
+def sum_block_objectives(regions, evaluate, n_grad=3):
+    """``(lml, grad, failure)``: the sums of ``evaluate(l)`` -> ``(lml, grad)`` over ``regions``, in their order; grad has the
+    length of the first block's gradient -- 3, or d + 2 under ARD -- and ``n_grad`` zeros when no block gave one.  A
     block that raises ``numpy.linalg.LinAlgError`` is left out of the sums and raises failure to 1, one that raises the
     'schedule watchdog' RuntimeError to ``device.INFO_WATCHDOG``; any other exception propagates.  failure is the largest
     code met: 0 = every block is fine."""
-    lml, grad, failure = 0.0, np.zeros(3), 0.0
+    lml, grad, failure = 0.0, None, 0.0
     for l in regions:
         try:
             a, g = evaluate(l)
@@ -73,5 +74,7 @@ def sum_block_objectives(regions, evaluate):
                 raise
             failure = max(failure, float(dev.INFO_WATCHDOG))
             continue
+        if grad is None:
+            grad = np.zeros(np.shape(g))
         lml, grad = lml + a, grad + g
-    return lml, grad, failure
+    return lml, (np.zeros(n_grad) if grad is None else grad), failure

@@ -15,20 +15,59 @@ reference outputs in tests/golden/kernel_objects.npz).
 import numpy as np
 from scipy.special import kv, gammaln
 
+#: most input dimensions the covariance kernels take, so the most length-scales of an ARD kernel (csrc/common.hpp MAXD)
+MAXD = 8
+
+
+def _lengthscale(l):
+    """``(l, ard)`` of a constructor's ``l``: a scalar stays a float (isotropic); a sequence becomes a fresh float64
+    (d,) array, one length-scale per input dimension (ARD), 1 <= d <= MAXD."""
+    if np.ndim(l) == 0:
+        if not l > 0:
+            raise ValueError('length-scale must be positive')
+        return float(l), False
+    v = np.array(l, dtype=np.float64)
+    if v.ndim != 1 or v.size < 1:
+        raise ValueError('length-scales must be a scalar or a sequence of at least one number')
+    if v.size > MAXD:
+        raise ValueError('at most %d length-scales, got %d' % (MAXD, v.size))
+    if not (np.isfinite(v).all() and (v > 0).all()):
+        raise ValueError('length-scale must be positive')
+    return v, True
+
+
+def _refuse_ard(kernel):
+    """The scalar-distance protocol is a function of ONE distance: an ARD kernel has none."""
+    if kernel.ard:
+        raise TypeError('not yet supported')
+
+
+def _unit_inputs(kernel, x, x2):
+    """``(x, x2, l)`` for the Gram calls: as given with the kernel's ``l``, or, under ARD, divided by the length-scales
+    (``Hyper.unit_lengthscale`` / ``scaled``) with l = 1.0."""
+    if not kernel.ard:
+        return x, x2, kernel.l
+    from .Hyper import scaled, unit_lengthscale
+    for v in (x, x2):
+        if v is not None and int(v.shape[1]) != len(kernel.l):
+            raise ValueError('inputs of dimension %d under %d length-scales' % (int(v.shape[1]), len(kernel.l)))
+    scale, xs = unit_lengthscale(x, kernel.l)
+    return xs, None if x2 is None else scaled(x2, scale), 1.0
+
 
 class RBFKernel(object):
     """k(r) = sf * exp(-r^2 / (2 l^2));  ``sf`` is the signal VARIANCE, as the
     reference's kernels multiply by ``sf`` directly (KernelClass.py:77).
     ``noise``: fixed Gaussian noise variance of the blocks using this kernel,
-    or None for the plugin's rule 0.01 * var(targets) (RegressionInput.py:62)."""
+    or None for the plugin's rule 0.01 * var(targets) (RegressionInput.py:62).
+    ``l``: a scalar (``l`` a float, ``ard`` False) or a sequence of 1 .. MAXD positive numbers, one length-scale per input
+    dimension (``l`` a (d,) float64 array, ``ard`` True): k = sf * exp(-1/2 sum_k ((x_k - x'_k) / l_k)^2)."""
     name = 'RBF'
 
     def __init__(self, l=1., sf=1., noise=None):
-        if not l > 0:
-            raise ValueError('length-scale must be positive')
+        self.l, self.ard = _lengthscale(l)
         if not sf > 0:
             raise ValueError('signal variance must be positive')
-        self.l = float(l)
         self.sf = float(sf)
         self.noise = None if noise is None else float(noise)
 
@@ -45,6 +84,7 @@ class RBFKernel(object):
 
     # ---- scalar-distance protocol (host, NumPy) ---------------------------
     def log_kernel(self, r):
+        _refuse_ard(self)
         r = np.asarray(r, dtype=np.float64)
         return np.log(self.sf) - 0.5 * (r / self.l) ** 2
 
@@ -54,6 +94,7 @@ class RBFKernel(object):
     def log_spectral(self, s):
         # 1-D spectral density in the reference's convention (KernelClass.py:80-90):
         # S(s) = sf * sqrt(2 pi) * l * exp(-l^2 s^2 / 2)
+        _refuse_ard(self)
         s = np.asarray(s, dtype=np.float64)
         return np.log(self.sf) + 0.5 * np.log(2 * np.pi) + np.log(self.l) - 0.5 * (self.l * s) ** 2
 
@@ -70,10 +111,11 @@ class RBFKernel(object):
         """Gram matrix on the GPU.  ``x``/``x2``: CUDA tensors (n x d).  Returns a
         torch view (n x n2) of the padded device buffer."""
         from . import device as dev
+        x, x2, l = _unit_inputs(self, x, x2)
         if x2 is None:
-            buf = dev.rbf_gram(x, self.l, self.sf, diag_add, lower_only)
+            buf = dev.rbf_gram(x, l, self.sf, diag_add, lower_only)
             return buf[:x.shape[0], :x.shape[0]]
-        buf = dev.rbf_cross(x, x2, self.l, self.sf)
+        buf = dev.rbf_cross(x, x2, l, self.sf)
         return buf[:x.shape[0], :x2.shape[0]]
 
     def K(self, x, x2=None, dtype='f64'):
@@ -153,7 +195,9 @@ class DenseMaternKernel(object):
     ``sf`` is the signal VARIANCE and k(0) = sf, as for :class:`RBFKernel`, whose protocol this
     follows; ``spectral`` / ``estimate_kernel`` are those of :class:`MaternKernel` (the reference's
     convention), so that the reduced-rank model over the Laplacian basis converges to this kernel
-    up to the reference's factor sqrt(2).  General real nu stays with :class:`MaternKernel`."""
+    up to the reference's factor sqrt(2).  General real nu stays with :class:`MaternKernel`.
+    ``l``: a scalar, or a sequence of per-dimension length-scales (ARD) as for :class:`RBFKernel`: r is then
+    sqrt(sum_k ((x_k - x'_k) / l_k)^2) at l = 1."""
     name = 'Matern'
     #: nu -> covariance id of the C ABI (include/cimrgp.h CIMRGP_COV_MATERN12/32/52)
     COV_IDS = {0.5: 1, 1.5: 2, 2.5: 3}
@@ -161,12 +205,10 @@ class DenseMaternKernel(object):
     def __init__(self, nu=1.5, l=1., sf=1., noise=None):
         if float(nu) not in self.COV_IDS:
             raise ValueError('nu must be 0.5, 1.5 or 2.5 (general nu: MaternKernel, reduced-rank path only)')
-        if not l > 0:
-            raise ValueError('length-scale must be positive')
+        self.l, self.ard = _lengthscale(l)
         if not sf > 0:
             raise ValueError('signal variance must be positive')
         self.nu = float(nu)
-        self.l = float(l)
         self.sf = float(sf)
         self.noise = None if noise is None else float(noise)
         self.cov = self.COV_IDS[self.nu]
@@ -188,6 +230,7 @@ class DenseMaternKernel(object):
         return np.log1p(t + t * t / 3.0)
 
     def log_kernel(self, r):
+        _refuse_ard(self)
         t = np.sqrt(2 * self.nu) * np.abs(np.asarray(r, dtype=np.float64)) / self.l
         return np.log(self.sf) + self._log_poly(t) - t
 
@@ -195,6 +238,7 @@ class DenseMaternKernel(object):
         return np.exp(self.log_kernel(r))
 
     def _matern(self):
+        _refuse_ard(self)
         return MaternKernel(nu=self.nu, l=self.l, sf=self.sf)
 
     def log_spectral(self, s):
@@ -212,10 +256,11 @@ class DenseMaternKernel(object):
         """Gram matrix on the GPU (k_gram).  ``x``/``x2``: CUDA tensors (n x d).  Returns a
         torch view (n x n2) of the padded device buffer."""
         from . import device as dev
+        x, x2, l = _unit_inputs(self, x, x2)
         if x2 is None:
-            buf = dev.rbf_gram(x, self.l, self.sf, diag_add, lower_only, cov=self.cov)
+            buf = dev.rbf_gram(x, l, self.sf, diag_add, lower_only, cov=self.cov)
             return buf[:x.shape[0], :x.shape[0]]
-        buf = dev.rbf_cross(x, x2, self.l, self.sf, cov=self.cov)
+        buf = dev.rbf_cross(x, x2, l, self.sf, cov=self.cov)
         return buf[:x.shape[0], :x2.shape[0]]
 
     def K(self, x, x2=None, dtype='f64'):
@@ -237,7 +282,8 @@ class SparseKernel(object):
     A region of n rows gets m = min(n, ``num_inducing``) inducing inputs, rows of the region's own (normalised, warped)
     inputs picked by ``inducing``: ``'stride'`` -- rows floor((k + 0.5) n / m), k = 0 .. m - 1 (every row, in order, when
     m = n) -- or ``'random'`` -- ``numpy.random.RandomState([seed, layer, region]).permutation(n)[:m]``.  Either is a
-    function of (seed, layer, region, n) alone.  ``jitter``: eps of K_uu + eps sf I."""
+    function of (seed, layer, region, n) alone.  ``jitter``: eps of K_uu + eps sf I.  ``ard`` is the wrapped kernel's too:
+    a base with per-dimension length-scales makes an ARD sparse layer."""
     INDUCING = ('stride', 'random')
 
     def __init__(self, kernel, num_inducing=1000, approximation='fitc', jitter=1e-6, inducing='stride', seed=0):
@@ -265,6 +311,7 @@ class SparseKernel(object):
     sf = property(lambda self: self.kernel.sf)
     noise = property(lambda self: self.kernel.noise)
     cov = property(lambda self: self.kernel.cov)
+    ard = property(lambda self: self.kernel.ard)
 
     @property
     def nu(self):

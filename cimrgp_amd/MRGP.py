@@ -159,6 +159,9 @@ class MultiResolutionGaussianProcess(object):
             if isinstance(k, SparseKernel) and dev.as_torch_dtype(dtype) != torch.float64:
                 # cond(K_uu + eps sf I) ~ m / eps exceeds what FP32 holds at eps = 1e-6
                 raise TypeError('not yet supported')
+            if k.ard and len(k.l) != x_train.shape[1]:
+                raise ValueError('an ARD kernel with %d length-scales for inputs of dimension %d'
+                                 % (len(k.l), x_train.shape[1]))
         if snr_ratio is not None:
             # reference: initial noise variance of layer 0 from an SNR (MRGP.py:196-199,966-971)
             self.spectral_density_obj = list(self.spectral_density_obj)
@@ -246,7 +249,9 @@ class MultiResolutionGaussianProcess(object):
     def layer_log_marginal_likelihood(self, layer, ell, sf, noise):
         """(lml, grad) of layer ``layer`` at (ell, sf = variance, noise) on the residual targets of the last fit
         (y - f_bar of that layer, the layer's bias rule), summed over all regions and ranks; grad is w.r.t.
-        (log sf, log ell, log noise).  Collective: every rank calls it.  Raises LinAlgError if a block is not PD."""
+        (log sf, log ell, log noise).  ``ell`` a (d,) vector, whatever the layer's own kernel: one length-scale per input
+        dimension (ARD), grad w.r.t. (log sf, log l_1 .. log l_d, log noise).  Collective: every rank calls it.  Raises
+        LinAlgError if a block is not PD."""
         if not self._fitted:
             raise RuntimeError('call fit() before evaluating a layer objective')
         lml, grad, failure = self._layer_objective(layer, self._f_bar_layers[layer], ell, sf, noise)
@@ -264,7 +269,7 @@ class MultiResolutionGaussianProcess(object):
             buf = torch.tensor([lml] + list(grad) + [failure], dtype=torch.float64, device=self.device)
             dist.allreduce_sum_(buf, self.group)
             vals = buf.cpu().numpy()
-            lml, grad, failure = float(vals[0]), vals[1:4], float(vals[4])
+            lml, grad, failure = float(vals[0]), vals[1:-1], float(vals[-1])       # grad: 3 entries, or d + 2 under ARD
         if dev.is_watchdog(failure):
             raise RuntimeError('cimrgp_potrf: schedule watchdog while evaluating the objective of layer %d' % j)
         return lml, np.asarray(grad, dtype=np.float64), failure
@@ -276,17 +281,20 @@ class MultiResolutionGaussianProcess(object):
         which a block is not positive definite is a failed point of ``Hyper.minimize_lml``.  With several ranks every
         evaluation costs one small all-reduce.
         A sparse layer learns its base kernel's values (the inducing inputs stay where the layer's rule puts them) and
-        the learned kernel is wrapped in a ``SparseKernel`` with the same settings."""
+        the learned kernel is wrapped in a ``SparseKernel`` with the same settings.
+        An ARD kernel learns its d length-scales: theta = (log sf, log l_1 .. log l_d, log noise), from the constructor's
+        vector (``RBFKernel(l=[1., 1.])`` starts an ARD search from an isotropic point)."""
         k0 = self.spectral_density_obj[j]
+        n_ell = len(k0.l) if k0.ard else None
 
         def objective(theta):
-            lml, grad, failure = self._layer_objective(j, f_bar, *unpack_theta(theta))
+            lml, grad, failure = self._layer_objective(j, f_bar, *unpack_theta(theta, n_ell))
             return None if failure != 0.0 else (lml, grad)
 
         theta0 = pack_theta(k0.sf, k0.l, k0.noise if k0.noise is not None else NOISE_FRACTION * k0.sf)
         res = minimize_lml(objective, theta0, self.max_iters)
         self.optimizer_results[j] = res
-        self.posterior_obj[j].kernel = k0.with_values(*unpack_theta(res.x))
+        self.posterior_obj[j].kernel = k0.with_values(*unpack_theta(res.x, n_ell))
 
     def _fit(self):
         n, q = self._y.shape

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import device as dev
-from .Hyper import sum_block_objectives
+from .Hyper import scaled, sum_block_objectives, unit_lengthscale
 
 NOISE_FRACTION = 0.01    # RegressionInput.py:62: labels.var() * 0.01
 NOISE_FLOOR = 1e-8       # x sf: keeps a constant-target block positive definite
@@ -103,6 +103,9 @@ class DenseBlock(object):
     """Device-resident state of one (resolution, region) block."""
 
     def __init__(self, x, kernel):
+        if getattr(kernel, 'ard', False):
+            # one length-scale per dimension: the layer object scales the inputs (DensePosterior); a block runs at one l
+            raise TypeError('a DenseBlock takes an isotropic kernel: under ARD pass x / l and kernel.with_values(1.0, sf, noise)')
         self.x = x                       # (n x d) device view, normalised inputs
         self.n = int(x.shape[0])
         self.kernel = kernel
@@ -229,6 +232,23 @@ def _layer_array(views, group):
             return None
         rows = max(rows, v.storage_offset() // v.stride(0) + v.shape[0])
     return torch.as_strided(v0, (int(rows), int(v0.shape[1])), v0.stride(), 0)
+
+
+def scale_layer_inputs(x, lengthscales):
+    """``(scale, x_all, views)`` of a layer's inputs under per-dimension length-scales (ARD): ``scale`` = 1 / lengthscales
+    (``Hyper.unit_lengthscale``), ``views[l]`` = x[l] * scale for the region views ``x``.  When these are row ranges of one
+    array (:func:`_layer_array`) there is ONE scaled copy ``x_all`` of it (rows x d) and the views are the same row ranges
+    of that copy, so that the batched calls still address a block by one row offset; else x_all is None."""
+    ls = np.asarray(lengthscales, dtype=np.float64)
+    if ls.shape != (int(x[0].shape[1]),):
+        raise ValueError('%d length-scales for inputs of dimension %d' % (ls.size, int(x[0].shape[1])))
+    whole = _layer_array(x, list(range(len(x))))
+    if whole is None:
+        scale = unit_lengthscale(x[0], ls)[0]
+        return scale, None, [scaled(v, scale) for v in x]
+    scale, x_all = unit_lengthscale(whole, ls)
+    rows = [v.storage_offset() // v.stride(0) for v in x]
+    return scale, x_all, [x_all[r:r + int(v.shape[0])] for r, v in zip(rows, x)]
 
 
 def _same_rows(arrays, group):
@@ -425,6 +445,37 @@ class DensePosterior(object):
         self.blocks = [None] * self.n_regions
         self.batches = []                # _FittedBatch records of the last sweep (equal-sized blocks fitted together)
 
+    # An ARD kernel (``kernel.ard``): the layer computes on inputs divided by the length-scales, under the same covariance
+    # at l = 1.0 ("ARD length-scales for the model's layers").  The scaled copy of the training inputs belongs
+    # to the kernel: setting ``kernel`` drops it, the next call that takes the region views makes it, and every call until
+    # the kernel changes shares it.
+    @property
+    def kernel(self):
+        return self._kernel
+
+    @kernel.setter
+    def kernel(self, kernel):
+        self._kernel = kernel
+        self._unit = kernel.with_values(1.0, kernel.sf, kernel.noise) if getattr(kernel, 'ard', False) else kernel
+        self._ard = None                 # (key of the region views, scale, scaled layer array, scaled region views)
+
+    def _scaled_train(self, x):
+        """``x`` (region views) as the device calls take them: as given, or the views of the ARD copy."""
+        if not self._kernel.ard:
+            return x
+        key = (x[0].untyped_storage().data_ptr(), x[0].dtype, tuple((v.storage_offset(), int(v.shape[0])) for v in x))
+        if self._ard is None or self._ard[0] != key:
+            self._ard = (key,) + scale_layer_inputs(x, self._kernel.l)
+        return self._ard[3]
+
+    def _scaled_test(self, x_all, xs):
+        """``(x_all, xs)`` of a prediction: as given, or the ARD copy of the fit and ``xs`` in its units."""
+        if not self._kernel.ard:
+            return x_all, xs
+        if self._ard is None:
+            raise RuntimeError('an ARD layer predicts after it was fitted')
+        return self._ard[2], scaled(xs, self._ard[1])
+
     def needs_whole_layer(self):
         """Whether the layer's fit reads statistics over ALL its regions (a shared bias, or a shared noise taken from
         the targets): such a layer needs the whole latent function on every rank (MRGP._fit)."""
@@ -449,6 +500,7 @@ class DensePosterior(object):
         self.batches = []
         if not regions:
             return
+        x, k = self._scaled_train(x), self._unit
         # equal-sized small blocks: one batch per size (a uniform index set has at most two sizes per
         # layer, the last region taking the remainder, IndexSetGenerator.py:51-65)
         single = []
@@ -462,7 +514,7 @@ class DensePosterior(object):
         fan = _Fanout(y_mean[single[0]].device, len(single), max(int(x[l].shape[0]) for l in single))
         for l in single:
             with torch.cuda.stream(fan.stream()):
-                blk = DenseBlock(x[l], self.kernel)
+                blk = DenseBlock(x[l], k)
                 blk.fit(y_mean[l], f_bar[l], train_out[l], shared_bias, shared_noise, keep_factor=keep_factors)
                 if fan.pool:
                     blk.hand_over_to(fan.main)
@@ -475,7 +527,7 @@ class DensePosterior(object):
         backward solve and the training-point prediction are each launched once for all the blocks.  The
         matrices live in one arena (batch x n x ld); a group whose arena would not fit the free memory is cut
         into sub-batches (and the arena of a sub-batch is dropped at once when the factors are not kept)."""
-        k = self.kernel
+        k = self._unit                   # x: what _scaled_train gave
         n = int(x[group[0]].shape[0])
         q = self.dy
         device, dtype, ld, ws_bytes, per_call = _arena_geometry(
@@ -522,11 +574,17 @@ class DensePosterior(object):
         grad are meaningless when it is not 0.  Equal-sized blocks whose views are slices of one layer array go
         through ONE C call per sub-batch (cimrgp_layer_lml_grad_cov, one host read-back of its results); the others
         (larger than BATCH_MAX_N, or not slices) through the single-block composition
-        (RegressionInput.log_marginal_likelihood), summed with the failure codes of Hyper.sum_block_objectives."""
+        (RegressionInput.log_marginal_likelihood), summed with the failure codes of Hyper.sum_block_objectives.
+        ``ell`` a (d,) vector is ARD, whatever ``self.kernel`` is: grad has d + 2 entries ordered as ``Hyper.pack_theta``
+        (sf, l_1 .. l_d, noise); the inputs are scaled once per evaluation and the batched call is
+        cimrgp_layer_lml_grad_ard_cov."""
         from .RegressionInput import log_marginal_likelihood
         regions = list(range(self.n_regions) if owned is None else owned)
         q = self.dy
         cov = self.kernel.cov
+        ard = np.ndim(ell) > 0
+        n_grad = int(x[0].shape[1]) + 2 if ard else 3
+        xb = scale_layer_inputs(x, ell)[2] if ard else x         # what the batched call takes
         shared_bias = None
         if not self.bias_region_specific:
             shared_bias = dev.block_stats(self._whole_layer(y_mean), self._whole_layer(f_bar))[:q]
@@ -535,25 +593,28 @@ class DensePosterior(object):
             bias = shared_bias if shared_bias is not None else dev.block_stats(y_mean[l], f_bar[l])[:q]
             return log_marginal_likelihood(x[l], dev.residual(y_mean[l], f_bar[l], bias), ell, sf2, noise, cov)
 
-        lml, grad, failure = 0.0, np.zeros(3), 0.0
-        for n_l, group, sliced in _groups_by_size(x, regions, (y_mean, x, f_bar)):
+        lml, grad, failure = 0.0, np.zeros(n_grad), 0.0
+        for n_l, group, sliced in _groups_by_size(xb, regions, (y_mean, xb, f_bar)):
             if n_l <= BATCH_MAX_N and sliced:
-                a, g, f = self._objective_batched(group, ell, sf2, noise, y_mean, x, f_bar, shared_bias)
+                a, g, f = self._objective_batched(group, ell, sf2, noise, y_mean, xb, f_bar, shared_bias)
             else:
-                a, g, f = sum_block_objectives(group, single)
+                a, g, f = sum_block_objectives(group, single, n_grad)
             lml, grad, failure = lml + a, grad + g, max(failure, f)
         return lml, grad, failure
 
     def _objective_batched(self, group, ell, sf2, noise, y_mean, x, f_bar, shared_bias):
         """:meth:`layer_objective` of ``group`` (regions of equal size): sub-batches sized by the free memory as in
-        :meth:`_fit_batched` (the K^-1 arena and the carried identity rows on top of the factor)."""
+        :meth:`_fit_batched` (the K^-1 arena and the carried identity rows on top of the factor).  ``ell`` a vector: ``x``
+        holds the inputs divided by it, and the records have d + 3 entries."""
         n = int(x[group[0]].shape[0])
         q = self.dy
-        scratch = dev.layer_lml_scratch_bytes(n, q, 1, y_mean[group[0]].dtype)
+        ard = np.ndim(ell) > 0
+        width = int(x[group[0]].shape[1]) + 3 if ard else 4
+        scratch = (dev.layer_lml_ard_scratch_bytes if ard else dev.layer_lml_scratch_bytes)(n, q, 1, y_mean[group[0]].dtype)
         device, dtype, ld, ws_bytes, per_call = _arena_geometry(
             y_mean[group[0]], n, len(group), lambda ld, ws, esz: 2 * n * ld * esz + ws + scratch, 0.8)
         y_all, x_all, f_all = _layer_array(y_mean, group), _layer_array(x, group), _layer_array(f_bar, group)
-        lml, grad, failure = 0.0, np.zeros(3), 0.0
+        lml, grad, failure = 0.0, np.zeros(width - 1), 0.0
         for c0 in range(0, len(group), per_call):
             sub = group[c0:c0 + per_call]
             nb = len(sub)
@@ -562,12 +623,16 @@ class DensePosterior(object):
             kinv = torch.empty((nb, n, ld), dtype=dtype, device=device)
             ws_arena = torch.empty((nb, ws_bytes), dtype=torch.uint8, device=device)
             info = torch.zeros(nb, dtype=torch.int32, device=device)
-            out = torch.empty((nb, 4), dtype=torch.float64, device=device)
-            dev.layer_lml_grad(x_all, y_all, f_all, starts, n, ell, sf2, noise, shared_bias, karena, kinv, ws_arena, info, out,
-                               cov=self.kernel.cov)
+            out = torch.empty((nb, width), dtype=torch.float64, device=device)
+            if ard:
+                dev.layer_lml_grad_ard(x_all, y_all, f_all, starts, n, sf2, noise, shared_bias, karena, kinv, ws_arena, info, out,
+                                       cov=self.kernel.cov)
+            else:
+                dev.layer_lml_grad(x_all, y_all, f_all, starts, n, ell, sf2, noise, shared_bias, karena, kinv, ws_arena, info, out,
+                                   cov=self.kernel.cov)
             del karena, kinv, ws_arena
             res = torch.cat([out.reshape(-1), info.to(torch.float64)]).cpu().numpy()     # one read-back per call
-            vals, infos = res[:4 * nb].reshape(nb, 4), res[4 * nb:]
+            vals, infos = res[:width * nb].reshape(nb, width), res[width * nb:]
             if np.any(infos != 0):
                 failure = max(failure, float(infos.max()))
                 continue
@@ -609,7 +674,8 @@ class DensePosterior(object):
         together and have equally many test points go through ONE batched call per sub-batch
         (cimrgp_layer_predict); the others one by one on the stream pool (:meth:`_run_layer`).  ``var`` None: the mean
         alone, every block through the fused :func:`device.predict_mean`, which never forms W."""
-        k = self.kernel
+        k = self._unit
+        x_all, xs = self._scaled_test(x_all, xs)
 
         def batched(bt, t_starts, ns):
             dev.layer_predict(x_all, bt.starts, bt.n, xs, t_starts, ns, k.l, k.sf, bt.karena, bt.ws_arena, bt.z, bt.bias,
@@ -624,8 +690,16 @@ class DensePosterior(object):
     def predict_grad_layer(self, x_all, xs, test_bounds, owned, mean_grad, var_grad):
         """Accumulate the layer's predictive gradients at the test points (test block l = rows test_bounds[l] of ``xs``,
         served by training block l) through :meth:`_run_layer`: ONE cimrgp_layer_predict_grad_cov call per sub-batch
-        (with :meth:`_FittedBatch.alpha`), the others one by one on the stream pool."""
-        k = self.kernel
+        (with :meth:`_FittedBatch.alpha`), the others one by one on the stream pool.
+        An ARD layer's calls differentiate w.r.t. the SCALED test inputs: it computes into zeroed buffers of its own and adds
+        them times 1 / l_k along d (d f / d x_k = (d f / d (x_k / l_k)) / l_k) into the buffers the layers share."""
+        k = self._unit
+        ard_out = None
+        if self._kernel.ard:
+            ard_out = (mean_grad, var_grad)
+            x_all, xs = self._scaled_test(x_all, xs)
+            mean_grad = None if mean_grad is None else torch.zeros_like(mean_grad)
+            var_grad = None if var_grad is None else torch.zeros_like(var_grad)
 
         def batched(bt, t_starts, ns):
             dev.layer_predict_grad(x_all, bt.starts, bt.n, xs, t_starts, ns, k.l, k.sf, bt.karena, bt.ws_arena, bt.alpha(),
@@ -637,6 +711,12 @@ class DensePosterior(object):
         self._run_layer(owned, test_bounds, xs.device,
                         lambda bt, ns: (ns * dev.padded_ld(bt.n) + 2 * bt.n * self.dy) * xs.element_size(),
                         lambda: 0.5 * free_device_bytes(xs.device), batched, single)
+        if ard_out is not None:
+            scale = self._ard[1]
+            if mean_grad is not None:
+                ard_out[0].add_(mean_grad * scale[None, :, None])
+            if var_grad is not None:
+                ard_out[1].add_(var_grad * scale[None, :])
 
     def loo_layer(self, y_all, y, owned, mean, var):
         """Leave-one-out prediction of the layer's own targets by its ``owned`` blocks (:meth:`DenseBlock.loo`), written
@@ -663,6 +743,7 @@ class DensePosterior(object):
         ONE cimrgp_layer_joint_cov call per sub-batch and the other blocks as batches of one; they run afterwards, in
         that order (``joint_run`` reads ``info`` back per call).  Returns the largest relative jitter used."""
         calls = []
+        x_all, xs = self._scaled_test(x_all, xs)
 
         def per_block(bt, ns):
             ldc, ldw = dev.joint_ld(ns, xs.dtype), dev.joint_ld(bt.n, xs.dtype)
@@ -673,7 +754,7 @@ class DensePosterior(object):
                         lambda l, a, b: calls.append(self.blocks[l].joint_call(l, a, b)), fan_out=False)
         used = 0.0
         for call in calls:
-            used = max(used, joint_run(call, self.kernel, xs, layer, add_noise, cov_out, samples, seed, jitter))
+            used = max(used, joint_run(call, self._unit, xs, layer, add_noise, cov_out, samples, seed, jitter))
         return used
 
     @staticmethod

@@ -307,6 +307,7 @@ class SparsePosterior(object):
         self.bias_region_specific = bias_region_specific
         self.blocks = [None] * self.n_regions
         self._z = {}                     # region -> (key of its inputs, Z on the device)
+        self._scale = {}                 # region -> 1 / l on the device, of the last fit under an ARD base kernel
 
     def needs_whole_layer(self):
         """As ``DensePosterior.needs_whole_layer``: a shared bias, or a shared noise taken from the targets."""
@@ -330,8 +331,24 @@ class SparsePosterior(object):
         return self._z[l][1]
 
     def _block(self, l, x_l, z, kernel=None):
+        """The block of region l: the layer's own for a fit (``kernel`` None; noise on the device), or one under the trial
+        kernel ``kernel`` for the objective.  An ARD kernel ("ARD length-scales for the model's layers") runs at
+        l = 1.0 on x / l and Z / l, Z being rows of x picked by index as ever: the objective's block does the scaling itself
+        (``lengthscales=``); the layer's block, which takes no ``lengthscales``, is built on inputs scaled here, and
+        :meth:`predict_layer` scales the test inputs with the ``self._scale[l]`` kept for it."""
         k = self.kernel
-        return SparseBlock(x_l, z, k.kernel if kernel is None else kernel, k.approximation, k.jitter, device_noise=kernel is None)
+        base = k.kernel if kernel is None else kernel
+        if not base.ard:
+            if kernel is None:
+                self._scale.pop(l, None)
+            return SparseBlock(x_l, z, base, k.approximation, k.jitter, device_noise=kernel is None)
+        if int(x_l.shape[1]) != len(base.l):
+            raise ValueError('%d length-scales for inputs of dimension %d' % (len(base.l), int(x_l.shape[1])))
+        unit = base.with_values(1.0, base.sf, base.noise)
+        if kernel is not None:
+            return SparseBlock(x_l, z, unit, k.approximation, k.jitter, lengthscales=base.l)
+        self._scale[l], xs = unit_lengthscale(x_l, base.l)
+        return SparseBlock(xs, scaled(z, self._scale[l]), unit, k.approximation, k.jitter, device_noise=True)
 
     def _fan(self, device, items):
         """The stream pool for blocks of (n, m) in ``items``."""
@@ -378,14 +395,16 @@ class SparsePosterior(object):
         fan = self._fan(xs.device, [(b - a, self.blocks[l].m) for l, a, b in rest])
         for l, a, b in rest:
             with torch.cuda.stream(fan.stream()):
-                self.blocks[l].predict_layer(xs[a:b], mean[a:b], None if var is None else var[a:b], add_noise)
+                xq = xs[a:b] if l not in self._scale else scaled(xs[a:b], self._scale[l])
+                self.blocks[l].predict_layer(xq, mean[a:b], None if var is None else var[a:b], add_noise)
         fan.join()
 
     def layer_objective(self, ell, sf2, noise, y_mean, x, f_bar, owned=None):
         """As ``DensePosterior.layer_objective``: (lml, grad w.r.t. (log sf2, log ell, log noise), failure) of the layer's
         residual targets under (ell, sf2, noise), the sum of :meth:`SparseBlock.lml_grad` (``want_z=False``) over the
         ``owned`` regions; Z follows the layer's rule and stays fixed.  failure: 0, else 1 (a factor not positive definite
-        or a non-positive lambda_i) or the watchdog code; lml and grad are meaningless when it is not 0."""
+        or a non-positive lambda_i) or the watchdog code; lml and grad are meaningless when it is not 0.  ``ell`` a (d,)
+        vector is ARD: grad has d + 2 entries, (log sf2, log l_1 .. log l_d, log noise)."""
         regions = list(range(self.n_regions) if owned is None else owned)
         q = self.dy
         trial = self.kernel.kernel.with_values(ell, sf2, noise)
@@ -398,7 +417,7 @@ class SparsePosterior(object):
             blk = self._block(l, x[l], self._inducing_inputs(l, x[l]), kernel=trial)
             return blk.lml_grad(dev.residual(y_mean[l], f_bar[l], bias), want_z=False)[:2]
 
-        return sum_block_objectives(regions, block)
+        return sum_block_objectives(regions, block, np.size(ell) + 2)
 
     def _status(self, l):
         """Device float64 (3,): info_u, the count of non-positive lambda_i, info_b of block l; None if it has none."""

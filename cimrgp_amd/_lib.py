@@ -145,6 +145,13 @@ SPARSE_ARD_SIGNATURES = {
                                         _vp]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/cimrgp_layer_ard.h (the layer objective under ARD)
+LAYER_ARD_SIGNATURES = {
+    "cimrgp_layer_lml_grad_ard_scratch_bytes": (_sz, [_i32, _i64, _i32, _i32]),
+    "cimrgp_layer_lml_grad_ard_cov": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _dbl, _dbl, _vp, _vp, _i64, _i64,
+                                             _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -166,7 +173,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + \
             list(JOINT_SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(LOO_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items()) + \
-            list(SPARSE_GRAD_SIGNATURES.items()) + list(SPARSE_LAYER_SIGNATURES.items()) + list(SPARSE_ARD_SIGNATURES.items()):
+            list(SPARSE_GRAD_SIGNATURES.items()) + list(SPARSE_LAYER_SIGNATURES.items()) + list(SPARSE_ARD_SIGNATURES.items()) + \
+            list(LAYER_ARD_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if a symbol is missing
         fn.restype = res
         fn.argtypes = args

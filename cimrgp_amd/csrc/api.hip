@@ -645,16 +645,22 @@ int cimrgp_layer_predict_cov(int dtype, int cov, const void* x_dev, const int64_
 size_t cimrgp_layer_lml_grad_scratch_bytes(int dtype, int64_t n, int q, int batch)
 {
     if (!dtype_known(dtype) || n <= 0 || q < 1 || batch < 1) return 0;
-    return lml_scratch_layout(elem_bytes(dtype), n, q, batch).total;
+    return lml_scratch_layout(elem_bytes(dtype), n, q, batch, lml_grad_record_width(false)).total;
 }
 
-int cimrgp_layer_lml_grad_cov(int dtype, int cov, const void* x_dev, const void* y_dev, const void* fbar_dev,
-                              const int64_t* starts_dev, int batch, int64_t n, int d, int q, double ell, double sf2,
-                              double noise, const void* shared_bias_dev, void* k_arena_dev, int64_t ldk, int64_t k_stride,
-                              void* kinv_arena_dev, void* ws_arena_dev, size_t ws_stride_bytes, int32_t* info_dev,
-                              void* scratch_dev, double* out_dev, void* stream)
+size_t cimrgp_layer_lml_grad_ard_scratch_bytes(int dtype, int64_t n, int q, int batch)
 {
-    const char* fn = "cimrgp_layer_lml_grad_cov";
+    if (!dtype_known(dtype) || n <= 0 || q < 1 || batch < 1) return 0;
+    return lml_scratch_layout(elem_bytes(dtype), n, q, batch, lml_grad_record_width(true)).total;
+}
+
+// cimrgp_layer_lml_grad_cov and cimrgp_layer_lml_grad_ard_cov; ard: pre-scaled inputs, unit length-scale (ell = 1.0 passed)
+static int layer_lml_grad_impl(const char* fn, bool ard, int dtype, int cov, const void* x_dev, const void* y_dev,
+                               const void* fbar_dev, const int64_t* starts_dev, int batch, int64_t n, int d, int q, double ell,
+                               double sf2, double noise, const void* shared_bias_dev, void* k_arena_dev, int64_t ldk,
+                               int64_t k_stride, void* kinv_arena_dev, void* ws_arena_dev, size_t ws_stride_bytes,
+                               int32_t* info_dev, void* scratch_dev, double* out_dev, void* stream)
+{
     CIMRGP_REQUIRE(x_dev && y_dev && starts_dev && k_arena_dev && kinv_arena_dev && ws_arena_dev && info_dev && scratch_dev && out_dev,
                    fn, "null pointer");
     CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
@@ -680,8 +686,30 @@ int cimrgp_layer_lml_grad_cov(int dtype, int cov, const void* x_dev, const void*
         fr.y = (const T*)y_dev; fr.fbar = (const T*)fbar_dev; fr.q = q; fr.shared_bias = (const T*)shared_bias_dev;
         fr.noise_fixed = noise;
         a.kinv = (T*)kinv_arena_dev; a.scratch = scratch_dev; a.out = out_dev;
-        return layer_lml_grad_run<T>(a, stream_of(stream));
+        return layer_lml_grad_run<T>(a, stream_of(stream), ard);
     });
+}
+
+int cimrgp_layer_lml_grad_cov(int dtype, int cov, const void* x_dev, const void* y_dev, const void* fbar_dev,
+                              const int64_t* starts_dev, int batch, int64_t n, int d, int q, double ell, double sf2,
+                              double noise, const void* shared_bias_dev, void* k_arena_dev, int64_t ldk, int64_t k_stride,
+                              void* kinv_arena_dev, void* ws_arena_dev, size_t ws_stride_bytes, int32_t* info_dev,
+                              void* scratch_dev, double* out_dev, void* stream)
+{
+    return layer_lml_grad_impl("cimrgp_layer_lml_grad_cov", false, dtype, cov, x_dev, y_dev, fbar_dev, starts_dev, batch, n, d, q, ell,
+                               sf2, noise, shared_bias_dev, k_arena_dev, ldk, k_stride, kinv_arena_dev, ws_arena_dev, ws_stride_bytes,
+                               info_dev, scratch_dev, out_dev, stream);
+}
+
+int cimrgp_layer_lml_grad_ard_cov(int dtype, int cov, const void* xs_dev, const void* y_dev, const void* fbar_dev,
+                                  const int64_t* starts_dev, int batch, int64_t n, int d, int q, double sf2, double noise,
+                                  const void* shared_bias_dev, void* k_arena_dev, int64_t ldk, int64_t k_stride,
+                                  void* kinv_arena_dev, void* ws_arena_dev, size_t ws_stride_bytes, int32_t* info_dev,
+                                  void* scratch_dev, double* out_dev, void* stream)
+{
+    return layer_lml_grad_impl("cimrgp_layer_lml_grad_ard_cov", true, dtype, cov, xs_dev, y_dev, fbar_dev, starts_dev, batch, n, d, q,
+                               1.0, sf2, noise, shared_bias_dev, k_arena_dev, ldk, k_stride, kinv_arena_dev, ws_arena_dev,
+                               ws_stride_bytes, info_dev, scratch_dev, out_dev, stream);
 }
 
 int cimrgp_set_rows_queues(int queues)

@@ -393,12 +393,14 @@ template <typename T> int lml_grad_run(const T* x, int64_t n, int d, const T* ki
                                        bool ard = false, int cov = CIMRGP_COV_RBF, const char* fn = nullptr);
 // the gradient of `batch` blocks (K^-1 lower triangles at ks apart, inputs from rows starts[b]) and each block's log
 // marginal likelihood from its factor l (same layout as kinv) and z = L^-1 r (batch x n x q): out[4 b + 0 .. 3];
-// partial: batch x lml_grad_tiles_count(n) x 3 doubles
+// partial: batch x lml_grad_tiles_count(n) x lml_grad_record_width(ard) doubles.  ard: x pre-scaled by the length-scales,
+// unit length-scale (ell is not read), d length-scale entries: out[(d + 3) b + 0 .. d + 2]
 int64_t lml_grad_tiles_count(int64_t n);
+int lml_grad_record_width(bool ard);
 template <typename T> int lml_grad_batched_run(const T* x, const int64_t* starts, int batch, int64_t n, int d, const T* kinv,
                                                int64_t ld, int64_t ks, const T* l, const T* alpha, const T* z, int q, double ell,
                                                double sf2, double noise, double* out, double* partial, hipStream_t st, int cov,
-                                               const char* fn);
+                                               const char* fn, bool ard = false);
 
 // layer.hip: one call per layer for a batch of equal-sized blocks
 // The fit front end (fit_front_run): statistics -> bias, noise | residual rows | Gram + noise | factorisation with the
@@ -432,14 +434,14 @@ template <typename T> struct LayerGrad {
     BatchCov bc; Points<T> tr; Factors<const T> f; Points<T> te;
     const T* alpha = nullptr; int64_t sa = 0; int q = 0; Arena<T> w; T* mg = nullptr; T* vg = nullptr; int accumulate = 0;
 };
-// log marginal likelihood + gradient of a batch of blocks (cimrgp_layer_lml_grad_cov); the scratch holds the carried
+// log marginal likelihood + gradient of a batch of blocks (cimrgp_layer_lml_grad_cov and its ARD twin); the scratch holds the carried
 // rows (q residual rows + the identity, per block), z, alpha, the backward solve's work area, bias, noise and the
 // gradient's tile records, at the byte offsets of lml_scratch_layout: layer_lml_grad_run points fr's rows, z, alpha,
-// work, bias and noise there (fr.noise_fixed is the call's noise)
+// work, bias and noise there (fr.noise_fixed is the call's noise).  np: entries per tile record (lml_grad_record_width)
 struct LmlScratch { int64_t ldr = 0, srows = 0; size_t rows = 0, z = 0, alpha = 0, work = 0, bias = 0, noise = 0, partial = 0, total = 0; };
-LmlScratch lml_scratch_layout(size_t esz, int64_t n, int q, int batch);
+LmlScratch lml_scratch_layout(size_t esz, int64_t n, int q, int batch, int np);
 template <typename T> struct LayerLml { FitFront<T> fr; T* kinv = nullptr; void* scratch = nullptr; double* out = nullptr; };
-template <typename T> int layer_lml_grad_run(const LayerLml<T>& a, hipStream_t st);
+template <typename T> int layer_lml_grad_run(const LayerLml<T>& a, hipStream_t st, bool ard);
 
 // reduced.hip
 template <typename T> int laplace_basis_run(const T* x, int64_t n, int d, const double* interval, int m, T* phi, hipStream_t st);

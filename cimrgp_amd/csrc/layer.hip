@@ -211,7 +211,7 @@ int layer_predict_run(const LayerPredict<T>& a, hipStream_t st)
                                  st, a.bc.batch, a.te.starts, a.w.stride);
 }
 
-// ---- log marginal likelihood and its gradient for a batch of blocks (cimrgp_layer_lml_grad_cov) ----
+// ---- log marginal likelihood and its gradient for a batch of blocks (cimrgp_layer_lml_grad_cov, ..._ard_cov) ----
 //   statistics -> bias | residual rows r^T and the identity as q + n carried rows | Gram + noise | factorisation with
 //   the rows carried: z^T = r^T L^-T and U = L^-T come out of the same panel sweep | backward solve (alpha) |
 //   lower(K^-1) = U U^T (batched SYRK on the matrix cores) | gradient tiles + per-block finish (misc.hip)
@@ -240,7 +240,7 @@ __global__ void k_layer_neg_lower(T* __restrict__ k, int64_t ld, int64_t ks, int
     if (j <= i) k[b * ks + i * ld + j] = -k[b * ks + i * ld + j];
 }
 
-LmlScratch lml_scratch_layout(size_t esz, int64_t n, int q, int batch)
+LmlScratch lml_scratch_layout(size_t esz, int64_t n, int q, int batch, int np)
 {
     LmlScratch s;
     s.ldr = padded_ld(n);                    // device.padded_ld's rule
@@ -254,21 +254,21 @@ LmlScratch lml_scratch_layout(size_t esz, int64_t n, int q, int batch)
     s.work = off;    off += seg(nb * (size_t)(2 * n * q) * esz);
     s.bias = off;    off += seg(nb * (size_t)q * esz);
     s.noise = off;   off += seg(nb * esz);
-    s.partial = off; off += seg(nb * (size_t)lml_grad_tiles_count(n) * 3 * sizeof(double));
+    s.partial = off; off += seg(nb * (size_t)lml_grad_tiles_count(n) * (size_t)np * sizeof(double));
     s.total = off;
     return s;
 }
 
 template <typename T>
-int layer_lml_grad_run(const LayerLml<T>& a, hipStream_t st)
+int layer_lml_grad_run(const LayerLml<T>& a, hipStream_t st, bool ard)
 {
-    const char* fn = "cimrgp_layer_lml_grad_cov";
+    const char* fn = ard ? "cimrgp_layer_lml_grad_ard_cov" : "cimrgp_layer_lml_grad_cov";
     FitFront<T> fr = a.fr;
     const int64_t n = fr.tr.n;
     CIMRGP_REQUIRE(fr.bc.batch >= 1 && fr.bc.batch < 65536, fn, "batch count out of range");
     CIMRGP_REQUIRE(n > 0 && n < (1ll << 30), fn, "bad dimensions");
     CIMRGP_REQUIRE(fr.q >= 1 && fr.q <= MAXQ, fn, "number of outputs must be in [1, 8]");
-    const LmlScratch sl = lml_scratch_layout(sizeof(T), n, fr.q, fr.bc.batch);
+    const LmlScratch sl = lml_scratch_layout(sizeof(T), n, fr.q, fr.bc.batch, lml_grad_record_width(ard));
     char* base = (char*)a.scratch;
     fr.rows = Arena<T>{(T*)(base + sl.rows), sl.ldr, sl.srows};
     fr.eye = true;
@@ -291,7 +291,7 @@ int layer_lml_grad_run(const LayerLml<T>& a, hipStream_t st)
     CIMRGP_LAUNCH_CHECK(fn);
     return lml_grad_batched_run<T>(fr.tr.x, fr.tr.starts, fr.bc.batch, n, fr.bc.d, (const T*)a.kinv, k.ld, k.stride, (const T*)k.p,
                                    (const T*)fr.alpha, (const T*)fr.z, fr.q, fr.bc.ell, fr.bc.sf2, fr.noise_fixed, a.out, partial, st,
-                                   fr.bc.cov, fn);
+                                   fr.bc.cov, fn, ard);
 }
 
 // The targets of ONE block as carried rows and back (cimrgp_block_posterior).
@@ -336,7 +336,7 @@ template int cross_solve_run<float>(const BatchCov&, const Points<float>&, const
                                     const Arena<float>&, hipStream_t);
 template int layer_predict_run<double>(const LayerPredict<double>&, hipStream_t);
 template int layer_predict_run<float>(const LayerPredict<float>&, hipStream_t);
-template int layer_lml_grad_run<double>(const LayerLml<double>&, hipStream_t);
-template int layer_lml_grad_run<float>(const LayerLml<float>&, hipStream_t);
+template int layer_lml_grad_run<double>(const LayerLml<double>&, hipStream_t, bool);
+template int layer_lml_grad_run<float>(const LayerLml<float>&, hipStream_t, bool);
 
 }  // namespace cimrgp

@@ -373,23 +373,32 @@ template int lml_grad_run<float>(const float*, int64_t, int, const float*, int64
 // tile records (k_lml_grad_final's order), the data fit sum_c z_c^T z_c = sum_c r_c^T K^-1 r_c from z = L^-1 r, and
 // sum_i log L_ii from the factor's diagonal:
 //   out[4b + 0] = -1/2 fit - q sum log L_ii - 1/2 n q log 2 pi,  out[4b + 1 .. 3] = the gradient.
+// ARD (cimrgp_layer_lml_grad_ard_cov): tile records of LG_NP entries and nout = d + 2 gradient entries, the record of
+// block b at out[(d + 3) b]: [LML | sf | l_1 .. l_d | noise].  One body for both; per component the sums run in the
+// same order whatever the record width.
 namespace {
 
-template <typename T>
-__global__ __launch_bounds__(1024)
-void k_layer_lml_final(const double* __restrict__ partial, int64_t ntiles, double noise, const T* __restrict__ l, int64_t ld,
-                       int64_t ls, const T* __restrict__ z, int64_t n, int q, double* __restrict__ out)
+// NP entries per tile record, the last one the trace term; nout <= NP gradient entries, the last one the noise's
+template <typename T, int NP>
+__device__ __forceinline__
+void layer_lml_final(const double* __restrict__ partial, int64_t ntiles, double noise, const T* __restrict__ l, int64_t ld,
+                     int64_t ls, const T* __restrict__ z, int64_t n, int q, double* __restrict__ out, int nout)
 {
     __shared__ double red[16];
     const int64_t b = blockIdx.x;
-    partial += b * ntiles * 3;
+    partial += b * ntiles * NP;
     l += b * ls;
     z += b * n * q;
-    double g[3];
-    for (int c = 0; c < 3; ++c) {
-        double s = 0.0;
-        for (int64_t t = threadIdx.x; t < ntiles; t += blockDim.x) s += partial[t * 3 + c];
-        g[c] = block_sum_1024(s, red);
+    double g[NP];
+#pragma unroll
+    for (int c = 0; c < NP; ++c) {
+        g[c] = 0.0;
+        if (c < nout) {
+            const int src = (c == nout - 1) ? NP - 1 : c;
+            double s = 0.0;
+            for (int64_t t = threadIdx.x; t < ntiles; t += blockDim.x) s += partial[t * NP + src];
+            g[c] = block_sum_1024(s, red);
+        }
     }
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += blockDim.x) s += log((double)l[i * ld + i]);
@@ -398,14 +407,32 @@ void k_layer_lml_final(const double* __restrict__ partial, int64_t ntiles, doubl
     for (int64_t e = threadIdx.x; e < n * q; e += blockDim.x) s += (double)z[e] * (double)z[e];
     const double fit = block_sum_1024(s, red);
     if (threadIdx.x == 0) {
-        out[4 * b + 0] = -0.5 * fit - (double)q * half_logdet - 0.5 * (double)(n * q) * log(2.0 * M_PI);
-        out[4 * b + 1] = 0.5 * g[0];
-        out[4 * b + 2] = 0.5 * g[1];
-        out[4 * b + 3] = 0.5 * g[2] * noise;
+        out[(nout + 1) * b + 0] = -0.5 * fit - (double)q * half_logdet - 0.5 * (double)(n * q) * log(2.0 * M_PI);
+#pragma unroll
+        for (int c = 0; c < NP; ++c)
+            if (c < nout) out[(nout + 1) * b + 1 + c] = 0.5 * g[c] * (c == nout - 1 ? noise : 1.0);
     }
 }
 
+template <typename T>
+__global__ __launch_bounds__(1024)
+void k_layer_lml_final(const double* __restrict__ partial, int64_t ntiles, double noise, const T* __restrict__ l, int64_t ld,
+                       int64_t ls, const T* __restrict__ z, int64_t n, int q, double* __restrict__ out)
+{
+    layer_lml_final<T, 3>(partial, ntiles, noise, l, ld, ls, z, n, q, out, 3);
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024)
+void k_layer_lml_final_ard(const double* __restrict__ partial, int64_t ntiles, double noise, const T* __restrict__ l, int64_t ld,
+                           int64_t ls, const T* __restrict__ z, int64_t n, int q, double* __restrict__ out, int nout)
+{
+    layer_lml_final<T, LG_NP>(partial, ntiles, noise, l, ld, ls, z, n, q, out, nout);
+}
+
 }  // namespace
+
+int lml_grad_record_width(bool ard) { return ard ? LG_NP : 3; }
 
 int64_t lml_grad_tiles_count(int64_t n)
 {
@@ -416,7 +443,7 @@ int64_t lml_grad_tiles_count(int64_t n)
 template <typename T>
 int lml_grad_batched_run(const T* x, const int64_t* starts, int batch, int64_t n, int d, const T* kinv, int64_t ld, int64_t ks,
                          const T* l, const T* alpha, const T* z, int q, double ell, double sf2, double noise, double* out,
-                         double* partial, hipStream_t st, int cov, const char* fn)
+                         double* partial, hipStream_t st, int cov, const char* fn, bool ard)
 {
     CIMRGP_REQUIRE(n > 0 && n < (1ll << 30), fn, "bad size");
     CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
@@ -427,23 +454,31 @@ int lml_grad_batched_run(const T* x, const int64_t* starts, int batch, int64_t n
     const LgBatch bb{starts, ks};
     const int rc = with_cov(cov, [&](auto c) {
         constexpr int COV = decltype(c)::value;
-        hipLaunchKernelGGL((k_lml_grad_tiles<T, COV, false, true>), dim3((unsigned)tiles, (unsigned)batch), dim3(256), 0, st, x, (int)n,
-                           d, kinv, ld, alpha, q, (T)cov_scale(COV, ell), (T)sf2, (T)(1.0 / (ell * ell)), partial, bb);
+        if (ard)      // inputs pre-scaled by the length-scales: unit length-scale here, as in lml_grad_run_cov
+            hipLaunchKernelGGL((k_lml_grad_tiles<T, COV, true, true>), dim3((unsigned)tiles, (unsigned)batch), dim3(256), 0, st, x,
+                               (int)n, d, kinv, ld, alpha, q, (T)cov_scale(COV, 1.0), (T)sf2, (T)1, partial, bb);
+        else
+            hipLaunchKernelGGL((k_lml_grad_tiles<T, COV, false, true>), dim3((unsigned)tiles, (unsigned)batch), dim3(256), 0, st, x,
+                               (int)n, d, kinv, ld, alpha, q, (T)cov_scale(COV, ell), (T)sf2, (T)(1.0 / (ell * ell)), partial, bb);
         CIMRGP_LAUNCH_CHECK(fn);
         return 0;
     });
     if (rc) return rc;
-    hipLaunchKernelGGL((k_layer_lml_final<T>), dim3((unsigned)batch), dim3(1024), 0, st, (const double*)partial, tiles, noise, l, ld, ks,
-                       z, n, q, out);
+    if (ard)
+        hipLaunchKernelGGL((k_layer_lml_final_ard<T>), dim3((unsigned)batch), dim3(1024), 0, st, (const double*)partial, tiles, noise, l,
+                           ld, ks, z, n, q, out, d + 2);
+    else
+        hipLaunchKernelGGL((k_layer_lml_final<T>), dim3((unsigned)batch), dim3(1024), 0, st, (const double*)partial, tiles, noise, l, ld,
+                           ks, z, n, q, out);
     CIMRGP_LAUNCH_CHECK(fn);
     return 0;
 }
 
 template int lml_grad_batched_run<double>(const double*, const int64_t*, int, int64_t, int, const double*, int64_t, int64_t,
                                           const double*, const double*, const double*, int, double, double, double, double*,
-                                          double*, hipStream_t, int, const char*);
+                                          double*, hipStream_t, int, const char*, bool);
 template int lml_grad_batched_run<float>(const float*, const int64_t*, int, int64_t, int, const float*, int64_t, int64_t,
                                          const float*, const float*, const float*, int, double, double, double, double*,
-                                         double*, hipStream_t, int, const char*);
+                                         double*, hipStream_t, int, const char*, bool);
 
 }  // namespace cimrgp

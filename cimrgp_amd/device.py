@@ -610,6 +610,28 @@ def layer_lml_grad(x, y, fbar, starts, n, ell, sf2, noise, shared_bias, karena, 
     return out
 
 
+def layer_lml_ard_scratch_bytes(n, q, batch, dtype):
+    return int(_lib.load().cimrgp_layer_lml_grad_ard_scratch_bytes(_DT[dtype], int(n), int(q), int(batch)))
+
+
+def layer_lml_grad_ard(xs, y, fbar, starts, n, sf2, noise, shared_bias, karena, kinv_arena, ws_arena, info, out, cov=_lib.COV_RBF):
+    """:func:`layer_lml_grad` with one length-scale per input dimension (cimrgp_layer_lml_grad_ard_cov,
+    include/cimrgp_layer_ard.h): ``xs`` holds the inputs already divided by their length-scales and the covariance runs at
+    unit length-scale.  out (batch, d + 3) float64 = [LML | d/dlog sf | d/dlog l_1 .. l_d | d/dlog noise] per block
+    (undefined where info != 0)."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
+    lib = _lib.load()
+    batch = int(karena.shape[0])
+    q = int(y.shape[1])
+    scratch = torch.empty(max(layer_lml_ard_scratch_bytes(n, q, batch, y.dtype), 16), dtype=torch.uint8, device=y.device)
+    _lib.check(lib.cimrgp_layer_lml_grad_ard_cov(_DT[y.dtype], cov, _p(xs), _p(y), _p(fbar), _p(starts), batch, int(n),
+                                                 int(xs.shape[1]), q, float(sf2), float(noise), _p(shared_bias), _p(karena),
+                                                 karena.stride(1), karena.stride(0), _p(kinv_arena), _p(ws_arena),
+                                                 ws_arena.stride(0), _p(info), _p(scratch), _p(out), _stream()),
+               "cimrgp_layer_lml_grad_ard_cov")
+    return out
+
+
 def solve_lt(lbuf, n, ws, z):
     """Backward half of D3: z (n x q) = L^-1 R is overwritten with alpha = L^-T z."""
     lib = _lib.load()

@@ -490,4 +490,8 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
  * input dimension: include/cimrgp_sparse_ard.h. */
 #include "cimrgp_sparse_ard.h"
 
+/* The hyper-parameter objective of a layer's blocks with one length-scale per input dimension (ARD):
+ * include/cimrgp_layer_ard.h. */
+#include "cimrgp_layer_ard.h"
+
 #endif /* CIMRGP_H */
