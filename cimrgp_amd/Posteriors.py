@@ -385,31 +385,40 @@ def joint_run(call, kernel, xs, layer, add_noise, cov_out=None, samples=None, se
     nb, ns, n = len(regions), call.ns, call.batch.n
     if ns <= 0 or nb == 0:
         return 0.0
-
-    def joint_cov(c, diag, *factor_out):
-        dev.layer_joint_cov(c.x, c.batch.starts, n, xs, c.t_starts, ns, kernel.l, sf2, c.batch.karena, c.batch.ws_arena, diag,
-                            *factor_out, cov=kernel.cov)
-
-    dtype, device = xs.dtype, xs.device
     sf2 = float(kernel.sf)
+    extra = call.batch.noise.to(xs.dtype) if add_noise else torch.zeros(nb, dtype=xs.dtype, device=xs.device)
+
+    def joint_cov(i, rel, *out):
+        c, ex = (call, extra) if i is None else (call.part(i), extra[i:i + 1])
+        dev.layer_joint_cov(c.x, c.batch.starts, n, xs, c.t_starts, ns, kernel.l, sf2, c.batch.karena, c.batch.ws_arena,
+                            ex if rel is None else ex + rel * sf2, *out, cov=kernel.cov)
+
+    return joint_blocks(joint_cov, regions, ns, call.t_starts, xs.dtype, xs.device, layer, cov_out, samples, seed, jitter)
+
+
+def joint_blocks(joint_cov, regions, ns, t_starts, dtype, device, layer, cov_out=None, samples=None, seed=0, jitter=1e-6):
+    """What :func:`joint_run` does with the covariance blocks, whoever builds them (the exact blocks of a layer, or a
+    sparse block: ``Sparse.SparseBlock.joint``).  ``joint_cov(i, rel, carena[, cws, info])`` fills the blocks of the call
+    (``i`` None; carena (nb, ns, ldc)) or block ``i`` alone (the arenas' slices [i:i + 1]) with rel sf2 (+ noise) on the
+    diagonal (``rel`` None: nothing but the noise) and, given ``cws`` and ``info``, factors them.  Block b serves the test
+    rows from ``t_starts[b]`` (device int64)."""
+    nb = len(regions)
     ldc = dev.joint_ld(ns, dtype)
     carena = torch.empty((nb, ns, ldc), dtype=dtype, device=device)
-    extra = call.batch.noise.to(dtype) if add_noise else torch.zeros(nb, dtype=dtype, device=device)
     if samples is None:
-        joint_cov(call, extra, carena)
-        for i, a in enumerate(call.t_starts.cpu().tolist()):
+        joint_cov(None, None, carena)
+        for i, a in enumerate(t_starts.cpu().tolist()):
             cov_out[a:a + ns, a:a + ns] += torch.tril(carena[i, :, :ns])
         return 0.0
     cws = torch.empty((nb, _ws_bytes(ns, dtype)), dtype=torch.uint8, device=device)
     info = torch.zeros(nb, dtype=torch.int32, device=device)
-    diag = extra + jitter * sf2
-    joint_cov(call, diag, carena, cws, info)
+    joint_cov(None, jitter, carena, cws, info)
     used = float(jitter)
     for i in np.flatnonzero(info.cpu().numpy() != 0):          # info read once per call
-        one, rel = call.part(int(i)), max(float(jitter), JOINT_JITTER_FLOOR)
+        i, rel = int(i), max(float(jitter), JOINT_JITTER_FLOOR)
         for _ in range(JOINT_RETRIES):
             rel *= 10.0
-            joint_cov(one, extra[i:i + 1] + rel * sf2, carena[i:i + 1], cws[i:i + 1], info[i:i + 1])
+            joint_cov(i, rel, carena[i:i + 1], cws[i:i + 1], info[i:i + 1])
             code = int(info[i].item())
             if code == 0:
                 break
@@ -424,12 +433,12 @@ def joint_run(call, kernel, xs, layer, add_noise, cov_out=None, samples=None, se
     keys = torch.tensor([(int(layer) << 32) + int(l) for l in regions], dtype=torch.int64).to(device)
     cols = int(samples.shape[0])
     ldz = dev.joint_ld(ns, dtype)
-    chunk = int(max(1, min(cols, JOINT_Z_BYTES // (nb * ldz * xs.element_size()))))
+    chunk = int(max(1, min(cols, JOINT_Z_BYTES // (nb * ldz * carena.element_size()))))
     z = torch.empty((nb, chunk, ldz), dtype=dtype, device=device)
     for c0 in range(0, cols, chunk):
         cc = min(chunk, cols - c0)
         dev.normal_fill(seed, keys, c0, cc, ns, z)
-        dev.layer_sample(carena, ns, z, cc, call.t_starts, samples[c0:c0 + cc])
+        dev.layer_sample(carena, ns, z, cc, t_starts, samples[c0:c0 + cc])
     return used
 
 

@@ -533,6 +533,95 @@ class SparseGP(RegressionMethod):
             mean = self._reverse_trans_labels(mean)
         return mean, var
 
+    def _fitted_block(self, what):
+        if self.block is None:
+            raise RuntimeError('call fit() before %s()' % what)
+        return self.block
+
+    def _test_inputs(self, test_data):
+        return dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, self.block.x.device)
+
+    def predictive_gradients(self, test_data, budget_bytes=None):
+        """``GP_RBF.predictive_gradients`` for the sparse posterior: ``(dmu_dX (N*, d, q), dvar_dX (N*, d))`` with respect
+        to the original test inputs.  The mean gradient is in the original label units, the variance gradient in z-scored
+        label units, as ``predict_with_variance`` leaves the variance (:meth:`~cimrgp_amd.Sparse.SparseBlock.predict_grad`;
+        ARD's 1 / lengthscale is applied by the block)."""
+        blk = self._fitted_block('predictive_gradients')
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        xs = self._test_inputs(test_data)
+        ns, d = int(xs.shape[0]), int(xs.shape[1])
+        mean_grad = torch.empty((ns, d, int(blk.gamma.shape[1])), dtype=self.dtype, device=xs.device)
+        var_grad = torch.empty((ns, d), dtype=self.dtype, device=xs.device)
+        blk.predict_grad(xs, mean_grad, var_grad, budget_bytes=budget_bytes)
+        dmu, dvar = mean_grad.double().cpu().numpy(), var_grad.double().cpu().numpy()
+        if self.preprocess:
+            inv_std = 1.0 / np.asarray(self.data_std, dtype=np.float64)
+            dmu = dmu * inv_std[None, :, None] * np.asarray(self.labels_std, dtype=np.float64)[None, None, :]
+            dvar = dvar * inv_std[None, :]
+        return dmu, dvar
+
+    def _loo_z(self, budget_bytes=None):
+        """(labels, LOO mean, LOO variance) in the (z-scored) units of the fit, NumPy."""
+        blk = self._fitted_block('leave_one_out')
+        y = self._y
+        mean = torch.empty_like(y)
+        var = torch.empty(y.shape[0], dtype=self.dtype, device=y.device)
+        blk.loo(y, mean, var, budget_bytes=budget_bytes)
+        return y.double().cpu().numpy(), mean.double().cpu().numpy(), var.double().cpu().numpy()
+
+    def leave_one_out(self, budget_bytes=None):
+        """Closed-form leave-one-out prediction of every training label from the other n - 1 under the fitted sparse
+        model (exact for FITC's covariance Q_ff + Lambda; VFE / DTC: the same formula with Lambda = noise I):
+        ``(mean (n, q), var (n,))``, at the cost of one prediction pass over the training set.  The mean is in the original
+        label units; the variance is left in z-scored label units and includes the noise, as ``GP_RBF.leave_one_out``'s."""
+        _, mean, var = self._loo_z(budget_bytes)
+        if self.preprocess:
+            mean = self._reverse_trans_labels(mean)
+        return mean, var
+
+    def loo_log_predictive_density(self, budget_bytes=None):
+        """(n,) log densities of each training label under its leave-one-out predictive Gaussian, in z-scored label
+        units, summed over the outputs; their sum scores the fit -- and the choice of m -- without a held-out set."""
+        y, mean, var = self._loo_z(budget_bytes)
+        q = y.shape[1]
+        return -0.5 * q * np.log(2 * np.pi * var) - 0.5 * ((y - mean) ** 2).sum(axis=1) / var
+
+    def predict_with_covariance(self, test_data):
+        """Mean (un-z-scored) and the latent joint predictive covariance (N* x N*, z-scored label units like
+        ``predict_with_variance``'s variance, which is its diagonal)."""
+        blk = self._fitted_block('predict_with_covariance')
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        mean, _ = self._predict_mean_var(test_data, want_var=False)
+        xs = self._test_inputs(test_data)
+        ns = int(xs.shape[0])
+        cov = torch.zeros((ns, ns), dtype=self.dtype, device=xs.device)
+        blk.joint(xs, cov_out=cov)
+        cov = torch.tril(cov) + torch.tril(cov, -1).t()
+        if self.preprocess:
+            mean = self._reverse_trans_labels(mean)
+        return mean, cov.double().cpu().numpy()
+
+    def posterior_samples_f(self, test_data, size=1, seed=0):
+        """``size`` draws (size, N*, q) of the latent function in the original label units: the z-scored draw
+        mean + chol(Sigma + 1e-6 sf2 I) Z (Z_c = phi(seed, 0, c, .), c = sample * q + output; include/cimrgp_joint.h)
+        times labels_std, plus labels_mean, per output -- ``GP_RBF.posterior_samples_f``'s convention."""
+        blk = self._fitted_block('posterior_samples_f')
+        if int(size) < 1:
+            raise ValueError('size must be at least 1')
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        mean, _ = self._predict_mean_var(test_data, want_var=False)
+        ns, q = mean.shape
+        xs = self._test_inputs(test_data)
+        out = torch.zeros((int(size) * q, ns), dtype=self.dtype, device=xs.device)
+        blk.joint(xs, samples=out, seed=int(seed))
+        f = mean[None, :, :] + out.double().cpu().numpy().reshape(int(size), q, ns).transpose(0, 2, 1)
+        if self.preprocess:
+            f = f * self.labels_std + self.labels_mean
+        return f
+
 
 class SGP_FITC(SparseGP):
     """The reference's ``SGP_FITC`` plugin: :class:`SparseGP` with ``approximation='fitc'``."""

@@ -20,13 +20,15 @@ from device scalars (cimrgp_sparse_lambda_dev, cimrgp_sparse_tail_dev) and read 
 ``SparseBlock(..., lengthscales=)`` gives every input dimension its own length-scale (ARD; DESIGN.md, "ARD length-scales for
 the sparse GP"): the block works on x / l and z / l with a unit length-scale, and ``lml_grad`` takes the d derivatives w.r.t.
 log l_e from cimrgp_cov_pair_grad_ard.
+After a fit the block also answers ``predict_grad``, ``loo`` and ``joint`` ("Posterior queries of the sparse GP":
+cimrgp_cov_cross_grad, cimrgp_sparse_tail_grad, cimrgp_sparse_loo, cimrgp_sparse_joint_cov); a model layer's block does not.
 """
 import numpy as np
 import torch
 
 from . import device as dev
 from .Hyper import scaled, sum_block_objectives, unit_lengthscale
-from .Posteriors import DensePosterior, NOISE_FRACTION, NOISE_FLOOR, _Fanout, block_targets
+from .Posteriors import DensePosterior, NOISE_FRACTION, NOISE_FLOOR, _Fanout, block_targets, joint_blocks
 
 APPROXIMATIONS = {'fitc': 0, 'vfe': 1, 'dtc': 1}
 
@@ -69,6 +71,7 @@ class SparseBlock(object):
             self._zs = scaled(self.z, self._scale)
         self.n, self.m = int(x.shape[0]), int(z.shape[0])
         self.kernel = kernel
+        self.device_noise = bool(device_noise)
         self.approximation = 'fitc' if key == 'fitc' else 'vfe'
         self.mode = APPROXIMATIONS[key]
         self.jitter = float(jitter)
@@ -270,6 +273,97 @@ class SparseBlock(object):
             wstar[:rows].copy_(astar[:rows])
             dev.trsm_rows(self.lb, m, self.ws_b, wstar, rows)
             yield s0, s1, astar, wstar
+
+    def _ready_for(self, what):
+        """The posterior queries below are the plugins': a model layer's block (``device_noise=True``) is refused."""
+        if self.device_noise:
+            raise TypeError('%s() of a sparse layer of the model (device_noise=True) is not yet supported' % what)
+        if self.gamma is None:
+            raise RuntimeError('call fit() before %s()' % what)
+
+    def grad_chunk_rows(self, budget_bytes=None):
+        """Test rows per pass of ``predict_grad``: the d + 1 slabs of A* and of W* within ``budget_bytes``, a multiple of 256."""
+        budget = PREDICT_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
+        per_row = 2 * (int(self.z.shape[1]) + 1) * dev.padded_ld(self.m) * self.z.element_size()
+        return max(256, budget // per_row // 256 * 256)
+
+    def predict_grad(self, xs, mean_grad=None, var_grad=None, budget_bytes=None):
+        """Gradients of :meth:`predict`'s mean and variance w.r.t. the test inputs ("Posterior queries of the
+        sparse GP"): ``mean_grad`` (ns, d, q) and ``var_grad`` (ns, d), either may be None, at ``xs`` (ns x d, device, the
+        caller's units -- with ``lengthscales`` the chain rule through x / l is applied).  K(X*, Z) and its d derivative
+        slabs go through the SAME two row solves as :meth:`predict`, stacked as one (d + 1) rows x m operand; chunks of
+        ``grad_chunk_rows(budget_bytes)`` test rows, a row's result does not depend on the chunking."""
+        self._ready_for('predict_grad')
+        k, m = self.kernel, self.m
+        ns, d = int(xs.shape[0]), int(xs.shape[1])
+        step = self.grad_chunk_rows(budget_bytes)
+        ld = dev.padded_ld(m)
+        cap = min(step, max(ns, 1))
+        abuf = torch.empty((d + 1) * cap * ld, dtype=xs.dtype, device=xs.device)
+        wbuf = torch.empty_like(abuf)
+        for s0 in range(0, ns, step):
+            s1 = min(ns, s0 + step)
+            rows = s1 - s0
+            a = abuf[:(d + 1) * rows * ld].view(d + 1, rows, ld)         # the slabs lie back to back: one operand of
+            w = wbuf[:(d + 1) * rows * ld].view(d + 1, rows, ld)         # (d + 1) rows x m for the row solves
+            xc = xs[s0:s1] if self._scale is None else scaled(xs[s0:s1], self._scale)
+            dev.cov_cross_grad(xc.contiguous(), self._zs, k.l, k.sf, a, cov=k.cov)
+            dev.trsm_rows(self.lu, m, self.ws_u, a.view(-1, ld), (d + 1) * rows)
+            w.copy_(a)
+            dev.trsm_rows(self.lb, m, self.ws_b, w.view(-1, ld), (d + 1) * rows)
+            dev.sparse_tail_grad(a if var_grad is not None else None, w, rows, m, self.gamma if mean_grad is not None else None,
+                                 None if mean_grad is None else mean_grad[s0:s1], None if var_grad is None else var_grad[s0:s1])
+        if self._scale is not None:                      # d / dx_e = (d / d(x_e / l_e)) / l_e
+            if mean_grad is not None:
+                mean_grad.mul_(self._scale[None, :, None])
+            if var_grad is not None:
+                var_grad.mul_(self._scale[None, :])
+        return mean_grad, var_grad
+
+    def loo(self, r, mean=None, var=None, budget_bytes=None):
+        """Leave-one-out prediction of the fit's own targets ``r`` (n x q, device): ``mean`` (n x q) and ``var`` (n,),
+        either may be None.  Exact for FITC's covariance A A^T + Lambda (for VFE / DTC the same formula with Lambda =
+        noise I): loo_mean_i = r_i - (r_i - mu_i) / (1 - h_i), loo_var_i = lambda_i / (1 - h_i), the variance of an
+        observation, with the leverage h_i = w_i |V_i|^2.  A and V = A L_B^-T are recomputed in the chunks of
+        :meth:`predict` over the training inputs; a row's result does not depend on the chunking.  One host read at the
+        end: a row with 1 - h_i <= 0 raises LinAlgError."""
+        self._ready_for('loo')
+        k = self.kernel
+        r = r.contiguous()
+        bad = torch.zeros(1, dtype=torch.int32, device=r.device)
+        for s0, s1, a, v in self._star_chunks(self.x, budget_bytes):
+            dev.sparse_loo(a, v, s1 - s0, self.m, self.gamma, r[s0:s1], k.sf, k.noise, self.mode, bad,
+                           None if mean is None else mean[s0:s1], None if var is None else var[s0:s1])
+        count = int(bad.item())
+        if count > 0:
+            raise np.linalg.LinAlgError("sparse GP leave-one-out: 1 - h_i is not positive for %d of the rows" % count)
+        return mean, var
+
+    def joint(self, xs, cov_out=None, samples=None, seed=0, include_noise=False, jitter=1e-6):
+        """The joint predictive distribution at ``xs`` (ns x d, device): Sigma = K(X*, X*) - A* A*^T + W* W*^T, whose
+        diagonal is :meth:`predict`'s variance.  ``cov_out`` (ns x ns): Sigma (+ noise I with ``include_noise``) is added
+        to its lower triangle.  ``samples`` (cols x ns): chol(Sigma + jitter sf I) Z is added, Z_c = phi(seed, 0, c, .)
+        (cimrgp_normal_fill), with the escalation rule of the exact blocks (``Posteriors.joint_blocks``, the same code).
+        The ns x ns matrix and the rows A*, W* are held whole.  Returns the largest relative jitter used."""
+        self._ready_for('joint')
+        k, m = self.kernel, self.m
+        ns = int(xs.shape[0])
+        if ns == 0:
+            return 0.0
+        xc = (xs if self._scale is None else scaled(xs, self._scale)).contiguous()
+        astar = torch.empty((ns, dev.joint_ld(m, xs.dtype)), dtype=xs.dtype, device=xs.device)
+        dev.rbf_cross(xc, self._zs, k.l, k.sf, out=astar, cov=k.cov)
+        dev.trsm_rows(self.lu, m, self.ws_u, astar, ns)
+        wstar = astar.clone()
+        dev.trsm_rows(self.lb, m, self.ws_b, wstar, ns)
+        extra = k.noise if include_noise else 0.0
+
+        def joint_cov(i, rel, carena, cws=None, info=None):
+            dev.sparse_joint_cov(xc, k.l, k.sf, extra + (0.0 if rel is None else rel * k.sf), astar, wstar, m, carena[0],
+                                 None if cws is None else cws[0], info, cov=k.cov)
+
+        t_starts = torch.zeros(1, dtype=torch.int64, device=xs.device)
+        return joint_blocks(joint_cov, [0], ns, t_starts, xs.dtype, xs.device, 0, cov_out, samples, seed, jitter)
 
     def predict_layer(self, xs, mean, var=None, add_noise=False, budget_bytes=None):
         """A model layer's block (:meth:`fit_layer`): ``mean`` (ns x q) += W* gamma + bias and, with ``var`` (ns,),

@@ -152,6 +152,15 @@ LAYER_ARD_SIGNATURES = {
                                              _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/cimrgp_sparse_post.h (posterior queries of the sparse GP)
+SPARSE_POST_SIGNATURES = {
+    "cimrgp_cov_cross_grad": (_i32, [_i32, _i32, _vp, _i64, _vp, _i64, _i32, _dbl, _dbl, _vp, _i64, _i64, _vp]),
+    "cimrgp_sparse_tail_grad": (_i32, [_i32, _vp, _vp, _i64, _i64, _i32, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "cimrgp_sparse_loo": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp]),
+    "cimrgp_sparse_joint_cov": (_i32, [_i32, _i32, _vp, _i64, _i32, _dbl, _dbl, _dbl, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _sz, _vp,
+                                       _vp]),
+}
+
 _lib = None
 
 
@@ -174,7 +183,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + \
             list(JOINT_SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(LOO_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items()) + \
             list(SPARSE_GRAD_SIGNATURES.items()) + list(SPARSE_LAYER_SIGNATURES.items()) + list(SPARSE_ARD_SIGNATURES.items()) + \
-            list(LAYER_ARD_SIGNATURES.items()):
+            list(LAYER_ARD_SIGNATURES.items()) + list(SPARSE_POST_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if a symbol is missing
         fn.restype = res
         fn.argtypes = args

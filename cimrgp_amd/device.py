@@ -587,6 +587,59 @@ def sparse_grad_combine(abuf, ybuf, n, m, beta, b, w, t):
     return ybuf
 
 
+def cov_cross_grad(xa, xb, ell, sf2, out, cov=_lib.COV_RBF):
+    """The d + 1 slabs [K(xa, xb); dK / d xa_0; ..; dK / d xa_{d-1}] into ``out`` (d + 1, >= na, ldo) from one pass over
+    the pairs (cimrgp_cov_cross_grad, include/cimrgp_sparse_post.h); slab 0 is :func:`rbf_cross`'s output bit for bit."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
+    lib = _lib.load()
+    na, d = xa.shape
+    if out.dim() != 3 or int(out.shape[0]) != int(d) + 1 or int(out.shape[1]) < int(na) or out.stride(2) != 1:
+        raise ValueError("out must be (d + 1, >= na, ldo) with unit column stride")
+    _lib.check(lib.cimrgp_cov_cross_grad(_DT[xa.dtype], cov, _p(xa), int(na), _p(xb), int(xb.shape[0]), int(d), float(ell),
+                                         float(sf2), _p(out), out.stride(1), out.stride(0), _stream()), "cimrgp_cov_cross_grad")
+    return out
+
+
+def sparse_tail_grad(aslabs, wslabs, ns, m, gamma, mean_grad=None, var_grad=None, accumulate=False):
+    """mean_grad (ns, d, q) (+)= dW_e gamma and var_grad (ns, d) (+)= 2 sum_j (W* dW_e - A* dA_e) from the solved slabs
+    ``aslabs`` / ``wslabs`` (d + 1, >= ns, ld), which share their layout (cimrgp_sparse_tail_grad); either output, and
+    ``aslabs`` without ``var_grad``, may be None."""
+    lib = _lib.load()
+    if aslabs is not None and (aslabs.stride(0) != wslabs.stride(0) or aslabs.stride(1) != wslabs.stride(1)):
+        raise ValueError("aslabs and wslabs must have the same row pitch and slab stride")
+    q = 0 if gamma is None else int(gamma.shape[1])
+    _lib.check(lib.cimrgp_sparse_tail_grad(_DT[wslabs.dtype], _p(aslabs), _p(wslabs), int(ns), int(m), int(wslabs.shape[0]) - 1,
+                                           wslabs.stride(1), wslabs.stride(0), _p(gamma), q, _p(mean_grad), _p(var_grad),
+                                           int(bool(accumulate)), _stream()), "cimrgp_sparse_tail_grad")
+
+
+def sparse_loo(abuf, vbuf, n, m, gamma, r, sf2, noise, mode, bad, mean_out=None, var_out=None):
+    """Leave-one-out mean (n x q) and variance (n,) of the rows of a sparse fit from A = abuf[:n, :m] and V = vbuf[:n, :m]
+    (cimrgp_sparse_loo); ``bad`` (device int32[1]) counts the rows with 1 - h_i <= 0 and is never reset here."""
+    lib = _lib.load()
+    if abuf.stride(0) != vbuf.stride(0):
+        raise ValueError("abuf and vbuf must have the same row pitch")
+    if bad.dtype != torch.int32 or bad.numel() < 1:
+        raise ValueError("bad must hold one int32")
+    _lib.check(lib.cimrgp_sparse_loo(_DT[abuf.dtype], _p(abuf), _p(vbuf), int(n), int(m), abuf.stride(0), _p(gamma), _p(r),
+                                     int(gamma.shape[1]), float(sf2), float(noise), int(mode), _p(mean_out), _p(var_out), _p(bad),
+                                     _stream()), "cimrgp_sparse_loo")
+
+
+def sparse_joint_cov(xs, ell, sf2, diag, astar, wstar, m, cbuf, cws=None, info=None, cov=_lib.COV_RBF):
+    """lower(cbuf[:ns, :ns]) = K(xs, xs) + diag I - A* A*^T + W* W*^T (cimrgp_sparse_joint_cov); with ``cws`` (uint8
+    workspace) and ``info`` (int32[1]) the block is factored in place and its strict upper triangle zeroed."""
+    cov = _cov_id(cov)             # an unknown id is refused before any allocation
+    lib = _lib.load()
+    if astar.stride(0) != wstar.stride(0):
+        raise ValueError("astar and wstar must have the same row pitch")
+    ns, d = xs.shape
+    _lib.check(lib.cimrgp_sparse_joint_cov(_DT[xs.dtype], cov, _p(xs), int(ns), int(d), float(ell), float(sf2), float(diag),
+                                           _p(astar), _p(wstar), int(m), astar.stride(0), _p(cbuf), cbuf.stride(0), _p(cws),
+                                           0 if cws is None else cws.numel(), _p(info), _stream()), "cimrgp_sparse_joint_cov")
+    return cbuf
+
+
 def layer_lml_scratch_bytes(n, q, batch, dtype):
     return int(_lib.load().cimrgp_layer_lml_grad_scratch_bytes(_DT[dtype], int(n), int(q), int(batch)))
 

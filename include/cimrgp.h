@@ -494,4 +494,8 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
  * include/cimrgp_layer_ard.h. */
 #include "cimrgp_layer_ard.h"
 
+/* Posterior queries of the sparse GP after a fit (predictive gradients, leave-one-out, joint covariance):
+ * include/cimrgp_sparse_post.h. */
+#include "cimrgp_sparse_post.h"
+
 #endif /* CIMRGP_H */
