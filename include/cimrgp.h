@@ -103,7 +103,11 @@ int cimrgp_cov_cross(int dtype, int cov, const void* xa_dev, int64_t na,
  * diagonal blocks needed by cimrgp_potrs / cimrgp_trsm_rows afterwards (the
  * 64 x 64 and 256 x 256 inverses and, per pair of full panels, the off-diagonal
  * block of the 512 x 512 inverse the backward solve steps through).
- * info_dev: one int32, written asynchronously. */
+ * info_dev: one int32, written asynchronously (cleared by the call: a stale value is not an input).  After a
+ * failure at order i the columns of L left of the 64-column block that holds column i-1 are final (bit for bit those
+ * of the same call on a matrix that differs only from that block on), the carried rows' columns left of the
+ * CIMRGP_NB-column panel that holds column i-1 are final likewise, and everything else -- the rest of K and B, the
+ * workspace -- is undefined; the next factorisation on the same stream is not affected. */
 size_t cimrgp_potrf_workspace_bytes(int dtype, int64_t n);
 int cimrgp_potrf(int dtype, void* k_dev, int64_t n, int64_t ldk,
                  void* workspace_dev, size_t workspace_bytes,
