@@ -112,7 +112,157 @@ class RegressionMethod(object):
         return None
 
 
-class GP_RBF(RegressionMethod):
+class PosteriorQueries(RegressionMethod):
+    """The posterior queries of a plugin that holds one fitted block (``GP_RBF``: a DenseBlock, ``SparseGP``: a
+    SparseBlock), written once: the z-scoring in and out, the chain rule through ``data_std`` / ``labels_std``, the
+    symmetric covariance from its lower triangle, the (size, q, ns) reshape of the samples and the Gaussian log density.
+    A plugin keeps ``block`` (None before ``fit``), ``_y`` (the fit's z-scored labels on the device), ``dtype``, and
+    supplies ``_joint``; ``_accumulates`` says whether the block's ``predict`` / ``predict_grad`` add into their outputs
+    (which are then zeroed first) or overwrite them; ``_test_inputs`` and ``_grad_scale`` are overridden by the plugin
+    that rescales its inputs itself.  The public methods here have the exact plugin's signatures; keyword arguments that
+    a plugin's own public methods add (``budget_bytes``, ``include_noise``) go to the block's method unchanged."""
+    _accumulates = False
+
+    def _fitted_block(self, what):
+        if self.block is None:
+            raise RuntimeError('call fit() before %s()' % what)
+        return self.block
+
+    def _test_inputs(self, test_data):
+        """The (preprocessed) test inputs on the block's device, in the block's units."""
+        return dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, self.block.x.device)
+
+    def _grad_scale(self):
+        """d (block's inputs) / d (preprocessed inputs) per dimension where the plugin rescales them, else None."""
+        return None
+
+    def _joint(self, blk, xs, cov_out=None, samples=None, seed=0):
+        """Add the joint predictive covariance at ``xs`` to ``cov_out``'s lower triangle, or draws to ``samples``."""
+        raise NotImplementedError
+
+    def _outputs(self, shape, device):
+        return (torch.zeros if self._accumulates else torch.empty)(shape, dtype=self.dtype, device=device)
+
+    def _predict(self, test_data):
+        return self._predict_mean_var(test_data, want_var=False)[0]
+
+    def _predict_mean_var(self, test_data, want_var, **block_kw):
+        blk = self._fitted_block('predict')
+        xs = self._test_inputs(test_data)
+        mean = self._outputs((xs.shape[0], self._y.shape[1]), xs.device)
+        var = self._outputs(xs.shape[0], xs.device) if want_var else None
+        blk.predict(xs, mean, var, **block_kw)
+        return mean.double().cpu().numpy(), None if var is None else var.double().cpu().numpy()
+
+    def _predict_with_variance(self, test_data, **block_kw):
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        mean, var = self._predict_mean_var(test_data, True, **block_kw)
+        if self.preprocess:
+            mean = self._reverse_trans_labels(mean)
+        return mean, var
+
+    def predict_with_variance(self, test_data):
+        """Mean (un-z-scored) and latent predictive variance (in z-scored label units
+        times labels_std^2 per column is left to the caller; returned as is)."""
+        return self._predict_with_variance(test_data)
+
+    def _predictive_gradients(self, test_data, **block_kw):
+        blk = self._fitted_block('predictive_gradients')
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        xs = self._test_inputs(test_data)
+        ns, d = int(xs.shape[0]), int(xs.shape[1])
+        mean_grad = self._outputs((ns, d, int(self._y.shape[1])), xs.device)
+        var_grad = self._outputs((ns, d), xs.device)
+        blk.predict_grad(xs, mean_grad, var_grad, **block_kw)
+        dmu, dvar = mean_grad.double().cpu().numpy(), var_grad.double().cpu().numpy()
+        s = self._grad_scale()
+        if s is not None:
+            dmu = dmu * s[None, :, None]
+            dvar = dvar * s[None, :]
+        if self.preprocess:
+            inv_std = 1.0 / np.asarray(self.data_std, dtype=np.float64)
+            dmu = dmu * inv_std[None, :, None] * np.asarray(self.labels_std, dtype=np.float64)[None, None, :]
+            dvar = dvar * inv_std[None, :]
+        return dmu, dvar
+
+    def predictive_gradients(self, test_data):
+        """GPy's ``predictive_gradients``: ``(dmu_dX (N*, d, q), dvar_dX (N*, d))`` with respect to the original test
+        inputs (the chain rule through the input z-scoring and, with ARD, the per-dimension 1 / lengthscale scaling).  The
+        mean gradient is in the original label units, per output; the variance gradient is left in z-scored label units,
+        as ``predict_with_variance`` leaves the variance."""
+        return self._predictive_gradients(test_data)
+
+    def _loo_z(self, **block_kw):
+        """(labels, LOO mean, LOO variance) in the (z-scored) units of the fit, NumPy."""
+        blk = self._fitted_block('leave_one_out')
+        y = self._y
+        mean = torch.empty_like(y)
+        var = torch.empty(y.shape[0], dtype=self.dtype, device=y.device)
+        blk.loo(y, mean, var, **block_kw)
+        return y.double().cpu().numpy(), mean.double().cpu().numpy(), var.double().cpu().numpy()
+
+    def _leave_one_out(self, **block_kw):
+        _, mean, var = self._loo_z(**block_kw)
+        if self.preprocess:
+            mean = self._reverse_trans_labels(mean)
+        return mean, var
+
+    def leave_one_out(self):
+        """Closed-form leave-one-out prediction of every training label from the other n - 1 (Rasmussen & Williams
+        5.4.2; hyper-parameters and noise as fitted): ``(mean (n, q), var (n,))``.  The mean is in the original label
+        units; the variance is left in z-scored label units, as ``predict_with_variance`` leaves it, but includes the
+        noise: it is the variance of an observation."""
+        return self._leave_one_out()
+
+    def _loo_log_predictive_density(self, **block_kw):
+        y, mean, var = self._loo_z(**block_kw)
+        q = y.shape[1]
+        return -0.5 * q * np.log(2 * np.pi * var) - 0.5 * ((y - mean) ** 2).sum(axis=1) / var
+
+    def loo_log_predictive_density(self):
+        """(n,) log densities of each training label under its leave-one-out predictive Gaussian, in z-scored label
+        units, summed over the outputs; their sum is the LOO-CV score (R&W eq. 5.11)."""
+        return self._loo_log_predictive_density()
+
+    def predict_with_covariance(self, test_data):
+        """Mean (un-z-scored) and the latent joint predictive covariance (N* x N*, z-scored label units like
+        ``predict_with_variance``'s variance, which is its diagonal)."""
+        blk = self._fitted_block('predict_with_covariance')
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        mean, _ = self._predict_mean_var(test_data, want_var=False)
+        xs = self._test_inputs(test_data)
+        ns = int(xs.shape[0])
+        cov = torch.zeros((ns, ns), dtype=self.dtype, device=xs.device)
+        self._joint(blk, xs, cov_out=cov)
+        cov = torch.tril(cov) + torch.tril(cov, -1).t()
+        if self.preprocess:
+            mean = self._reverse_trans_labels(mean)
+        return mean, cov.double().cpu().numpy()
+
+    def posterior_samples_f(self, test_data, size=1, seed=0):
+        """``size`` draws (size, N*, q) of the latent function in the original label units: the z-scored draw
+        mean + chol(Sigma + 1e-6 sf2 I) Z (Z_c = phi(seed, 0, c, .), c = sample * q + output; include/cimrgp_joint.h)
+        times labels_std, plus labels_mean, per output."""
+        blk = self._fitted_block('posterior_samples_f')
+        if int(size) < 1:
+            raise ValueError('size must be at least 1')
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        mean, _ = self._predict_mean_var(test_data, want_var=False)
+        ns, q = mean.shape
+        xs = self._test_inputs(test_data)
+        out = torch.zeros((int(size) * q, ns), dtype=self.dtype, device=xs.device)
+        self._joint(blk, xs, samples=out, seed=int(seed))
+        f = mean[None, :, :] + out.double().cpu().numpy().reshape(int(size), q, ns).transpose(0, 2, 1)
+        if self.preprocess:
+            f = f * self.labels_std + self.labels_mean
+        return f
+
+
+class GP_RBF(PosteriorQueries):
     name = 'GP_RBF'
 
     def __init__(self, lengthscale=1., variance=1., dtype='f64', device=None, optimize=True, max_iters=1000, ARD=False):
@@ -190,128 +340,22 @@ class GP_RBF(RegressionMethod):
         sink = torch.zeros_like(y)
         self.block.fit(y, None, sink, shared_bias=zero_bias)
         dev.raise_if_not_pd(self.block.info)
-        self._y_dev = y                                  # the (z-scored) labels: leave_one_out reads them
+        self._y = y                                      # the (z-scored) labels: leave_one_out reads them
         return True
 
-    def _predict(self, test_data):
-        return self._predict_mean_var(test_data, want_var=False)[0]
+    # ---- what PosteriorQueries asks of the plugin ----------------------------------------------
+    _accumulates = True                  # DenseBlock.predict / predict_grad add into their outputs
 
     def _test_inputs(self, test_data):
-        """The (preprocessed) test inputs on the block's device, in the block's units (ARD: divided by the length-scales)."""
-        xs = dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, self.block.x.device)
+        """ARD: divided by the length-scales here, the block runs at unit length-scale."""
+        xs = super(GP_RBF, self)._test_inputs(test_data)
         return scaled(xs, self._scale) if self.ARD else xs
 
-    def _predict_mean_var(self, test_data, want_var):
-        blk = self.block
-        xs = self._test_inputs(test_data)
-        q = blk.alpha.shape[1]
-        mean = torch.zeros((xs.shape[0], q), dtype=self.dtype, device=xs.device)
-        var = torch.zeros(xs.shape[0], dtype=self.dtype, device=xs.device) if want_var else None
-        blk.predict(xs, mean, var)
-        return (mean.double().cpu().numpy(), None if var is None else var.double().cpu().numpy())
+    def _grad_scale(self):
+        return 1.0 / np.asarray(self.lengthscales, dtype=np.float64) if self.ARD else None
 
-    def predict_with_variance(self, test_data):
-        """Mean (un-z-scored) and latent predictive variance (in z-scored label units
-        times labels_std^2 per column is left to the caller; returned as is)."""
-        if self.preprocess:
-            test_data = self._preprocess(test_data, False)
-        mean, var = self._predict_mean_var(test_data, want_var=True)
-        if self.preprocess:
-            mean = self._reverse_trans_labels(mean)
-        return mean, var
-
-
-    def predictive_gradients(self, test_data):
-        """GPy's ``predictive_gradients``: ``(dmu_dX (N*, d, q), dvar_dX (N*, d))`` with respect to the original test
-        inputs (the chain rule through the input z-scoring and, with ARD, the per-dimension 1 / lengthscale scaling).  The
-        mean gradient is in the original label units, per output; the variance gradient is left in z-scored label units,
-        as ``predict_with_variance`` leaves the variance."""
-        if self.preprocess:
-            test_data = self._preprocess(test_data, False)
-        blk = self.block
-        xs = self._test_inputs(test_data)
-        ns, d = int(xs.shape[0]), int(xs.shape[1])
-        q = blk.alpha.shape[1]
-        mean_grad = torch.zeros((ns, d, q), dtype=self.dtype, device=xs.device)
-        var_grad = torch.zeros((ns, d), dtype=self.dtype, device=xs.device)
-        blk.predict_grad(xs, mean_grad, var_grad)
-        dmu = mean_grad.double().cpu().numpy()
-        dvar = var_grad.double().cpu().numpy()
-        if self.ARD:
-            s = 1.0 / np.asarray(self.lengthscales, dtype=np.float64)
-            dmu = dmu * s[None, :, None]
-            dvar = dvar * s[None, :]
-        if self.preprocess:
-            inv_std = 1.0 / np.asarray(self.data_std, dtype=np.float64)
-            dmu = dmu * inv_std[None, :, None] * np.asarray(self.labels_std, dtype=np.float64)[None, None, :]
-            dvar = dvar * inv_std[None, :]
-        return dmu, dvar
-
-    def _loo_z(self):
-        """(labels, LOO mean, LOO variance) in the (z-scored) units of the fit, NumPy."""
-        blk = self.block
-        if blk is None:
-            raise RuntimeError('call fit() before leave_one_out()')
-        y = self._y_dev
-        mean = torch.empty_like(y)
-        var = torch.empty(y.shape[0], dtype=self.dtype, device=y.device)
-        blk.loo(y, mean, var)
-        return y.double().cpu().numpy(), mean.double().cpu().numpy(), var.double().cpu().numpy()
-
-    def leave_one_out(self):
-        """Closed-form leave-one-out prediction of every training label from the other n - 1 (Rasmussen & Williams
-        5.4.2; hyper-parameters and noise as fitted): ``(mean (n, q), var (n,))``.  The mean is in the original label
-        units; the variance is left in z-scored label units, as ``predict_with_variance`` leaves it, but includes the
-        noise: it is the variance of an observation."""
-        _, mean, var = self._loo_z()
-        if self.preprocess:
-            mean = self._reverse_trans_labels(mean)
-        return mean, var
-
-    def loo_log_predictive_density(self):
-        """(n,) log densities of each training label under its leave-one-out predictive Gaussian, in z-scored label
-        units, summed over the outputs; their sum is the LOO-CV score (R&W eq. 5.11)."""
-        y, mean, var = self._loo_z()
-        q = y.shape[1]
-        return -0.5 * q * np.log(2 * np.pi * var) - 0.5 * ((y - mean) ** 2).sum(axis=1) / var
-
-    def _joint(self, test_data, cov_out=None, samples=None, seed=0):
-        blk = self.block
-        xs = self._test_inputs(test_data)
+    def _joint(self, blk, xs, cov_out=None, samples=None, seed=0):
         joint_run(blk.joint_call(0, 0, xs.shape[0]), blk.kernel, xs, 0, False, cov_out, samples, seed)
-        return xs.shape[0]
-
-    def predict_with_covariance(self, test_data):
-        """Mean (un-z-scored) and the latent joint predictive covariance (N* x N*, z-scored label units like
-        ``predict_with_variance``'s variance, which is its diagonal)."""
-        if self.preprocess:
-            test_data = self._preprocess(test_data, False)
-        mean, _ = self._predict_mean_var(test_data, want_var=False)
-        ns = np.atleast_2d(np.asarray(test_data)).shape[0]
-        cov = torch.zeros((ns, ns), dtype=self.dtype, device=self.block.x.device)
-        self._joint(test_data, cov_out=cov)
-        cov = torch.tril(cov) + torch.tril(cov, -1).t()
-        if self.preprocess:
-            mean = self._reverse_trans_labels(mean)
-        return mean, cov.double().cpu().numpy()
-
-    def posterior_samples_f(self, test_data, size=1, seed=0):
-        """``size`` draws (size, N*, q) of the latent function in the original label units: the z-scored draw
-        mean + chol(Sigma + 1e-6 sf2 I) Z (Z_c = phi(seed, 0, c, .), c = sample * q + output; include/cimrgp_joint.h)
-        times labels_std, plus labels_mean, per output."""
-        if int(size) < 1:
-            raise ValueError('size must be at least 1')
-        if self.preprocess:
-            test_data = self._preprocess(test_data, False)
-        mean, _ = self._predict_mean_var(test_data, want_var=False)
-        ns, q = mean.shape
-        out = torch.zeros((int(size) * q, ns), dtype=self.dtype, device=self.block.x.device)
-        self._joint(test_data, samples=out, seed=int(seed))
-        f = mean[None, :, :] + out.double().cpu().numpy().reshape(int(size), q, ns).transpose(0, 2, 1)
-        if self.preprocess:
-            f = f * self.labels_std + self.labels_mean
-        return f
-
 
 class GP_Matern(GP_RBF):
     """``GP_RBF`` with the Matern covariance of smoothness ``nu`` in {0.5, 1.5, 2.5}
@@ -330,7 +374,7 @@ class GP_Matern(GP_RBF):
         return DenseMaternKernel(nu=self.nu, l=l, sf=sf, noise=noise)
 
 
-class SparseGP(RegressionMethod):
+class SparseGP(PosteriorQueries):
     """Inducing-point GP regression plugin (:class:`~cimrgp_amd.Sparse.SparseBlock`): ``approximation='fitc'`` or
     ``'vfe'``, cost n m^2 for m = ``num_inducing`` inducing inputs.  ``Z=None`` draws them from the z-scored training
     inputs, ``numpy.random.RandomState(seed).permutation(n)[:min(n, num_inducing)]``; a given ``Z`` (m x d) is in the
@@ -510,118 +554,33 @@ class SparseGP(RegressionMethod):
         self.inducing_inputs = z * self.data_std + self.data_mean if self.preprocess else z
         return True
 
-    def _predict(self, test_data):
-        return self._predict_mean_var(test_data, want_var=False)[0]
-
-    def _predict_mean_var(self, test_data, want_var, include_noise=False, budget_bytes=None):
-        blk = self.block
-        if blk is None:
-            raise RuntimeError('call fit() before predict()')
-        xs = dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, blk.x.device)
-        mean = torch.empty((xs.shape[0], blk.gamma.shape[1]), dtype=self.dtype, device=xs.device)
-        var = torch.empty(xs.shape[0], dtype=self.dtype, device=xs.device) if want_var else None
-        blk.predict(xs, mean, var, include_noise=include_noise, budget_bytes=budget_bytes)
-        return mean.double().cpu().numpy(), None if var is None else var.double().cpu().numpy()
+    # ---- the posterior queries: PosteriorQueries', with the block's own keyword arguments -----------------------
+    def _joint(self, blk, xs, cov_out=None, samples=None, seed=0):
+        blk.joint(xs, cov_out=cov_out, samples=samples, seed=seed)
 
     def predict_with_variance(self, test_data, include_noise=False, budget_bytes=None):
         """Mean (un-z-scored) and predictive variance, left in z-scored label units as ``GP_RBF.predict_with_variance``
         leaves it (latent; ``include_noise`` adds the noise).  ``budget_bytes``: work area of the chunked prediction."""
-        if self.preprocess:
-            test_data = self._preprocess(test_data, False)
-        mean, var = self._predict_mean_var(test_data, True, include_noise, budget_bytes)
-        if self.preprocess:
-            mean = self._reverse_trans_labels(mean)
-        return mean, var
-
-    def _fitted_block(self, what):
-        if self.block is None:
-            raise RuntimeError('call fit() before %s()' % what)
-        return self.block
-
-    def _test_inputs(self, test_data):
-        return dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, self.block.x.device)
+        return self._predict_with_variance(test_data, include_noise=include_noise, budget_bytes=budget_bytes)
 
     def predictive_gradients(self, test_data, budget_bytes=None):
         """``GP_RBF.predictive_gradients`` for the sparse posterior: ``(dmu_dX (N*, d, q), dvar_dX (N*, d))`` with respect
         to the original test inputs.  The mean gradient is in the original label units, the variance gradient in z-scored
         label units, as ``predict_with_variance`` leaves the variance (:meth:`~cimrgp_amd.Sparse.SparseBlock.predict_grad`;
         ARD's 1 / lengthscale is applied by the block)."""
-        blk = self._fitted_block('predictive_gradients')
-        if self.preprocess:
-            test_data = self._preprocess(test_data, False)
-        xs = self._test_inputs(test_data)
-        ns, d = int(xs.shape[0]), int(xs.shape[1])
-        mean_grad = torch.empty((ns, d, int(blk.gamma.shape[1])), dtype=self.dtype, device=xs.device)
-        var_grad = torch.empty((ns, d), dtype=self.dtype, device=xs.device)
-        blk.predict_grad(xs, mean_grad, var_grad, budget_bytes=budget_bytes)
-        dmu, dvar = mean_grad.double().cpu().numpy(), var_grad.double().cpu().numpy()
-        if self.preprocess:
-            inv_std = 1.0 / np.asarray(self.data_std, dtype=np.float64)
-            dmu = dmu * inv_std[None, :, None] * np.asarray(self.labels_std, dtype=np.float64)[None, None, :]
-            dvar = dvar * inv_std[None, :]
-        return dmu, dvar
-
-    def _loo_z(self, budget_bytes=None):
-        """(labels, LOO mean, LOO variance) in the (z-scored) units of the fit, NumPy."""
-        blk = self._fitted_block('leave_one_out')
-        y = self._y
-        mean = torch.empty_like(y)
-        var = torch.empty(y.shape[0], dtype=self.dtype, device=y.device)
-        blk.loo(y, mean, var, budget_bytes=budget_bytes)
-        return y.double().cpu().numpy(), mean.double().cpu().numpy(), var.double().cpu().numpy()
+        return self._predictive_gradients(test_data, budget_bytes=budget_bytes)
 
     def leave_one_out(self, budget_bytes=None):
         """Closed-form leave-one-out prediction of every training label from the other n - 1 under the fitted sparse
         model (exact for FITC's covariance Q_ff + Lambda; VFE / DTC: the same formula with Lambda = noise I):
         ``(mean (n, q), var (n,))``, at the cost of one prediction pass over the training set.  The mean is in the original
         label units; the variance is left in z-scored label units and includes the noise, as ``GP_RBF.leave_one_out``'s."""
-        _, mean, var = self._loo_z(budget_bytes)
-        if self.preprocess:
-            mean = self._reverse_trans_labels(mean)
-        return mean, var
+        return self._leave_one_out(budget_bytes=budget_bytes)
 
     def loo_log_predictive_density(self, budget_bytes=None):
         """(n,) log densities of each training label under its leave-one-out predictive Gaussian, in z-scored label
         units, summed over the outputs; their sum scores the fit -- and the choice of m -- without a held-out set."""
-        y, mean, var = self._loo_z(budget_bytes)
-        q = y.shape[1]
-        return -0.5 * q * np.log(2 * np.pi * var) - 0.5 * ((y - mean) ** 2).sum(axis=1) / var
-
-    def predict_with_covariance(self, test_data):
-        """Mean (un-z-scored) and the latent joint predictive covariance (N* x N*, z-scored label units like
-        ``predict_with_variance``'s variance, which is its diagonal)."""
-        blk = self._fitted_block('predict_with_covariance')
-        if self.preprocess:
-            test_data = self._preprocess(test_data, False)
-        mean, _ = self._predict_mean_var(test_data, want_var=False)
-        xs = self._test_inputs(test_data)
-        ns = int(xs.shape[0])
-        cov = torch.zeros((ns, ns), dtype=self.dtype, device=xs.device)
-        blk.joint(xs, cov_out=cov)
-        cov = torch.tril(cov) + torch.tril(cov, -1).t()
-        if self.preprocess:
-            mean = self._reverse_trans_labels(mean)
-        return mean, cov.double().cpu().numpy()
-
-    def posterior_samples_f(self, test_data, size=1, seed=0):
-        """``size`` draws (size, N*, q) of the latent function in the original label units: the z-scored draw
-        mean + chol(Sigma + 1e-6 sf2 I) Z (Z_c = phi(seed, 0, c, .), c = sample * q + output; include/cimrgp_joint.h)
-        times labels_std, plus labels_mean, per output -- ``GP_RBF.posterior_samples_f``'s convention."""
-        blk = self._fitted_block('posterior_samples_f')
-        if int(size) < 1:
-            raise ValueError('size must be at least 1')
-        if self.preprocess:
-            test_data = self._preprocess(test_data, False)
-        mean, _ = self._predict_mean_var(test_data, want_var=False)
-        ns, q = mean.shape
-        xs = self._test_inputs(test_data)
-        out = torch.zeros((int(size) * q, ns), dtype=self.dtype, device=xs.device)
-        blk.joint(xs, samples=out, seed=int(seed))
-        f = mean[None, :, :] + out.double().cpu().numpy().reshape(int(size), q, ns).transpose(0, 2, 1)
-        if self.preprocess:
-            f = f * self.labels_std + self.labels_mean
-        return f
-
+        return self._loo_log_predictive_density(budget_bytes=budget_bytes)
 
 class SGP_FITC(SparseGP):
     """The reference's ``SGP_FITC`` plugin: :class:`SparseGP` with ``approximation='fitc'``."""

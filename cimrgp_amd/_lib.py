@@ -17,7 +17,8 @@ LIB_PATH = os.environ.get("CIMRGP_LIB_PATH", os.path.join(_HERE, "libcimrgp.so")
 
 _vp, _i64, _i32, _dbl, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_size_t
 
-# name -> (restype, argtypes); must list every symbol of include/cimrgp.h
+# One table per header: name -> (restype, argtypes).  tests/test_abi_signatures_host.py holds each table to its header's
+# prototypes, type for type.
 SIGNATURES = {
     "cimrgp_version": (_i32, []),
     "cimrgp_last_error": (C.c_char_p, []),
@@ -81,14 +82,14 @@ SIGNATURES = {
     "cimrgp_profile_collect_bytes": (_i32, [C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_i64)]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/cimrgp_objective.h (the layer objective)
+# include/cimrgp_objective.h: the layer objective
 OBJECTIVE_SIGNATURES = {
     "cimrgp_layer_lml_grad_scratch_bytes": (_sz, [_i32, _i64, _i32, _i32]),
     "cimrgp_layer_lml_grad_cov": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _dbl, _dbl, _dbl, _vp, _vp, _i64,
                                          _i64, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/cimrgp_joint.h (joint covariance and samples)
+# include/cimrgp_joint.h: joint covariance and samples
 JOINT_SIGNATURES = {
     "cimrgp_normal_fill": (_i32, [_i32, C.c_uint64, _vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp]),
     "cimrgp_layer_joint_cov": (_i32, [_i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _dbl, _dbl, _vp, _i64, _i64, _vp,
@@ -96,7 +97,7 @@ JOINT_SIGNATURES = {
     "cimrgp_layer_sample": (_i32, [_i32, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/cimrgp_grad.h (predictive gradients)
+# include/cimrgp_grad.h: predictive gradients
 GRAD_SIGNATURES = {
     "cimrgp_trsm_rows_lt": (_i32, [_i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp]),
     "cimrgp_trsm_rows_lt_batched": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _sz, _vp, _i64, _i64, _i64, _i32, _vp]),
@@ -106,7 +107,7 @@ GRAD_SIGNATURES = {
                                              _vp, _sz, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _i32, _vp]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/cimrgp_loo.h (leave-one-out cross-validation)
+# include/cimrgp_loo.h: leave-one-out cross-validation
 LOO_SIGNATURES = {
     "cimrgp_trtri_rows": (_i32, [_i32, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
     "cimrgp_kinv_diag_scratch_bytes": (_sz, [_i32, _i64, _i64]),
@@ -116,7 +117,7 @@ LOO_SIGNATURES = {
     "cimrgp_loo_batched": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/cimrgp_sparse.h (inducing-point sparse GP regression)
+# include/cimrgp_sparse.h: inducing-point sparse GP regression
 SPARSE_SIGNATURES = {
     "cimrgp_wsyrk_tn_scratch_bytes": (_sz, [_i32, _i64, _i64, _i32]),
     "cimrgp_wsyrk_tn": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _dbl, _vp, _i64, _vp, _vp, _sz, _vp]),
@@ -124,7 +125,7 @@ SPARSE_SIGNATURES = {
     "cimrgp_sparse_tail": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _dbl, _dbl, _vp, _vp, _i32, _vp]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/cimrgp_sparse_grad.h (gradients of the sparse objective)
+# include/cimrgp_sparse_grad.h: gradients of the sparse objective
 SPARSE_GRAD_SIGNATURES = {
     "cimrgp_cov_pair_grad_scratch_bytes": (_sz, [_i64, _i64, _i32]),
     "cimrgp_cov_pair_grad": (_i32, [_i32, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp, _sz, _vp]),
@@ -132,27 +133,27 @@ SPARSE_GRAD_SIGNATURES = {
     "cimrgp_sparse_grad_combine": (_i32, [_i32, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/cimrgp_sparse_layer.h (sparse layers of the model)
+# include/cimrgp_sparse_layer.h: sparse layers of the model
 SPARSE_LAYER_SIGNATURES = {
     "cimrgp_sparse_lambda_dev": (_i32, [_i32, _vp, _i64, _i64, _i64, _dbl, _vp, _i32, _vp, _vp, _vp, _vp]),
     "cimrgp_sparse_tail_dev": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _i32, _vp]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/cimrgp_sparse_ard.h (ARD length-scales of the sparse GP)
+# include/cimrgp_sparse_ard.h: ARD length-scales of the sparse GP
 SPARSE_ARD_SIGNATURES = {
     "cimrgp_cov_pair_grad_ard_scratch_bytes": (_sz, [_i64, _i64, _i32]),
     "cimrgp_cov_pair_grad_ard": (_i32, [_i32, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp, _sz,
                                         _vp]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/cimrgp_layer_ard.h (the layer objective under ARD)
+# include/cimrgp_layer_ard.h: the layer objective under ARD
 LAYER_ARD_SIGNATURES = {
     "cimrgp_layer_lml_grad_ard_scratch_bytes": (_sz, [_i32, _i64, _i32, _i32]),
     "cimrgp_layer_lml_grad_ard_cov": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _dbl, _dbl, _vp, _vp, _i64, _i64,
                                              _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
 }
 
-# name -> (restype, argtypes); must list every symbol of include/cimrgp_sparse_post.h (posterior queries of the sparse GP)
+# include/cimrgp_sparse_post.h: posterior queries of the sparse GP
 SPARSE_POST_SIGNATURES = {
     "cimrgp_cov_cross_grad": (_i32, [_i32, _i32, _vp, _i64, _vp, _i64, _i32, _dbl, _dbl, _vp, _i64, _i64, _vp]),
     "cimrgp_sparse_tail_grad": (_i32, [_i32, _vp, _vp, _i64, _i64, _i32, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _vp]),
@@ -160,6 +161,27 @@ SPARSE_POST_SIGNATURES = {
     "cimrgp_sparse_joint_cov": (_i32, [_i32, _i32, _vp, _i64, _i32, _dbl, _dbl, _dbl, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _sz, _vp,
                                        _vp]),
 }
+
+#: header -> its table, in the include order of include/cimrgp.h
+HEADERS = {
+    "cimrgp.h": SIGNATURES,
+    "cimrgp_objective.h": OBJECTIVE_SIGNATURES,
+    "cimrgp_joint.h": JOINT_SIGNATURES,
+    "cimrgp_grad.h": GRAD_SIGNATURES,
+    "cimrgp_loo.h": LOO_SIGNATURES,
+    "cimrgp_sparse.h": SPARSE_SIGNATURES,
+    "cimrgp_sparse_grad.h": SPARSE_GRAD_SIGNATURES,
+    "cimrgp_sparse_layer.h": SPARSE_LAYER_SIGNATURES,
+    "cimrgp_sparse_ard.h": SPARSE_ARD_SIGNATURES,
+    "cimrgp_layer_ard.h": LAYER_ARD_SIGNATURES,
+    "cimrgp_sparse_post.h": SPARSE_POST_SIGNATURES,
+}
+
+
+def signatures():
+    """name -> (restype, argtypes) over every header."""
+    return {name: sig for table in HEADERS.values() for name, sig in table.items()}
+
 
 _lib = None
 
@@ -180,10 +202,7 @@ def load():
             "`bash cimrgp_amd/csrc/build.sh` (needs hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + \
-            list(JOINT_SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(LOO_SIGNATURES.items()) + list(SPARSE_SIGNATURES.items()) + \
-            list(SPARSE_GRAD_SIGNATURES.items()) + list(SPARSE_LAYER_SIGNATURES.items()) + list(SPARSE_ARD_SIGNATURES.items()) + \
-            list(LAYER_ARD_SIGNATURES.items()) + list(SPARSE_POST_SIGNATURES.items()):
+    for name, (res, args) in signatures().items():
         fn = getattr(lib, name)          # AttributeError if a symbol is missing
         fn.restype = res
         fn.argtypes = args
