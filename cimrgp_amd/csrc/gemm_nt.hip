@@ -571,6 +571,7 @@ void k_thin_update(T* __restrict__ C, int64_t ldc, const T* __restrict__ A, int6
 #pragma unroll
         for (int r = 0; r < M; ++r) {
             T v = acc[i][r];
+            // wave_sum's order (reduce.hpp), written out: on the benchmark's path, and the helper changes the kernel's schedule
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
             acc[i][r] = v;

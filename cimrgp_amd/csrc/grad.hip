@@ -10,6 +10,7 @@
 //   layer_grad     per block: the shared cross-Gram and forward row solve (cross_solve_run, layer.hip), the batched
 //                  backward row solve above, then the batched contraction
 #include "abi.hpp"
+#include "reduce.hpp"
 
 namespace cimrgp {
 
@@ -226,16 +227,9 @@ void k_cov_predict_grad(const T* __restrict__ x, const int64_t* __restrict__ sta
             for (int k = 0; k < DD; ++k) vs[k] += gb * df[k];
         }
     }
-    // sum over the 32 phases of this test point (lanes ph = 0..31 of one half wave)
-#pragma unroll
-    for (int off = PG_PH / 2; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < DD; ++k) {
-            vs[k] += __shfl_xor(vs[k], off);
-#pragma unroll
-            for (int cc = 0; cc < Q; ++cc) ms[k][cc] += __shfl_xor(ms[k][cc], off);
-        }
-    }
+    // sum over the 32 phases of this test point (lanes ph = 0..31 of one half wave): wave_sum over 32 lanes
+    // (reduce.hpp)
+    wave_sum<PG_PH>(vs, ms);
     if (ph != 0 || !valid) return;
     const int64_t row = toff + gi;
     if (want_mean) {

@@ -17,27 +17,14 @@
 // per block for the prediction: a layer of 128 blocks of 2048 points was launch-bound (22 ms for 0.37
 // Tflop).
 #include "common.hpp"
+#include "reduce.hpp"
 
 namespace cimrgp {
 
 namespace {
 
-template <typename T>
-static __device__ __forceinline__ T ly_block_sum(T v, T* red)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    T s = (T)0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];   // fixed order: deterministic
-    return s;
-}
-
 // Per block b: column means of (y - f_bar) and the pooled population variance about them
-// (k_block_stats' arithmetic, misc.hip), then
+// (block_stats, reduce.hpp: the body of k_block_stats, misc.hip), then
 //   bias[b]  = the shared bias if given, else the column means
 //   noise[b] = the fixed value if >= 0, else the shared noise if given, else max(frac var, floor)
 // (RegressionInput.py:62: labels.var() * 0.01).
@@ -52,28 +39,14 @@ void k_layer_stats(const T* __restrict__ y, const T* __restrict__ fbar, const in
     const int b = blockIdx.x;
     const T* yb = y + starts[b] * q;
     const T* fb = fbar ? fbar + starts[b] * q : nullptr;
-    for (int c = 0; c < q; ++c) {
-        T s = (T)0;
-        for (int64_t i = threadIdx.x; i < n; i += blockDim.x)
-            s += yb[i * q + c] - (fb ? fb[i * q + c] : (T)0);
-        s = ly_block_sum(s, red);
-        if (threadIdx.x == 0) smean[c] = s / (T)n;
-    }
-    __syncthreads();
-    T s2 = (T)0;
-    for (int64_t e = threadIdx.x; e < n * q; e += blockDim.x) {
-        const int c = (int)(e % q);
-        const T r = yb[e] - (fb ? fb[e] : (T)0) - smean[c];
-        s2 += r * r;
-    }
-    s2 = ly_block_sum(s2, red);
+    const T var = block_stats(yb, fb, n, q, red, smean);
     if (threadIdx.x == 0) {
         for (int c = 0; c < q; ++c) bias[(int64_t)b * q + c] = shared_bias ? shared_bias[c] : smean[c];
         T v;
         if (noise_fixed >= (T)0) v = noise_fixed;
         else if (shared_noise) v = shared_noise[0];
         else {
-            v = frac * (s2 / (T)(n * q));
+            v = frac * var;
             if (!(v > floor_value)) v = floor_value;
         }
         noise[b] = v;

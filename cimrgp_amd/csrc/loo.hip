@@ -14,6 +14,7 @@
 // A row's values depend on its global index alone (tiles and strips are aligned to global row numbers, every K loop
 // has a fixed order): the result is bit-identical whatever the strip height.
 #include "abi.hpp"
+#include "reduce.hpp"
 #include "gemm_tile.hpp"
 
 namespace cimrgp {
@@ -153,7 +154,7 @@ void k_loo_update(T* __restrict__ U, int64_t ldu, int64_t su, int M, int N, int 
 // ---------------------------------------------------------------- row sums of squares ----
 // One workgroup per row of the strip (blockIdx.y = block): thread t sums the squares of columns first + t, first + t +
 // 256, ... (first = the row's own panel: what lies left of it is structurally zero and is not read), then the 256
-// partial sums are added pairwise in LDS.  The order depends on the row's global index alone.
+// partial sums are added pairwise in LDS (lds_tree, reduce.hpp).  The order depends on the row's global index alone.
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_loo_rowsq(const T* __restrict__ U, int64_t ldu, int64_t su, int r0, int n, T* __restrict__ out, int64_t so)
@@ -168,12 +169,7 @@ void k_loo_rowsq(const T* __restrict__ U, int64_t ldu, int64_t su, int r0, int n
         s += v * v;
     }
     red[tid] = s;
-    __syncthreads();
-#pragma unroll
-    for (int half = 128; half > 0; half >>= 1) {
-        if (tid < half) red[tid] += red[tid + half];
-        __syncthreads();
-    }
+    lds_tree<256>(red, tid);
     if (tid == 0) out[(int64_t)blockIdx.y * so + g] = (T)red[0];
 }
 

@@ -2,50 +2,25 @@
 // All HBM-bound and tiny (O(n q)); they exist so that the product path never
 // leaves the device between blocks.
 #include "common.hpp"
+#include "reduce.hpp"
 
 namespace cimrgp {
 
 namespace {
 
-
-template <typename T>
-static __device__ __forceinline__ T block_sum_1024(T v, T* red)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    T s = (T)0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];   // fixed order: deterministic
-    return s;
-}
-
 // stats[c] = mean_i (y - fbar)[i][c];  stats[q] = pooled population variance
-// of the centred block.  One workgroup (the block is at most a few MB).
+// of the centred block.  One workgroup (the block is at most a few MB); the sums are block_stats' (reduce.hpp).
 template <typename T>
 __global__ __launch_bounds__(1024)
 void k_block_stats(const T* __restrict__ y, const T* __restrict__ fbar, int64_t n, int q, T* __restrict__ stats)
 {
     __shared__ T red[16];
     __shared__ T smean[MAXQ];
-    for (int c = 0; c < q; ++c) {
-        T s = (T)0;
-        for (int64_t i = threadIdx.x; i < n; i += blockDim.x)
-            s += y[i * q + c] - (fbar ? fbar[i * q + c] : (T)0);
-        s = block_sum_1024(s, red);
-        if (threadIdx.x == 0) { smean[c] = s / (T)n; stats[c] = smean[c]; }
+    const T var = block_stats(y, fbar, n, q, red, smean);
+    if (threadIdx.x == 0) {
+        for (int c = 0; c < q; ++c) stats[c] = smean[c];
+        stats[q] = var;
     }
-    __syncthreads();
-    T s2 = (T)0;
-    for (int64_t e = threadIdx.x; e < n * q; e += blockDim.x) {
-        const int c = (int)(e % q);
-        const T r = y[e] - (fbar ? fbar[e] : (T)0) - smean[c];
-        s2 += r * r;
-    }
-    s2 = block_sum_1024(s2, red);
-    if (threadIdx.x == 0) stats[q] = s2 / (T)(n * q);
 }
 
 template <typename T>
@@ -85,14 +60,22 @@ __global__ void k_noise_from_stats(const T* __restrict__ stats, int q, T frac, T
     }
 }
 
+// sum_i log L_ii over one workgroup: thread t takes i = t, t + blockDim.x, ..; block_sum (reduce.hpp) adds.  Every
+// thread returns the sum.  red: 16 doubles in LDS.
+template <typename T>
+static __device__ __forceinline__ double logdet_half(const T* __restrict__ l, int64_t n, int64_t ld, double* red)
+{
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) s += log((double)l[i * ld + i]);
+    return block_sum(s, red);
+}
+
 template <typename T>
 __global__ __launch_bounds__(1024)
 void k_logdet_half(const T* __restrict__ l, int64_t n, int64_t ld, double* __restrict__ out)
 {
     __shared__ double red[16];
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) s += log((double)l[i * ld + i]);
-    s = block_sum_1024(s, red);
+    const double s = logdet_half(l, n, ld, red);
     if (threadIdx.x == 0) out[0] = s;
 }
 
@@ -283,16 +266,9 @@ void k_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict
             if (gr == gc) s_tr += (double)g;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s_sf += __shfl_xor(s_sf, off, 64);
-        s_l  += __shfl_xor(s_l, off, 64);
-        s_tr += __shfl_xor(s_tr, off, 64);
-        if (ARD) {
-#pragma unroll
-            for (int k = 0; k < MAXD; ++k) s_lk[k] += __shfl_xor(s_lk[k], off, 64);
-        }
-    }
+    // the lanes of a wave by wave_sum, then the four waves' lane-0 values in wave order (sum4; reduce.hpp)
+    if constexpr (ARD) wave_sum(s_sf, s_tr, s_lk);
+    else               wave_sum(s_sf, s_l, s_tr);
     if (ARD) {
         if (tx == 0) {
             red[0][ty] = s_sf;
@@ -301,27 +277,35 @@ void k_lml_grad_tiles(const T* __restrict__ x, int n, int d, const T* __restrict
             red[LG_NP - 1][ty] = s_tr;
         }
         __syncthreads();
-        if (tid < LG_NP) partial[(int64_t)id * LG_NP + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+        if (tid < LG_NP) partial[(int64_t)id * LG_NP + tid] = sum4(red[tid][0], red[tid][1], red[tid][2], red[tid][3]);
     } else {
         if (tx == 0) { red[0][ty] = s_sf; red[1][ty] = s_l; red[2][ty] = s_tr; }
         __syncthreads();
-        if (tid < 3) partial[(int64_t)id * 3 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+        if (tid < 3) partial[(int64_t)id * 3 + tid] = sum4(red[tid][0], red[tid][1], red[tid][2], red[tid][3]);
     }
+}
+
+// Entry c of the nout gradient entries from the tile records of one block, over one workgroup: np entries per record,
+// the last one the trace term, which is the last gradient entry (the noise's); the first nout - 1 are taken as they
+// come.  Thread t takes tiles t, t + blockDim.x, ..; block_sum (reduce.hpp) adds.  Every thread returns the entry.
+static __device__ __forceinline__ double lml_grad_entry(const double* __restrict__ partial, int64_t ntiles, int np, int nout, int c,
+                                                        double noise, double* red)
+{
+    const int src = (c == nout - 1) ? np - 1 : c;
+    double s = 0.0;
+    for (int64_t t = threadIdx.x; t < ntiles; t += blockDim.x) s += partial[t * np + src];
+    s = block_sum(s, red);
+    return 0.5 * s * (c == nout - 1 ? noise : 1.0);
 }
 
 __global__ __launch_bounds__(1024)
 void k_lml_grad_final(const double* __restrict__ partial, int64_t ntiles, double noise, double* __restrict__ out,
                       int np, int nout)
 {
-    // np entries per tile record, the last one the trace term; the first nout - 1 are copied out
     __shared__ double red[16];
     for (int c = 0; c < nout; ++c) {
-        const int src = (c == nout - 1) ? np - 1 : c;
-        double s = 0.0;
-        for (int64_t t = threadIdx.x; t < ntiles; t += blockDim.x) s += partial[t * np + src];
-        s = block_sum_1024(s, red);
-        if (threadIdx.x == 0) out[c] = 0.5 * s * (c == nout - 1 ? noise : 1.0);
-        __syncthreads();
+        const double g = lml_grad_entry(partial, ntiles, np, nout, c, noise, red);
+        if (threadIdx.x == 0) out[c] = g;
     }
 }
 
@@ -370,8 +354,8 @@ template int lml_grad_run<float>(const float*, int64_t, int, const float*, int64
 
 // ---- a layer's blocks at once (cimrgp_layer_lml_grad_cov) ----
 // The tile kernels above with grid.y = block, then per block one workgroup that finishes it: the gradient from its
-// tile records (k_lml_grad_final's order), the data fit sum_c z_c^T z_c = sum_c r_c^T K^-1 r_c from z = L^-1 r, and
-// sum_i log L_ii from the factor's diagonal:
+// tile records (lml_grad_entry, as k_lml_grad_final), the data fit sum_c z_c^T z_c = sum_c r_c^T K^-1 r_c from
+// z = L^-1 r, and sum_i log L_ii from the factor's diagonal (logdet_half, as k_logdet_half):
 //   out[4b + 0] = -1/2 fit - q sum log L_ii - 1/2 n q log 2 pi,  out[4b + 1 .. 3] = the gradient.
 // ARD (cimrgp_layer_lml_grad_ard_cov): tile records of LG_NP entries and nout = d + 2 gradient entries, the record of
 // block b at out[(d + 3) b]: [LML | sf | l_1 .. l_d | noise].  One body for both; per component the sums run in the
@@ -392,25 +376,17 @@ void layer_lml_final(const double* __restrict__ partial, int64_t ntiles, double 
     double g[NP];
 #pragma unroll
     for (int c = 0; c < NP; ++c) {
-        g[c] = 0.0;
-        if (c < nout) {
-            const int src = (c == nout - 1) ? NP - 1 : c;
-            double s = 0.0;
-            for (int64_t t = threadIdx.x; t < ntiles; t += blockDim.x) s += partial[t * NP + src];
-            g[c] = block_sum_1024(s, red);
-        }
+        g[c] = c < nout ? lml_grad_entry(partial, ntiles, NP, nout, c, noise, red) : 0.0;
     }
+    const double half_logdet = logdet_half(l, n, ld, red);
     double s = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) s += log((double)l[i * ld + i]);
-    const double half_logdet = block_sum_1024(s, red);
-    s = 0.0;
     for (int64_t e = threadIdx.x; e < n * q; e += blockDim.x) s += (double)z[e] * (double)z[e];
-    const double fit = block_sum_1024(s, red);
+    const double fit = block_sum(s, red);
     if (threadIdx.x == 0) {
         out[(nout + 1) * b + 0] = -0.5 * fit - (double)q * half_logdet - 0.5 * (double)(n * q) * log(2.0 * M_PI);
 #pragma unroll
         for (int c = 0; c < NP; ++c)
-            if (c < nout) out[(nout + 1) * b + 1 + c] = 0.5 * g[c] * (c == nout - 1 ? noise : 1.0);
+            if (c < nout) out[(nout + 1) * b + 1 + c] = g[c];
     }
 }
 

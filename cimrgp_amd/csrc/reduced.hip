@@ -6,6 +6,7 @@
 // Everything that does not scale with N (Bingham axes, ARD, Gamma/Normal updates) stays on the
 // host.
 #include "common.hpp"
+#include "reduce.hpp"
 
 namespace cimrgp {
 
@@ -177,7 +178,8 @@ void k_basis_moments(const T* __restrict__ x, int d, const double* __restrict__ 
         }
         __syncthreads();
     }
-    // ---- combine: lane groups (shuffles), then waves (LDS, fixed order), then the per-row sums
+    // ---- combine: lane groups (shuffles, ascending from a run-time width: not wave_sum's order, see reduce.hpp), then
+    // waves (LDS, fixed order), then the per-row sums
     for (int off = width; off < 64; off <<= 1) {
         s1 += __shfl_xor(s1, off, 64);
         s2 += __shfl_xor(s2, off, 64);
@@ -191,14 +193,8 @@ void k_basis_moments(const T* __restrict__ x, int d, const double* __restrict__ 
         s_red[wave * per_wave + m * Q + lane] = s1;
         s_red[wave * per_wave + m * Q + m + lane] = s2;
     }
-    // per-row sums: wave reduction then one value per wave into the tile area (free by now)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sn += __shfl_xor(sn, off, 64);
-        sv += __shfl_xor(sv, off, 64);
-#pragma unroll
-        for (int c = 0; c < Q; ++c) sr[c] += __shfl_xor(sr[c], off, 64);
-    }
+    // per-row sums: wave reduction (wave_sum, reduce.hpp) then one value per wave into the tile area (free by now)
+    wave_sum(sn, sv, sr);
     if (lane == 0) {
 #pragma unroll
         for (int c = 0; c < Q; ++c) tile[wave * (Q + 2) + c] = sr[c];
@@ -230,8 +226,8 @@ void k_basis_moments(const T* __restrict__ x, int d, const double* __restrict__ 
     }
 }
 
-// One workgroup per output element: 256 strided partial sums, then a fixed-shape tree -- the
-// result depends on the launch geometry only, never on timing.
+// One workgroup per output element: 256 strided partial sums, then a fixed-shape tree (lds_tree,
+// reduce.hpp) -- the result depends on the launch geometry only, never on timing.
 __global__ __launch_bounds__(256)
 void k_basis_moments_final(const double* __restrict__ partial, int nwg, double* __restrict__ out)
 {
@@ -240,11 +236,7 @@ void k_basis_moments_final(const double* __restrict__ partial, int nwg, double* 
     double s = 0.0;
     for (int w = threadIdx.x; w < nwg; w += 256) s += src[w];
     tree[threadIdx.x] = s;
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {
-        if ((int)threadIdx.x < half) tree[threadIdx.x] += tree[threadIdx.x + half];
-        __syncthreads();
-    }
+    lds_tree<256>(tree, (int)threadIdx.x);
     if (threadIdx.x == 0) out[blockIdx.x] = tree[0];
 }
 

@@ -118,6 +118,7 @@ void k_fwd_update(const T* __restrict__ L, int64_t ld, int n, T* __restrict__ wo
         T sv = (T)0;
 #pragma unroll
         for (int e = 0; e < EPL; ++e) sv += lv[e] * zs[c][lane * EPL + e];
+        // wave_sum's order (reduce.hpp), written out: on the benchmark's path, and the helper changes the kernel's schedule
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) sv += __shfl_xor(sv, off, 64);
         if (lane == 0 && r < n) work[(int64_t)c * n + r] = wold[c] - sv;
@@ -163,6 +164,7 @@ void k_bwd_alpha(const T* __restrict__ invT, int n, const T* __restrict__ work, 
         T sv = bv[0] * wv[c][0];
 #pragma unroll
         for (int e = 1; e < 4; ++e) sv += bv[e] * wv[c][e];
+        // wave_sum's order (reduce.hpp), written out: on the benchmark's path, and the helper changes the kernel's schedule
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) sv += __shfl_xor(sv, off, 64);
         if (lane == 0) out[(int64_t)c * n + k0 + r] = sv;
@@ -207,6 +209,7 @@ void k_bwd_alpha2(const T* __restrict__ invT, const T* __restrict__ xoff, int n,
 #pragma unroll
             for (int e = 0; e < 4; ++e) sv += xv[e] * work[(int64_t)c * n + k0 + PW + lane * 4 + e];
         }
+        // wave_sum's order (reduce.hpp), written out: on the benchmark's path, and the helper changes the kernel's schedule
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) sv += __shfl_xor(sv, off, 64);
         if (lane == 0) out[(int64_t)c * n + k0 + r2] = sv;
@@ -333,6 +336,8 @@ void k_predict_from_w(const T* __restrict__ W, int ns, int n, int64_t ldw, const
             for (int c = 0; c < Q; ++c) sm[c] += w * z[(int64_t)n2 * q + c];
         }
     }
+    // wave_sum's order, then sum4's over the four waves (reduce.hpp), both written out: on the benchmark's path, and the
+    // helpers change the kernel's schedule
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         ss += __shfl_xor(ss, off, 64);

@@ -20,6 +20,7 @@
 // more multiply per row tile and k step.
 // Every hand-off through LDS is: stores, lds_settle (read back the last word stored), lds_barrier.
 #include "abi.hpp"
+#include "reduce.hpp"
 
 namespace cimrgp {
 
@@ -283,24 +284,23 @@ void k_wsyrk_reduce(const T* __restrict__ cpart, const T* __restrict__ gpart, in
 }
 
 // --------------------------------------------------------------------- lambda ----
-// A wave per row (4 rows per workgroup): lane l adds the squares of columns l, l + 64, .. in FP64, then the 64 partial
-// sums are added pairwise (xor 32, 16, .. 1): a fixed order.  lam <- lambda_i, dtmp <- sf2 - q_i (k_sparse_sums turns
-// it into w).  noise_dev != nullptr: the noise is that element on the device, not the argument.
+// A wave per row (wave_row, reduce.hpp): lane l adds the squares of columns l, l + 64, .. in FP64, then the 64 partial
+// sums are added pairwise (wave_sum: xor 32, 16, .. 1): a fixed order.  lam <- lambda_i, dtmp <- sf2 - q_i
+// (k_sparse_sums turns it into w).  noise_dev != nullptr: the noise is that element on the device, not the argument.
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_sparse_rowsq(const T* __restrict__ A, int64_t lda, int n, int m, double sf2, double noise, const T* __restrict__ noise_dev,
                     int mode, T* __restrict__ lam, T* __restrict__ dtmp)
 {
-    const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= n) return;
+    int row, lane;
+    if (!wave_row(n, row, lane)) return;
     const T* a = A + (int64_t)row * lda;
     double s = 0.0;
     for (int c = lane; c < m; c += 64) {
         const double v = (double)a[c];
         s += v * v;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    wave_sum(s);
     if (lane == 0) {
         if (noise_dev) noise = (double)noise_dev[0];
         const double d = sf2 - s;
@@ -309,7 +309,8 @@ void k_sparse_rowsq(const T* __restrict__ A, int64_t lda, int n, int m, double s
     }
 }
 
-// One workgroup of 1024 threads: thread t takes i = t, t + 1024, ..; the 1024 partial sums are added pairwise in LDS.
+// One workgroup of 1024 threads: thread t takes i = t, t + 1024, ..; the 1024 partial sums are added pairwise in LDS
+// (lds_tree, reduce.hpp).
 template <typename T>
 __global__ __launch_bounds__(1024)
 void k_sparse_sums(const T* __restrict__ lam, T* __restrict__ w, int n, double* __restrict__ sums)
@@ -327,32 +328,23 @@ void k_sparse_sums(const T* __restrict__ lam, T* __restrict__ w, int n, double* 
     red[0][tid] = slog;
     red[1][tid] = sd;
     red[2][tid] = bad;
-    __syncthreads();
-    for (int half = 512; half > 0; half >>= 1) {
-        if (tid < half) {
-            red[0][tid] += red[0][tid + half];
-            red[1][tid] += red[1][tid + half];
-            red[2][tid] += red[2][tid + half];
-        }
-        __syncthreads();
-    }
+    lds_tree<1024, 3>(&red[0][0], tid);
     if (tid < 3) sums[tid] = red[tid][0];
 }
 
 // ----------------------------------------------------------------------- tail ----
-// bias (q elements) and extra (one element) may be nullptr: then they add nothing and the result is that of the call
-// without them, bit for bit.  Both are added in FP64 before the one rounding to T.
+// The row walk of k_sparse_rowsq (wave_row, wave_sum).  bias (q elements) and extra (one element) may be nullptr: then
+// they add nothing and the result is that of the call without them, bit for bit.  Both are added in FP64 before the one
+// rounding to T.
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_sparse_tail(const T* __restrict__ As, const T* __restrict__ Ws, int ns, int m, int64_t lda, const T* __restrict__ gamma, int q,
                    double base, const T* __restrict__ bias, const T* __restrict__ extra, T* __restrict__ mean, T* __restrict__ var,
                    int accumulate)
 {
-    const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= ns) return;
-    double sa = 0.0, sw = 0.0, acc[MAXQ];
-#pragma unroll
-    for (int c = 0; c < MAXQ; ++c) acc[c] = 0.0;
+    int row, lane;
+    if (!wave_row(ns, row, lane)) return;
+    double sa = 0.0, sw = 0.0, acc[MAXQ] = {};
     const T* wrow = Ws + (int64_t)row * lda;
     for (int j = lane; j < m; j += 64) {
         const double wv = (double)wrow[j];
@@ -361,32 +353,18 @@ void k_sparse_tail(const T* __restrict__ As, const T* __restrict__ Ws, int ns, i
             sa += av * av;
             sw += wv * wv;
         }
-        if (mean) {
-#pragma unroll
-            for (int c = 0; c < MAXQ; ++c)
-                if (c < q) acc[c] += wv * (double)gamma[j * q + c];
-        }
+        if (mean) dot_step(acc, wv, gamma + (int64_t)j * q, q);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sa += __shfl_xor(sa, off, 64);
-        sw += __shfl_xor(sw, off, 64);
-#pragma unroll
-        for (int c = 0; c < MAXQ; ++c) acc[c] += __shfl_xor(acc[c], off, 64);
-    }
+    wave_sum(sa, sw, acc);
     if (lane != 0) return;
     if (var) {
         if (extra) base += (double)extra[0];
-        const T v = (T)(base - sa + sw);
-        var[row] = accumulate ? var[row] + v : v;
+        put(var + row, (T)(base - sa + sw), accumulate);
     }
     if (mean) {
 #pragma unroll
         for (int c = 0; c < MAXQ; ++c)
-            if (c < q) {
-                const T v = bias ? (T)(acc[c] + (double)bias[c]) : (T)acc[c];
-                mean[(int64_t)row * q + c] = accumulate ? mean[(int64_t)row * q + c] + v : v;
-            }
+            if (c < q) put(mean + (int64_t)row * q + c, bias ? (T)(acc[c] + (double)bias[c]) : (T)acc[c], accumulate);
     }
 }
 

@@ -21,6 +21,7 @@
 // sum G dk/dlog l: the product wg df_e that db adds is multiplied by df_e once more.  k, g and db are the same
 // instructions in both arms.
 #include "abi.hpp"
+#include "reduce.hpp"
 
 namespace cimrgp {
 
@@ -138,16 +139,9 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
         }
     }
 
-    // the scalar sums: pairwise over the lanes of a wave, then the four waves in order
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sk += __shfl_xor(sk, off, 64);
-        if constexpr (!ARD) sl += __shfl_xor(sl, off, 64);
-        if constexpr (ARD) {
-#pragma unroll
-            for (int k = 0; k < DD; ++k) sd[k] += __shfl_xor(sd[k], off, 64);
-        }
-    }
+    // the scalar sums: pairwise over the lanes of a wave (wave_sum, reduce.hpp), then the four waves in order (sum4)
+    if constexpr (ARD) wave_sum(sk, sd);
+    else               wave_sum(sk, sl);
     if (lane == 0) {
         sred[wave][0] = sk;
         if constexpr (!ARD) sred[wave][1] = sl;
@@ -158,7 +152,7 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
     }
     __syncthreads();
     const int ns = ARD ? 1 + d : 2;             // the sums of the dimensions >= d (all 0) are not written
-    if (tid < ns) sumpart[(int64_t)blockIdx.x * ns + tid] = ((sred[0][tid] + sred[1][tid]) + sred[2][tid]) + sred[3][tid];
+    if (tid < ns) sumpart[(int64_t)blockIdx.x * ns + tid] = sum4(sred[0][tid], sred[1][tid], sred[2][tid], sred[3][tid]);
     if (!want_db) return;
     // db: per dimension, the NPH row phases of a column are added in phase order
     double* out = dbpart + (int64_t)blockIdx.x * PG_CT * d;
@@ -180,7 +174,7 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
 
 // blockIdx.x < dblocks: 256 elements of db, each the sum of its S partials in slice order; workgroup dblocks + c (sums
 // wanted, c < nsums): thread t adds the partials t, t + 256, .. of scalar sum c (tile-major within a slice), then the 256
-// partial sums are added pairwise in LDS.
+// partial sums are added pairwise in LDS (lds_tree, reduce.hpp).
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_pair_grad_reduce(const double* __restrict__ dbpart, const double* __restrict__ sumpart, int nb, int d, int tiles, int slices,
@@ -205,42 +199,29 @@ void k_pair_grad_reduce(const double* __restrict__ dbpart, const double* __restr
     double s = 0.0;
     for (int64_t p = tid; p < parts; p += 256) s += sumpart[nsums * p + c];
     red[tid] = s;
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {
-        if (tid < half) red[tid] += red[tid + half];
-        __syncthreads();
-    }
+    lds_tree<256>(red, tid);
     if (tid == 0) sums[c] = accumulate ? sums[c] + red[0] : red[0];
 }
 
 // ----------------------------------------------------------------------- rows ----
-// A wave per row (4 rows per workgroup), as k_sparse_rowsq / k_sparse_tail: lane l takes columns l, l + 64, .. in FP64,
-// then the 64 partial sums are added pairwise (xor 32, 16, .. 1): a fixed order.  t <- h_i (k_sparse_grad_sums turns it
-// into t for VFE).
+// A wave per row (wave_row, reduce.hpp), as k_sparse_rowsq / k_sparse_tail: lane l takes columns l, l + 64, .. in FP64,
+// then the 64 partial sums are added pairwise (wave_sum: xor 32, 16, .. 1): a fixed order.  t <- h_i (k_sparse_grad_sums
+// turns it into t for VFE).
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_sparse_grad_rows(const T* __restrict__ V, int64_t ldv, int n, int m, const T* __restrict__ gamma, const T* __restrict__ r,
                         const T* __restrict__ w, int q, T* __restrict__ beta, T* __restrict__ t)
 {
-    const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= n) return;
+    int row, lane;
+    if (!wave_row(n, row, lane)) return;
     const T* v = V + (int64_t)row * ldv;
-    double sv = 0.0, acc[MAXQ];
-#pragma unroll
-    for (int c = 0; c < MAXQ; ++c) acc[c] = 0.0;
+    double sv = 0.0, acc[MAXQ] = {};
     for (int j = lane; j < m; j += 64) {
         const double vv = (double)v[j];
         sv += vv * vv;
-#pragma unroll
-        for (int c = 0; c < MAXQ; ++c)
-            if (c < q) acc[c] += vv * (double)gamma[(int64_t)j * q + c];
+        dot_step(acc, vv, gamma + (int64_t)j * q, q);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sv += __shfl_xor(sv, off, 64);
-#pragma unroll
-        for (int c = 0; c < MAXQ; ++c) acc[c] += __shfl_xor(acc[c], off, 64);
-    }
+    wave_sum(sv, acc);
     if (lane != 0) return;
     const double wi = (double)w[row];
     double bsq = 0.0;
@@ -255,7 +236,8 @@ void k_sparse_grad_rows(const T* __restrict__ V, int64_t ldv, int n, int m, cons
     t[row] = (T)(0.5 * (bsq - (double)q * (wi - wi * wi * sv)));
 }
 
-// One workgroup of 1024 threads: thread k takes i = k, k + 1024, ..; the 1024 partial sums are added pairwise in LDS.
+// One workgroup of 1024 threads: thread k takes i = k, k + 1024, ..; the 1024 partial sums are added pairwise in LDS
+// (lds_tree).
 template <typename T>
 __global__ __launch_bounds__(1024)
 void k_sparse_grad_sums(T* __restrict__ t, int n, int mode, double tvfe, double* __restrict__ sums)
@@ -276,14 +258,7 @@ void k_sparse_grad_sums(T* __restrict__ t, int n, int mode, double tvfe, double*
     }
     red[0][tid] = sh;
     red[1][tid] = st;
-    __syncthreads();
-    for (int half = 512; half > 0; half >>= 1) {
-        if (tid < half) {
-            red[0][tid] += red[0][tid + half];
-            red[1][tid] += red[1][tid + half];
-        }
-        __syncthreads();
-    }
+    lds_tree<1024, 2>(&red[0][0], tid);
     if (tid < 2) sums[tid] = red[tid][0];
 }
 

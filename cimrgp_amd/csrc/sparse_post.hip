@@ -16,6 +16,7 @@
 // The row kernels follow k_sparse_tail (sparse.hip): lane l takes columns l, l + 64, .. in FP64, then the 64 partial sums
 // are added pairwise (xor 32, 16, .. 1) -- a fixed order that depends on m alone.
 #include "abi.hpp"
+#include "reduce.hpp"
 #include "gemm_tile.hpp"
 
 namespace cimrgp {
@@ -115,83 +116,57 @@ void k_cov_cross_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb
     }
 }
 
-// A wave per (row, e), 4 per workgroup.  A, gamma, mg, vg may be nullptr as the entry point allows.
+// A wave per (row, e), 4 per workgroup (wave_row, reduce.hpp); the lanes' partial sums are added by wave_sum.  A, gamma,
+// mg, vg may be nullptr as the entry point allows.
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_sparse_tail_grad(const T* __restrict__ A, const T* __restrict__ W, int ns, int m, int d, int64_t ld, int64_t ss,
                         const T* __restrict__ gamma, int q, T* __restrict__ mg, T* __restrict__ vg, int accumulate)
 {
-    const int64_t idx = (int64_t)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (idx >= (int64_t)ns * d) return;
+    int64_t idx;
+    int lane;
+    if (!wave_row((int64_t)ns * d, idx, lane)) return;
     const int64_t row = idx / d;
     const int e = (int)(idx - row * d);
     const T* w0 = W + row * ld;
     const T* we = w0 + (int64_t)(e + 1) * ss;
     const T* a0 = vg ? A + row * ld : nullptr;
     const T* ae = vg ? a0 + (int64_t)(e + 1) * ss : nullptr;
-    double sv = 0.0, acc[MAXQ];
-#pragma unroll
-    for (int c = 0; c < MAXQ; ++c) acc[c] = 0.0;
+    double sv = 0.0, acc[MAXQ] = {};
     for (int j = lane; j < m; j += 64) {
         const double dw = (double)we[j];
         if (vg) sv += (double)w0[j] * dw - (double)a0[j] * (double)ae[j];
-        if (mg) {
-#pragma unroll
-            for (int c = 0; c < MAXQ; ++c)
-                if (c < q) acc[c] += dw * (double)gamma[(int64_t)j * q + c];
-        }
+        if (mg) dot_step(acc, dw, gamma + (int64_t)j * q, q);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sv += __shfl_xor(sv, off, 64);
-#pragma unroll
-        for (int c = 0; c < MAXQ; ++c) acc[c] += __shfl_xor(acc[c], off, 64);
-    }
+    wave_sum(sv, acc);
     if (lane != 0) return;
-    if (vg) {
-        const T v = (T)(2.0 * sv);
-        vg[idx] = accumulate ? vg[idx] + v : v;
-    }
+    if (vg) put(vg + idx, (T)(2.0 * sv), accumulate);
     if (mg) {
 #pragma unroll
         for (int c = 0; c < MAXQ; ++c)
-            if (c < q) {
-                const T v = (T)acc[c];
-                mg[idx * q + c] = accumulate ? mg[idx * q + c] + v : v;
-            }
+            if (c < q) put(mg + idx * q + c, (T)acc[c], accumulate);
     }
 }
 
-// A wave per row, 4 rows per workgroup.  lm or lv may be nullptr.
+// A wave per row, 4 rows per workgroup (wave_row); the lanes' partial sums are added by wave_sum.  lm or lv may be nullptr.
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_sparse_loo(const T* __restrict__ A, const T* __restrict__ V, int n, int m, int64_t ld, const T* __restrict__ gamma,
                   const T* __restrict__ r, int q, double sf2, double noise, int mode, T* __restrict__ lm, T* __restrict__ lv,
                   int32_t* __restrict__ bad)
 {
-    const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= n) return;
+    int row, lane;
+    if (!wave_row(n, row, lane)) return;
     const T* a = A + (int64_t)row * ld;
     const T* v = V + (int64_t)row * ld;
-    double sa = 0.0, sv = 0.0, acc[MAXQ];
-#pragma unroll
-    for (int c = 0; c < MAXQ; ++c) acc[c] = 0.0;
+    double sa = 0.0, sv = 0.0, acc[MAXQ] = {};
     for (int j = lane; j < m; j += 64) {
         const double av = (double)a[j], vv = (double)v[j];
         sa += av * av;
         sv += vv * vv;
-#pragma unroll
-        for (int c = 0; c < MAXQ; ++c)
-            if (c < q) acc[c] += vv * (double)gamma[(int64_t)j * q + c];
+        dot_step(acc, vv, gamma + (int64_t)j * q, q);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sa += __shfl_xor(sa, off, 64);
-        sv += __shfl_xor(sv, off, 64);
-#pragma unroll
-        for (int c = 0; c < MAXQ; ++c) acc[c] += __shfl_xor(acc[c], off, 64);
-    }
+    wave_sum(sa, sv, acc);
     if (lane != 0) return;
     const double lam = mode == 0 ? sf2 - sa + noise : noise;
     const double one_h = 1.0 - sv / lam;

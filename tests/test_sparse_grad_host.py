@@ -37,7 +37,8 @@ def test_sparse_grad_header_symbols_are_exported_and_registered():
         assert getattr(lib, name).argtypes == _lib.SPARSE_GRAD_SIGNATURES[name][1], name
     assert '#include "cimrgp_sparse_grad.h"' in open(os.path.join(ROOT, "include", "cimrgp.h")).read()
     build = open(os.path.join(ROOT, "cimrgp_amd", "csrc", "build.sh")).read()
-    assert " sparse_grad;" in build and "cimrgp_sparse_grad.h -nt" in build
+    # every header beside cimrgp.h is a dependency of every object: the build script takes them by pattern
+    assert " sparse_grad;" in build and "for h in *.hpp ../../include/*.h" in build and '"$h" -nt "$f.o"' in build
 
 
 def test_pair_grad_scratch_bytes_by_formula():
