@@ -1,5 +1,5 @@
 """Hyper-parameter learning on the host: the rules every plugin and the model share ("Hyper-parameter learning on
-the host").  One place each for the ARD input scaling, the optimisers' parameter vector [log sf, log l .., log noise, (Z)],
+the host").  One place each for the ARD input scaling, the optimisers' parameter vector [log sf, log l .., log noise, (log v ..), (Z)],
 the L-BFGS-B call with its score of a failed trial point, and the sum of a layer's per-block objectives with its failure
 codes.  Host only: nothing here calls the library."""
 import numpy as np
@@ -33,6 +33,19 @@ def unpack_theta(theta, n_ell=None):
     length-scale, a float; else ARD with ``n_ell`` length-scales, a fresh (n_ell,) array."""
     vals = np.exp(theta[:(1 if n_ell is None else n_ell) + 2])
     return (float(vals[1]) if n_ell is None else vals[1:-1].copy()), float(vals[0]), float(vals[-1])
+
+
+def append_linear(theta, linear):
+    """``theta`` = [log sf, log l .., log noise] with the d log-variances of a linear term appended: [.., log v_1 .. log v_d];
+    Z, where it is learned, follows them."""
+    return np.concatenate([np.asarray(theta, dtype=np.float64), np.log(np.asarray(linear, dtype=np.float64).reshape(-1))])
+
+
+def split_linear(theta, n_linear, n_ell=None):
+    """``(head, linear, rest)`` of a parameter vector laid out by :func:`append_linear`: the [log sf, log l .., log noise] that
+    :func:`unpack_theta` reads, the ``n_linear`` variances (a fresh array, not their logarithms) and what follows them (Z)."""
+    nt = (1 if n_ell is None else n_ell) + 2
+    return theta[:nt], np.exp(theta[nt:nt + n_linear]), theta[nt + n_linear:]
 
 
 def minimize_lml(objective, theta0, max_iters, jac=True):

@@ -25,7 +25,7 @@ import torch
 
 from . import device as dev
 from ._lib import COV_RBF
-from .Hyper import minimize_lml, pack_theta, scaled, unit_lengthscale, unpack_theta
+from .Hyper import append_linear, minimize_lml, pack_theta, scaled, split_linear, unit_lengthscale, unpack_theta
 from .KernelClass import RBFKernel, DenseMaternKernel
 from .Posteriors import DenseBlock, NOISE_FRACTION, joint_run
 
@@ -439,6 +439,8 @@ class SparseGP(PosteriorQueries):
         self.optimizer_result = None
         self.block = None
         self.inducing_ids = None             # rows of the training set drawn as inducing inputs (Z=None)
+        self.linear_variances = None         # SparseGP_RBFLinear: (d,) variances of the linear term after fit
+        self._initial_linear = None          # ... and their starting value, a scalar or a (d,) vector
 
     def _make_kernel(self, l, sf, noise=None):
         if self.nu is None:
@@ -459,13 +461,17 @@ class SparseGP(PosteriorQueries):
             raise ValueError('Z must have the dimension of the inputs')
         return (self.Z - self.data_mean) / self.data_std if self.preprocess else self.Z
 
-    def _block(self, ell, sf, noise):
-        """The block at (ell, sf, noise); ARD: ``ell`` is the (d,) vector and the kernel's own length-scale 1."""
+    def _block(self, ell, sf, noise, linear=None):
+        """The block at (ell, sf, noise); ARD: ``ell`` is the (d,) vector and the kernel's own length-scale 1.  A model with a
+        linear term carries its variances: ``linear``, or the fitted ones."""
         from .Sparse import SparseBlock
+        if linear is None:
+            linear = self.linear_variances
+        kw = {} if linear is None else dict(linear=linear)
         if self.ARD:
             return SparseBlock(self._x, self._z, self._make_kernel(1.0, sf, noise), self.approximation, self.jitter,
-                               lengthscales=ell)
-        return SparseBlock(self._x, self._z, self._make_kernel(ell, sf, noise), self.approximation, self.jitter)
+                               lengthscales=ell, **kw)
+        return SparseBlock(self._x, self._z, self._make_kernel(ell, sf, noise), self.approximation, self.jitter, **kw)
 
     def _ell(self, ell):
         """The ``ell=`` argument of the two objective calls: the fitted value by default; ARD: a scalar stands for all
@@ -476,37 +482,55 @@ class SparseGP(PosteriorQueries):
             return self.lengthscales
         return np.full(self.lengthscales.shape[0], float(ell)) if np.ndim(ell) == 0 else np.asarray(ell, dtype=np.float64)
 
-    def log_marginal_likelihood(self, ell=None, sf=None, noise=None):
+    def _linear(self, linear):
+        """The ``linear=`` argument of the two objective calls: the (d,) variances of the linear term, a scalar standing for
+        all dimensions; refused by a model without the term."""
+        if linear is None:
+            return None
+        if self.linear_variances is None:
+            raise TypeError('%s has no linear term' % type(self).__name__)
+        d = self.linear_variances.shape[0]
+        return np.full(d, float(linear)) if np.ndim(linear) == 0 else np.asarray(linear, dtype=np.float64)
+
+    def log_marginal_likelihood(self, ell=None, sf=None, noise=None, linear=None):
         """The FITC marginal likelihood / the VFE bound of the fitted data at (ell, sf, noise); the fitted values by
-        default.  Raises LinAlgError if a factorisation fails or a lambda_i is not positive."""
+        default.  Raises LinAlgError if a factorisation fails or a lambda_i is not positive.  ``linear``: the variances of
+        the linear term of a model that has one (``SparseGP_RBFLinear``)."""
         if self.block is None:
             raise RuntimeError('call fit() before log_marginal_likelihood()')
-        if ell is None and sf is None and noise is None:
+        if ell is None and sf is None and noise is None and linear is None:
             return self.block.log_marginal_likelihood()
         k = self.kernel
-        blk = self._block(self._ell(ell), k.sf if sf is None else float(sf), k.noise if noise is None else float(noise))
+        blk = self._block(self._ell(ell), k.sf if sf is None else float(sf), k.noise if noise is None else float(noise),
+                          self._linear(linear))
         return blk.fit(self._y).log_marginal_likelihood()
 
-    def log_marginal_likelihood_grad(self, ell=None, sf=None, noise=None, want_z=True):
+    def log_marginal_likelihood_grad(self, ell=None, sf=None, noise=None, want_z=True, linear=None):
         """``(lml, dtheta, dZ)`` of the fitted data at (ell, sf, noise), the fitted values by default: the objective of
         :meth:`log_marginal_likelihood`, its gradient w.r.t. (log sf, log ell, log noise) as a (3,) array (ARD: one entry
         per length-scale, (d + 2,)) and, with ``want_z``, w.r.t. the inducing inputs in the (z-scored) units of the fit as
-        an (m, d) array, else None.
+        an (m, d) array, else None.  A model with a linear term has d more entries at the end of dtheta, w.r.t.
+        (log v_1 .. log v_d), taken at ``linear`` (default: the fitted variances).
         Raises as :meth:`log_marginal_likelihood` does."""
         if self.block is None:
             raise RuntimeError('call fit() before log_marginal_likelihood_grad()')
         k = self.kernel
-        blk = self._block(self._ell(ell), k.sf if sf is None else float(sf), k.noise if noise is None else float(noise))
+        blk = self._block(self._ell(ell), k.sf if sf is None else float(sf), k.noise if noise is None else float(noise),
+                          self._linear(linear))
         lml, dtheta, dz = blk.lml_grad(self._y, want_z=want_z)
         return lml, dtheta, None if dz is None else dz.double().cpu().numpy()
 
     def _optimize(self, noise0):
         """L-BFGS-B over [log sf, log l (ARD: one per dimension), log noise] and, with ``optimize_inducing``, Z: on the
         analytic gradient (``jac='analytic'``) or on SciPy's two-point differences of the objective.  Returns the
-        optimum's (ell, sf, noise)."""
+        optimum's (ell, sf, noise).  A model with a linear term learns its d log-variances too, between log noise and Z, and
+        leaves the optimum's in ``linear_variances``."""
         analytic, learn_z = self.jac == 'analytic', self.optimize_inducing
         n_ell = self.lengthscales.shape[0] if self.ARD else None
         theta0 = pack_theta(self.kernel.sf, self.lengthscales if self.ARD else self.kernel.l, noise0)
+        n_lin = 0 if self.linear_variances is None else self.linear_variances.shape[0]
+        if n_lin:
+            theta0 = append_linear(theta0, self.linear_variances)
         nt = theta0.shape[0]
         zshape = tuple(self._z.shape)
         if learn_z:
@@ -515,7 +539,7 @@ class SparseGP(PosteriorQueries):
         def objective(theta):
             if learn_z:
                 self._z = dev.to_device(theta[nt:].reshape(zshape), self.dtype, self._x.device)
-            blk = self._block(*unpack_theta(theta, n_ell))
+            blk = self._block(*unpack_theta(theta, n_ell), linear=split_linear(theta, n_lin, n_ell)[1] if n_lin else None)
             if not analytic:
                 return blk.fit(self._y).log_marginal_likelihood()
             lml, dtheta, dz = blk.lml_grad(self._y, want_z=learn_z)
@@ -525,6 +549,8 @@ class SparseGP(PosteriorQueries):
         if learn_z:
             self._z = dev.to_device(res.x[nt:].reshape(zshape), self.dtype, self._x.device)
         self.optimizer_result = res
+        if n_lin:
+            self.linear_variances = split_linear(res.x, n_lin, n_ell)[1]
         return unpack_theta(res.x, n_ell)
 
     def _fit(self, train_data):
@@ -532,6 +558,11 @@ class SparseGP(PosteriorQueries):
         d = np.atleast_2d(np.asarray(inputs)).shape[1]
         if self.ARD and np.ndim(self._initial[0]) > 0 and self._initial[0].shape[0] != d:
             raise ValueError('lengthscale has %d entries, the inputs have %d dimensions' % (self._initial[0].shape[0], d))
+        if self._initial_linear is not None:
+            v = self._initial_linear
+            if np.ndim(v) > 0 and v.shape[0] != d:
+                raise ValueError('linear_variance has %d entries, the inputs have %d dimensions' % (v.shape[0], d))
+            self.linear_variances = np.full(d, float(v)) if np.ndim(v) == 0 else v.copy()
         device = dev.require_gpu(self.device)
         inputs = np.atleast_2d(np.asarray(inputs, dtype=np.float64))
         labels = np.atleast_2d(np.asarray(labels, dtype=np.float64))
@@ -594,10 +625,52 @@ class SGP_FITC(SparseGP):
 
 class SparseGP_RBF(SparseGP):
     """The reference's ``SparseGP_RBF`` plugin: :class:`SparseGP` with ``approximation='vfe'``, the bound GPy's
-    ``SparseGPRegression`` optimises (without the reference's ``+ Linear`` term)."""
+    ``SparseGPRegression`` optimises, with the RBF (or Matern) covariance alone; the reference's ``RBF + Linear`` kernel is
+    :class:`SparseGP_RBFLinear`."""
     name = 'SparseGP_RBF'
 
     def __init__(self, num_inducing=1000, lengthscale=1., variance=1., nu=None, Z=None, seed=0, jitter=1e-6, dtype='f64',
                  device=None, optimize=False, max_iters=200, jac='2-point', optimize_inducing=False, ARD=False):
         super(SparseGP_RBF, self).__init__(num_inducing, 'vfe', lengthscale, variance, nu, Z, seed, jitter, dtype, device, optimize,
                                            max_iters, jac, optimize_inducing, ARD)
+
+
+class SparseGP_RBFLinear(SparseGP):
+    """The reference's ``SparseGP_RBF`` plugin with the kernel the reference gives it, ``RBF(d, ARD=True) + Linear(d, ARD=True)``
+    under GPy's ``SparseGPRegression`` (the VFE bound): k(x, x') = k_cov(x, x') + sum_e v_e x_e x'_e on the z-scored inputs
+    ("A linear term for the sparse GP").  The linear term lets the model extrapolate a trend in the labels, which a
+    stationary covariance can only soak up in a long length-scale.  ``linear_variance``: the starting v, a scalar (every
+    dimension) or a length-d sequence; after the fit ``linear_variances`` holds the (d,) vector.  ``optimize=True`` learns
+    them with the other hyper-parameters: the parameter vector is [log sf, log l .., log noise, log v_1 .. log v_d,
+    (Z.ravel())].  Everything else is :class:`SparseGP`'s, ``nu`` and ``approximation='fitc'`` included.  The five posterior
+    queries beyond ``predict`` / ``predict_with_variance`` are not built for this kernel and raise TypeError."""
+    name = 'SparseGP_RBFLinear'
+
+    def __init__(self, num_inducing=1000, lengthscale=1., variance=1., linear_variance=1., nu=None, Z=None, seed=0, jitter=1e-6,
+                 dtype='f64', device=None, optimize=False, max_iters=200, jac='2-point', optimize_inducing=False, ARD=True,
+                 approximation='vfe'):
+        super(SparseGP_RBFLinear, self).__init__(num_inducing, approximation, lengthscale, variance, nu, Z, seed, jitter, dtype,
+                                                 device, optimize, max_iters, jac, optimize_inducing, ARD)
+        v = np.asarray(linear_variance, dtype=np.float64)
+        if v.ndim > 1 or v.size == 0 or not (np.isfinite(v).all() and (v > 0).all()):
+            raise ValueError('linear_variance must be positive and finite, a scalar or one entry per input dimension, got %r'
+                             % (linear_variance,))
+        self._initial_linear = float(v) if v.ndim == 0 else v.copy()
+
+    def _not_built(self, what):
+        raise TypeError('%s() of %s (a covariance with a linear term) is not yet supported' % (what, self.name))
+
+    def predictive_gradients(self, test_data, budget_bytes=None):
+        self._not_built('predictive_gradients')
+
+    def leave_one_out(self, budget_bytes=None):
+        self._not_built('leave_one_out')
+
+    def loo_log_predictive_density(self, budget_bytes=None):
+        self._not_built('loo_log_predictive_density')
+
+    def predict_with_covariance(self, test_data):
+        self._not_built('predict_with_covariance')
+
+    def posterior_samples_f(self, test_data, size=1, seed=0):
+        self._not_built('posterior_samples_f')

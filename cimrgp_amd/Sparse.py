@@ -22,11 +22,16 @@ the sparse GP"): the block works on x / l and z / l with a unit length-scale, an
 log l_e from cimrgp_cov_pair_grad_ard.
 After a fit the block also answers ``predict_grad``, ``loo`` and ``joint`` ("Posterior queries of the sparse GP":
 cimrgp_cov_cross_grad, cimrgp_sparse_tail_grad, cimrgp_sparse_loo, cimrgp_sparse_joint_cov); a model layer's block does not.
+``SparseBlock(..., linear=)`` adds a linear term to the covariance, k(x, x') = k_cov(x, x') + sum_e v_e x_e x'_e ("A
+linear term for the sparse GP"): k(x, x) is then not the constant sf, and the fit, the prediction and ``lml_grad`` take the
+calls of include/cimrgp_sparse_linear.h (cimrgp_cov_gram_lin, cimrgp_cov_cross_lin, cimrgp_sparse_lambda_kd,
+cimrgp_cov_pair_grad_lin); the posterior queries of such a block are not built.
 """
 import numpy as np
 import torch
 
 from . import device as dev
+from . import device_linear as devl
 from .Hyper import scaled, sum_block_objectives, unit_lengthscale
 from .Posteriors import DensePosterior, NOISE_FRACTION, NOISE_FLOOR, _Fanout, block_targets, joint_blocks
 
@@ -39,13 +44,17 @@ PREDICT_BUDGET_BYTES = 1 << 30
 class SparseBlock(object):
     """Device-resident state of one inducing-point block: L_u and L_B with their workspaces, and gamma."""
 
-    def __init__(self, x, z, kernel, approximation='fitc', jitter=1e-6, device_noise=False, lengthscales=None):
+    def __init__(self, x, z, kernel, approximation='fitc', jitter=1e-6, device_noise=False, lengthscales=None, linear=None):
         """``x`` (n x d), ``z`` (m x d): device tensors in the same units; ``kernel``: an ``RBFKernel`` /
         ``DenseMaternKernel`` with its ``noise`` set.  ``device_noise``: the block is a model layer's, fitted by
         :meth:`fit_layer` with its noise variance in a device scalar; ``kernel.noise`` may then be None.
         ``lengthscales``: a (d,) array of positive length-scales, one per input dimension (ARD), in the units of ``x``;
         ``kernel.l`` must then be 1.0, as ``GP_RBF(ARD=True)`` builds its kernel.  The block computes on x / l and z / l;
-        ``x``, ``z``, the test inputs of :meth:`predict` and the dZ of :meth:`lml_grad` stay in the caller's units."""
+        ``x``, ``z``, the test inputs of :meth:`predict` and the dZ of :meth:`lml_grad` stay in the caller's units.
+        ``linear``: a (d,) array of positive variances v_e in the units of ``x``: the covariance is k_cov(x, x') +
+        sum_e v_e x_e x'_e (GPy's ``Linear(d, ARD=True)`` added to the kernel); the jitter stays ``jitter * sf``.  On the
+        scaled inputs the same term has the weights u_e = v_e l_e^2, which the block forms; callers speak in v.  None: no
+        such term, and every call is the one made before the term existed."""
         key = str(approximation).lower()
         if key not in APPROXIMATIONS:
             raise ValueError("approximation must be 'fitc' or 'vfe', got %r" % (approximation,))
@@ -69,6 +78,16 @@ class SparseBlock(object):
             self.lengthscales = ls.copy()
             self._scale, self._xs = unit_lengthscale(self.x, ls)
             self._zs = scaled(self.z, self._scale)
+        self.linear = self._u = self._lin = None         # v (caller's units), u = v l^2 (host), u as device float64 (d,)
+        if linear is not None:
+            v = np.asarray(linear, dtype=np.float64)
+            if v.shape != (int(x.shape[1]),) or not (np.isfinite(v).all() and (v > 0).all()):
+                raise ValueError('linear must be %d positive variances, one per input dimension' % int(x.shape[1]))
+            if device_noise:
+                raise ValueError('a linear term is not available to a model layer (device_noise=True)')
+            self.linear = v.copy()
+            self._u = v if self.lengthscales is None else v * self.lengthscales ** 2
+            self._lin = torch.as_tensor(self._u, dtype=torch.float64).to(x.device)
         self.n, self.m = int(x.shape[0]), int(z.shape[0])
         self.kernel = kernel
         self.device_noise = bool(device_noise)
@@ -85,6 +104,8 @@ class SparseBlock(object):
         """The fit's device calls, nothing read back: (A, w, lambda sums).  A (n x m) is the caller's to free.
         ``noise_dev``: the noise variance as a device scalar, in place of ``kernel.noise``."""
         k, n, m = self.kernel, self.n, self.m
+        if self._lin is not None:
+            return self._enqueue_fit_linear()
         self.lu = dev.rbf_gram(self._zs, k.l, k.sf, self.jitter * k.sf, lower_only=True, cov=k.cov)
         self.ws_u, self.info_u = dev.potrf(self.lu, m)
         a = dev.rbf_cross(self._xs, self._zs, k.l, k.sf, cov=k.cov)
@@ -93,6 +114,21 @@ class SparseBlock(object):
             _, w, sums = dev.sparse_lambda_dev(a, n, m, k.sf, noise_dev, self.mode)
         else:
             _, w, sums = dev.sparse_lambda(a, n, m, k.sf, k.noise, self.mode)
+        return a, w, sums
+
+    def _lin_diag(self, xs):
+        """sum_e u_e xs_ie^2 of scaled inputs ``xs``: the linear term's share of k(x_i, x_i), FP64 (O(n d) torch arithmetic)."""
+        return (xs.double() ** 2 * self._lin).sum(dim=1)
+
+    def _enqueue_fit_linear(self):
+        """:meth:`_enqueue_fit` with the linear term: the _lin Gram calls, and lambda from k(x_i, x_i) = sf + sum_e u_e x_ie^2."""
+        k, n, m = self.kernel, self.n, self.m
+        self.lu = devl.cov_gram_lin(self._zs, k.l, k.sf, self._lin, self.jitter * k.sf, lower_only=True, cov=k.cov)
+        self.ws_u, self.info_u = dev.potrf(self.lu, m)
+        a = devl.cov_cross_lin(self._xs, self._zs, k.l, k.sf, self._lin, cov=k.cov)
+        dev.trsm_rows(self.lu, m, self.ws_u, a, n)
+        kdiag = (k.sf + self._lin_diag(self._xs)).to(self._xs.dtype)
+        _, w, sums = devl.sparse_lambda_kd(a, n, m, kdiag, k.noise, self.mode)
         return a, w, sums
 
     def _enqueue_solve(self, r, c, w, sums):
@@ -171,7 +207,10 @@ class SparseBlock(object):
         The failure rules are :meth:`fit`'s.  A stays alive for the length of the call beside ONE more
         n x m buffer (V, Y, G_A and G_fu in place of one another); one host read-back at the end (the info words, the
         lambda count and the scalars).  g of Matern 1/2 is taken as 0 at r = 0 (an inducing input on a training input or
-        on another inducing input, where the objective has a kink): such pairs contribute nothing to dZ."""
+        on another inducing input, where the objective has a kink): such pairs contribute nothing to dZ.
+        With ``linear`` the gradient has d more entries at its end, w.r.t. log v_1 .. log v_d (cimrgp_cov_pair_grad_lin in
+        place of either pair contraction; dZ carries the linear part), and d / dlog sf is taken in its pairwise form: the
+        closed form 1/2 tr M + sf sum t holds only while k is proportional to sf."""
         k, n, m = self.kernel, self.n, self.m
         q = int(r.shape[1])
         r = r.contiguous()
@@ -215,25 +254,42 @@ class SparseBlock(object):
         guu[:m, :m] = -0.25 * (guu[:m, :m] + guu[:m, :m].t())
         # sum G o K, sum G o dK/dlog l and dZ: K_fu's pairs, then K_uu's added (G_uu symmetric: scale 2 = -2 x -1)
         # with lengthscales: [sum G o K, sum G o dK/dlog l_e for every e] on the scaled inputs, and dZ of the scaled Z
-        pair_grad = dev.cov_pair_grad if self._scale is None else dev.cov_pair_grad_ard
-        psums, dz = pair_grad(self._xs, self._zs, y, k.l, k.sf, want_db=want_z, cov=k.cov)
-        pair_grad(self._zs, self._zs, guu, k.l, k.sf, scale=2.0, accumulate=True, sums=psums, db=dz, want_db=want_z, cov=k.cov)
+        lin_terms = []
+        if self._lin is None:
+            pair_grad = dev.cov_pair_grad if self._scale is None else dev.cov_pair_grad_ard
+            psums, dz = pair_grad(self._xs, self._zs, y, k.l, k.sf, want_db=want_z, cov=k.cov)
+            pair_grad(self._zs, self._zs, guu, k.l, k.sf, scale=2.0, accumulate=True, sums=psums, db=dz, want_db=want_z, cov=k.cov)
+        else:
+            # lsums_e = sum G o dK/du_e over both matrices; sum_i t_i x_ie^2 is the diagonal's share (t_i = dF / dk_ii)
+            ard = self._scale is not None
+            psums, lsums, dz = devl.cov_pair_grad_lin(self._xs, self._zs, y, k.l, k.sf, self._lin, ard=ard, want_db=want_z, cov=k.cov)
+            devl.cov_pair_grad_lin(self._zs, self._zs, guu, k.l, k.sf, self._lin, ard=ard, scale=2.0, accumulate=True, sums=psums,
+                                   lsums=lsums, db=dz, want_db=want_z, cov=k.cov)
+            lin_terms = [lsums, (t.double()[:, None] * self._xs.double() ** 2).sum(dim=0)]
         del y
         if dz is not None and self._scale is not None:
             dz = dz * self._scale                        # d / dz_je = (d / d(z_je / l_e)) / l_e
         _, half_logdet_b, rwr, gg, _ = self._terms
         host = torch.cat([self.info_u.double(), self.info_b.double(), sums, half_logdet_b.reshape(1), rwr.reshape(1), gg.reshape(1),
                           gsums, psums, torch.diagonal(mm).double().sum().reshape(1),
-                          torch.diagonal(guu[:m, :m]).double().sum().reshape(1)]).cpu().numpy()
+                          torch.diagonal(guu[:m, :m]).double().sum().reshape(1)] + lin_terms).cpu().numpy()
         info_u, info_b, s0, s1, bad, hld, rwr_h, gg_h, sum_h, sum_t, gk = host[:11]
-        gl, (tr_m, tr_guu) = host[11:-2], host[-2:]      # gl: one entry, or one per length-scale
+        ngl = int(psums.shape[0]) - 1
+        gl, (tr_m, tr_guu) = host[11:11 + ngl], host[11 + ngl:13 + ngl]      # gl: one entry, or one per length-scale
         self._raise_if_failed(info_u, bad, info_b)
         lml = self._lml_from(s0, s1, hld, rwr_h, gg_h, q)
-        dsf = 0.5 * tr_m + k.sf * sum_t
         dnoise = k.noise * (sum_h + (0.5 * q / k.noise ** 2 * s1 if self.mode == 1 else 0.0))
-        #: the pairwise form of d F / d log sf, which the closed form above must equal (checked by the GPU tests)
-        self.grad_check = dict(closed=float(dsf), pairwise=float(gk + self.jitter * k.sf * tr_guu + k.sf * sum_t))
-        return lml, np.concatenate([[dsf], gl, [dnoise]]), dz
+        if self._lin is None:
+            dsf = 0.5 * tr_m + k.sf * sum_t
+            #: the pairwise form of d F / d log sf, which the closed form above must equal (checked by the GPU tests)
+            self.grad_check = dict(closed=float(dsf), pairwise=float(gk + self.jitter * k.sf * tr_guu + k.sf * sum_t))
+            return lml, np.concatenate([[dsf], gl, [dnoise]]), dz
+        d = self._u.shape[0]
+        lsums_h, tx2 = host[13 + ngl:13 + ngl + d], host[13 + ngl + d:]
+        dsf = gk + self.jitter * k.sf * tr_guu + k.sf * sum_t
+        #: 1/2 tr M = sum G o K over both matrices, whatever K is: the covariance's, the jitter's and the linear term's shares
+        self.grad_check = dict(closed=float(0.5 * tr_m), pairwise=float(gk + self.jitter * k.sf * tr_guu + (self._u * lsums_h).sum()))
+        return lml, np.concatenate([[dsf], gl, [dnoise], self._u * (lsums_h + tx2)]), dz
 
     def chunk_rows(self, budget_bytes=None):
         """Test rows per pass of ``predict``: A* and W* (pitch padded_ld(m)) within ``budget_bytes``, a multiple of 256."""
@@ -249,9 +305,15 @@ class SparseBlock(object):
             raise RuntimeError('call fit() before predict()')
         k, m = self.kernel, self.m
         extra = k.noise if include_noise else 0.0
+        accumulate = self._lin is not None
+        if accumulate:                                   # k(x*, x*) = sf + sum_e u_e x*_e^2: the tail adds onto the linear share
+            if mean is not None:
+                mean.zero_()
+            if var is not None:
+                var.copy_(self._lin_diag(xs if self._scale is None else scaled(xs, self._scale)))
         for s0, s1, astar, wstar in self._star_chunks(xs, budget_bytes):
             dev.sparse_tail(astar if var is not None else None, wstar, s1 - s0, m, self.gamma if mean is not None else None, k.sf,
-                            extra, None if mean is None else mean[s0:s1], None if var is None else var[s0:s1])
+                            extra, None if mean is None else mean[s0:s1], None if var is None else var[s0:s1], accumulate)
         return mean, var
 
     def _star_chunks(self, xs, budget_bytes=None):
@@ -268,16 +330,22 @@ class SparseBlock(object):
                 astar = dev.alloc_matrix(min(step, ns), m, xs.dtype, xs.device)
                 wstar = torch.empty_like(astar)
             xc = xs[s0:s1] if self._scale is None else scaled(xs[s0:s1], self._scale)
-            dev.rbf_cross(xc, self._zs, k.l, k.sf, out=astar, cov=k.cov)
+            if self._lin is None:
+                dev.rbf_cross(xc, self._zs, k.l, k.sf, out=astar, cov=k.cov)
+            else:
+                devl.cov_cross_lin(xc, self._zs, k.l, k.sf, self._lin, out=astar, cov=k.cov)
             dev.trsm_rows(self.lu, m, self.ws_u, astar, rows)
             wstar[:rows].copy_(astar[:rows])
             dev.trsm_rows(self.lb, m, self.ws_b, wstar, rows)
             yield s0, s1, astar, wstar
 
     def _ready_for(self, what):
-        """The posterior queries below are the plugins': a model layer's block (``device_noise=True``) is refused."""
+        """The posterior queries below are the plugins': a model layer's block (``device_noise=True``) is refused, and so is
+        a block with a linear term, before any device work."""
         if self.device_noise:
             raise TypeError('%s() of a sparse layer of the model (device_noise=True) is not yet supported' % what)
+        if self._lin is not None:
+            raise TypeError('%s() of a sparse block with a linear term is not yet supported' % what)
         if self.gamma is None:
             raise RuntimeError('call fit() before %s()' % what)
 

@@ -162,6 +162,16 @@ SPARSE_POST_SIGNATURES = {
                                        _vp]),
 }
 
+# include/cimrgp_sparse_linear.h: the sparse GP with a linear term in its covariance
+SPARSE_LINEAR_SIGNATURES = {
+    "cimrgp_cov_gram_lin": (_i32, [_i32, _i32, _vp, _i64, _i32, _dbl, _dbl, _vp, _dbl, _vp, _i64, _i32, _vp]),
+    "cimrgp_cov_cross_lin": (_i32, [_i32, _i32, _vp, _i64, _vp, _i64, _i32, _dbl, _dbl, _vp, _vp, _i64, _vp]),
+    "cimrgp_sparse_lambda_kd": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _dbl, _i32, _vp, _vp, _vp, _vp]),
+    "cimrgp_cov_pair_grad_lin_scratch_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "cimrgp_cov_pair_grad_lin": (_i32, [_i32, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _dbl, _dbl, _i32, _vp, _dbl, _i32, _vp, _vp,
+                                        _vp, _vp, _sz, _vp]),
+}
+
 #: header -> its table, in the include order of include/cimrgp.h
 HEADERS = {
     "cimrgp.h": SIGNATURES,
@@ -175,6 +185,7 @@ HEADERS = {
     "cimrgp_sparse_ard.h": SPARSE_ARD_SIGNATURES,
     "cimrgp_layer_ard.h": LAYER_ARD_SIGNATURES,
     "cimrgp_sparse_post.h": SPARSE_POST_SIGNATURES,
+    "cimrgp_sparse_linear.h": SPARSE_LINEAR_SIGNATURES,
 }
 
 

@@ -65,30 +65,34 @@ int rows_queues() { return g_rows_queues.load(std::memory_order_relaxed); }
 using namespace cimrgp;
 
 // The RBF entry points and their _cov twins share one body each: the RBF one forwards CIMRGP_COV_RBF, for which the
-// covariance check is always true; `fn` names the entry point that was called in every message.
+// covariance check is always true; `fn` names the entry point that was called in every message.  The _lin twins
+// (include/cimrgp_sparse_linear.h) pass lin_entry and their weights lin_dev, which must then be there.
 static int gram_impl(const char* fn, int dtype, int cov, const void* x_dev, int64_t n, int d, double ell, double sf2, double diag_add,
-                     void* k_dev, int64_t ldk, int lower_only, void* stream)
+                     void* k_dev, int64_t ldk, int lower_only, void* stream, bool lin_entry = false, const double* lin_dev = nullptr)
 {
     CIMRGP_REQUIRE(x_dev && k_dev, fn, "null pointer");
+    CIMRGP_REQUIRE(!lin_entry || lin_dev, fn, "null pointer (lin)");
     CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
     CIMRGP_REQUIRE(n >= 0, fn, "negative size");
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         return rbf_gram_run<T>((const T*)x_dev, n, (const T*)x_dev, n, d, ell, sf2, diag_add, (T*)k_dev, ldk, true, lower_only != 0,
-                               stream_of(stream), cov, fn);
+                               stream_of(stream), cov, fn, lin_dev);
     });
 }
 
 static int cross_impl(const char* fn, int dtype, int cov, const void* xa_dev, int64_t na, const void* xb_dev, int64_t nb, int d,
-                      double ell, double sf2, void* kab_dev, int64_t ld, void* stream)
+                      double ell, double sf2, void* kab_dev, int64_t ld, void* stream, bool lin_entry = false,
+                      const double* lin_dev = nullptr)
 {
     CIMRGP_REQUIRE(xa_dev && xb_dev && kab_dev, fn, "null pointer");
+    CIMRGP_REQUIRE(!lin_entry || lin_dev, fn, "null pointer (lin)");
     CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
     CIMRGP_REQUIRE(na >= 0 && nb >= 0, fn, "negative size");
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         return rbf_gram_run<T>((const T*)xa_dev, na, (const T*)xb_dev, nb, d, ell, sf2, 0.0, (T*)kab_dev, ld, false, false,
-                               stream_of(stream), cov, fn);
+                               stream_of(stream), cov, fn, lin_dev);
     });
 }
 
@@ -223,6 +227,18 @@ int cimrgp_cov_cross(int dtype, int cov, const void* xa_dev, int64_t na, const v
                      double sf2, void* kab_dev, int64_t ld, void* stream)
 {
     return cross_impl("cimrgp_cov_cross", dtype, cov, xa_dev, na, xb_dev, nb, d, ell, sf2, kab_dev, ld, stream);
+}
+
+int cimrgp_cov_gram_lin(int dtype, int cov, const void* x_dev, int64_t n, int d, double ell, double sf2, const double* lin_dev,
+                        double diag_add, void* k_dev, int64_t ldk, int lower_only, void* stream)
+{
+    return gram_impl("cimrgp_cov_gram_lin", dtype, cov, x_dev, n, d, ell, sf2, diag_add, k_dev, ldk, lower_only, stream, true, lin_dev);
+}
+
+int cimrgp_cov_cross_lin(int dtype, int cov, const void* xa_dev, int64_t na, const void* xb_dev, int64_t nb, int d, double ell,
+                         double sf2, const double* lin_dev, void* kab_dev, int64_t ld, void* stream)
+{
+    return cross_impl("cimrgp_cov_cross_lin", dtype, cov, xa_dev, na, xb_dev, nb, d, ell, sf2, kab_dev, ld, stream, true, lin_dev);
 }
 
 size_t cimrgp_potrf_workspace_bytes(int dtype, int64_t n)

@@ -364,10 +364,10 @@ template <> struct Cov<CIMRGP_COV_MATERN32> : MaternCov<CIMRGP_COV_MATERN32> {};
 template <> struct Cov<CIMRGP_COV_MATERN52> : MaternCov<CIMRGP_COV_MATERN52> {};
 
 // gram.hip.  cov: CIMRGP_COV_* (validated by the caller); fn: the entry point named in error messages (NULL: the RBF
-// entry point's name)
+// entry point's name); lin: d FP64 weights on the device, every element gets + sum_e lin[e] xa_ie xb_je (nullptr: no such term)
 template <typename T> int rbf_gram_run(const T* xa, int64_t na, const T* xb, int64_t nb, int d, double ell, double sf2,
                                        double diag_add, T* k, int64_t ld, bool symm, bool lower_only, hipStream_t st,
-                                       int cov = CIMRGP_COV_RBF, const char* fn = nullptr);
+                                       int cov = CIMRGP_COV_RBF, const char* fn = nullptr, const double* lin = nullptr);
 // K_b = k(rows_b, cols_b) for every block b into arena k; symm: rows == cols, the lower tiles, + diag_dev[b] on the diagonal
 template <typename T> int rbf_gram_batched_run(const BatchCov& bc, const Points<T>& rows, const Points<T>& cols, const T* diag_dev,
                                                const Arena<T>& k, bool symm, hipStream_t st);

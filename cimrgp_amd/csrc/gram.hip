@@ -1,6 +1,6 @@
 // D1: tiled Gram / cross-Gram builder and D4: fused predictive mean.  One kernel template per operation, every one
 // with the covariance policy COV of common.hpp (CIMRGP_COV_*: RBF = 0, Matern 1/2, 3/2, 5/2) as a parameter:
-// k_gram<T, COV, SYMM, D>, k_gram_lower_wide<T, COV, D>, k_gram_batched<T, COV, SYMM, D>, k_predict_mean<T, COV, D, Q>.
+// k_gram<T, COV, SYMM, D> (and k_gram_lin, its arm with a linear term), k_gram_lower_wide<T, COV, D>, k_gram_batched<T, COV, SYMM, D>, k_predict_mean<T, COV, D, Q>.
 //
 // Gram: one workgroup = one 64 x 64 tile; the row and column input tiles are
 // staged in LDS once; each thread produces a 4 x 4 patch whose 4 columns are
@@ -25,9 +25,14 @@ constexpr int GTILE = 64;
 // 512-byte runs (WIDTH = 64: 2 rows x 32 lanes in FP64, 4 rows x 16 lanes in FP32).  (Rounds 1-2: 4 adjacent columns =
 // 32 bytes per lane in two instructions, each of which wrote every other 16 bytes of its run: 3.5 TB/s with
 // the exponential taken out, against 5.8 TB/s for a plain fill of the same bytes.)
-template <typename T, int COV, bool SYMM, int D, int WIDTH, bool SKIP>
+//
+// LIN (include/cimrgp_sparse_linear.h): every element gets + sum_e lin[e] xa_ie xb_je.  The lane keeps lin[e] xb_je of its
+// EPL columns beside xc, rounded to the dtype once; an element costs d more multiply-adds in the dtype.  Nothing else
+// changes: the store layout is the one above.
+template <typename T, int COV, bool SYMM, int D, int WIDTH, bool SKIP, bool LIN = false>
 static __device__ __forceinline__ void gram_lanes(const T* sa, const T* sb, int row0, int col0, int na, int nb, int d,
-                                                   T c, T sf2, T diag_add, T* __restrict__ K, int64_t ld)
+                                                   T c, T sf2, T diag_add, T* __restrict__ K, int64_t ld,
+                                                   const double* __restrict__ lin = nullptr)
 {
     constexpr int EPL = 16 / (int)sizeof(T);    // elements per lane and row
     constexpr int LPR = WIDTH / EPL;            // lanes per tile row
@@ -44,6 +49,15 @@ static __device__ __forceinline__ void gram_lanes(const T* sa, const T* sb, int 
     for (int b = 0; b < EPL; ++b)
 #pragma unroll
         for (int k = 0; k < DD; ++k) xc[b][k] = sb[(cx + b) * MAXD + k];
+    T xl[LIN ? EPL : 1][LIN ? DD : 1];
+    if constexpr (LIN) {
+#pragma unroll
+        for (int k = 0; k < DD; ++k) {
+            const T w = (D || k < d) ? (T)lin[k] : (T)0;
+#pragma unroll
+            for (int b = 0; b < EPL; ++b) xl[b][k] = w * xc[b][k];
+        }
+    }
 
 #pragma unroll
     for (int a = 0; a < NIT; ++a) {
@@ -64,6 +78,13 @@ static __device__ __forceinline__ void gram_lanes(const T* sa, const T* sb, int 
                 }
             }
             T v = Cov<COV>::template value<T, D>(d2, df0, c, sf2);
+            if constexpr (LIN) {
+                T dot = (T)0;
+#pragma unroll
+                for (int k = 0; k < DD; ++k)
+                    if (D || k < d) dot += sa[r * MAXD + k] * xl[b][k];
+                v += dot;
+            }
             if (SYMM && (gr == gc + b)) v += diag_add;
             out[b] = v;
         }
@@ -84,10 +105,10 @@ static __device__ __forceinline__ void gram_lanes(const T* sa, const T* sb, int 
 }
 
 // One 64 x 64 tile of k(xa, xb): tile blockIdx.x of the tiles_n per tile row, or (SYMM, lower_only) of the lower triangle
-template <typename T, int COV, bool SYMM, int D>
+template <typename T, int COV, bool SYMM, int D, bool LIN = false>
 static __device__ __forceinline__ void gram_tile(const T* __restrict__ xa, int na, const T* __restrict__ xb, int nb, int d,
                                                   T c, T sf2, T diag_add, T* __restrict__ K, int64_t ld,
-                                                  int tiles_n, int lower_only)
+                                                  int tiles_n, int lower_only, const double* __restrict__ lin = nullptr)
 {
     __shared__ T sa[GTILE * MAXD];
     __shared__ T sb[GTILE * MAXD];
@@ -105,7 +126,7 @@ static __device__ __forceinline__ void gram_tile(const T* __restrict__ xa, int n
         sb[e] = (k < d && col0 + r < nb) ? xb[(int64_t)(col0 + r) * d + k] : (T)0;
     }
     __syncthreads();
-    gram_lanes<T, COV, SYMM, D, GTILE, false>(sa, sb, row0, col0, na, nb, d, c, sf2, diag_add, K, ld);
+    gram_lanes<T, COV, SYMM, D, GTILE, false, LIN>(sa, sb, row0, col0, na, nb, d, c, sf2, diag_add, K, ld, lin);
 }
 
 template <typename T, int COV, bool SYMM, int D>
@@ -114,6 +135,15 @@ void k_gram(const T* __restrict__ xa, int na, const T* __restrict__ xb, int nb, 
             T c, T sf2, T diag_add, T* __restrict__ K, int64_t ld, int tiles_n, int lower_only)
 {
     gram_tile<T, COV, SYMM, D>(xa, na, xb, nb, d, c, sf2, diag_add, K, ld, tiles_n, lower_only);
+}
+
+// The LIN arm of k_gram: lin = d FP64 weights on the device (both dtypes).
+template <typename T, int COV, bool SYMM, int D>
+__global__ __launch_bounds__(256)
+void k_gram_lin(const T* __restrict__ xa, int na, const T* __restrict__ xb, int nb, int d,
+                T c, T sf2, T diag_add, T* __restrict__ K, int64_t ld, int tiles_n, int lower_only, const double* __restrict__ lin)
+{
+    gram_tile<T, COV, SYMM, D, true>(xa, na, xb, nb, d, c, sf2, diag_add, K, ld, tiles_n, lower_only, lin);
 }
 
 // The lower triangle of a symmetric Gram matrix in 64 x 128 tiles (round 5): a tile row is 128 columns = 1 KB in FP64, so
@@ -219,7 +249,7 @@ void k_predict_mean(const T* __restrict__ x, int n, int d, const T* __restrict__
 
 template <typename T, int COV>
 static int gram_run_cov(const T* xa, int64_t na, const T* xb, int64_t nb, int d, double ell, double sf2,
-                        double diag_add, T* k, int64_t ld, bool symm, bool lower_only, hipStream_t st, const char* fn)
+                        double diag_add, T* k, int64_t ld, bool symm, bool lower_only, hipStream_t st, const char* fn, const double* lin)
 {
     if (na <= 0 || nb <= 0) return 0;
     CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
@@ -228,14 +258,18 @@ static int gram_run_cov(const T* xa, int64_t na, const T* xb, int64_t nb, int d,
     CIMRGP_REQUIRE(na < (1ll << 30) && nb < (1ll << 30), fn, "matrix too large");
     const int64_t tm = (na + GTILE - 1) / GTILE, tn = (nb + GTILE - 1) / GTILE;
     const T c = (T)cov_scale(COV, ell);
-    // the 64 x 64 tiles
+    // the 64 x 64 tiles; with the linear term (lin != nullptr) the only form: K_uu is m x m
     auto launch = [&](auto symm_, int64_t tiles, double diag, int lo) {
         with_dim(d, [&](auto dd) {
-            hipLaunchKernelGGL((k_gram<T, COV, decltype(symm_)::value, decltype(dd)::value>), dim3((unsigned)tiles), dim3(256), 0, st,
-                               xa, (int)na, xb, (int)nb, d, c, (T)sf2, (T)diag, k, ld, (int)tn, lo);
+            if (lin)
+                hipLaunchKernelGGL((k_gram_lin<T, COV, decltype(symm_)::value, decltype(dd)::value>), dim3((unsigned)tiles), dim3(256), 0,
+                                   st, xa, (int)na, xb, (int)nb, d, c, (T)sf2, (T)diag, k, ld, (int)tn, lo, lin);
+            else
+                hipLaunchKernelGGL((k_gram<T, COV, decltype(symm_)::value, decltype(dd)::value>), dim3((unsigned)tiles), dim3(256), 0, st,
+                                   xa, (int)na, xb, (int)nb, d, c, (T)sf2, (T)diag, k, ld, (int)tn, lo);
         });
     };
-    if (symm && lower_only && na == nb && xa == xb) {
+    if (symm && lower_only && na == nb && xa == xb && !lin) {
         // the lower triangle in 64 x 128 tiles: pairs of tile rows, P (P + 1) tiles in the full pairs (+ P + 1 for an odd last row)
         const int64_t pairs = tm / 2;
         const int64_t tiles = pairs * (pairs + 1) + ((tm & 1) ? pairs + 1 : 0);
@@ -259,11 +293,11 @@ static int gram_run_cov(const T* xa, int64_t na, const T* xb, int64_t nb, int d,
 
 template <typename T>
 int rbf_gram_run(const T* xa, int64_t na, const T* xb, int64_t nb, int d, double ell, double sf2,
-                 double diag_add, T* k, int64_t ld, bool symm, bool lower_only, hipStream_t st, int cov, const char* fn)
+                 double diag_add, T* k, int64_t ld, bool symm, bool lower_only, hipStream_t st, int cov, const char* fn, const double* lin)
 {
     if (!fn) fn = symm ? "cimrgp_rbf_gram" : "cimrgp_rbf_cross";
     return with_cov(cov, [&](auto c) {
-        return gram_run_cov<T, decltype(c)::value>(xa, na, xb, nb, d, ell, sf2, diag_add, k, ld, symm, lower_only, st, fn);
+        return gram_run_cov<T, decltype(c)::value>(xa, na, xb, nb, d, ell, sf2, diag_add, k, ld, symm, lower_only, st, fn, lin);
     });
 }
 
@@ -333,9 +367,9 @@ int predict_mean_run(const T* x, int64_t n, int d, const T* alpha, int q, const 
 }
 
 template int rbf_gram_run<double>(const double*, int64_t, const double*, int64_t, int, double, double, double,
-                                  double*, int64_t, bool, bool, hipStream_t, int, const char*);
+                                  double*, int64_t, bool, bool, hipStream_t, int, const char*, const double*);
 template int rbf_gram_run<float>(const float*, int64_t, const float*, int64_t, int, double, double, double,
-                                 float*, int64_t, bool, bool, hipStream_t, int, const char*);
+                                 float*, int64_t, bool, bool, hipStream_t, int, const char*, const double*);
 template int rbf_gram_batched_run<double>(const BatchCov&, const Points<double>&, const Points<double>&, const double*,
                                           const Arena<double>&, bool, hipStream_t);
 template int rbf_gram_batched_run<float>(const BatchCov&, const Points<float>&, const Points<float>&, const float*,

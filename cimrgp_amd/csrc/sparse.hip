@@ -1,5 +1,6 @@
 // Inducing-point (sparse) GP regression: the three calls of include/cimrgp_sparse.h and their two twins of
-// include/cimrgp_sparse_layer.h, which read the noise, a bias and an extra variance from the device (same kernel bodies).
+// include/cimrgp_sparse_layer.h, which read the noise, a bias and an extra variance from the device (same kernel bodies),
+// and cimrgp_sparse_lambda_kd of include/cimrgp_sparse_linear.h, which reads k(x_i, x_i) per row (same body again).
 //   wsyrk_tn       lower(C) = diag_add I + A^T diag(w) A and g = A^T diag(w) r for A (n x m, row-major), n >> m:
 //                    k_wsyrk_tn       one 128 x 128 output tile and one slice of K = n per workgroup, on the matrix cores
 //                                     (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32, Mx<T> in common.hpp); the partial
@@ -287,10 +288,11 @@ void k_wsyrk_reduce(const T* __restrict__ cpart, const T* __restrict__ gpart, in
 // A wave per row (wave_row, reduce.hpp): lane l adds the squares of columns l, l + 64, .. in FP64, then the 64 partial
 // sums are added pairwise (wave_sum: xor 32, 16, .. 1): a fixed order.  lam <- lambda_i, dtmp <- sf2 - q_i
 // (k_sparse_sums turns it into w).  noise_dev != nullptr: the noise is that element on the device, not the argument.
+// kdiag != nullptr (cimrgp_sparse_lambda_kd): k(x_i, x_i) is kdiag[i], not the constant sf2.
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_sparse_rowsq(const T* __restrict__ A, int64_t lda, int n, int m, double sf2, double noise, const T* __restrict__ noise_dev,
-                    int mode, T* __restrict__ lam, T* __restrict__ dtmp)
+                    const T* __restrict__ kdiag, int mode, T* __restrict__ lam, T* __restrict__ dtmp)
 {
     int row, lane;
     if (!wave_row(n, row, lane)) return;
@@ -303,7 +305,7 @@ void k_sparse_rowsq(const T* __restrict__ A, int64_t lda, int n, int m, double s
     wave_sum(s);
     if (lane == 0) {
         if (noise_dev) noise = (double)noise_dev[0];
-        const double d = sf2 - s;
+        const double d = (kdiag ? (double)kdiag[row] : sf2) - s;
         lam[row] = (T)(mode == 0 ? d + noise : noise);
         dtmp[row] = (T)d;
     }
@@ -428,18 +430,21 @@ int cimrgp_wsyrk_tn(int dtype, const void* a_dev, int64_t n, int64_t m, int64_t 
 }
 
 // cimrgp_sparse_lambda and cimrgp_sparse_lambda_dev: `dev_entry` says which; the first takes `noise`, the second noise_dev.
+// cimrgp_sparse_lambda_kd (include/cimrgp_sparse_linear.h): `kd_entry`, with kdiag_dev in place of sf2.
 static int sparse_lambda_impl(const char* fn, bool dev_entry, int dtype, const void* a_dev, int64_t n, int64_t m, int64_t lda, double sf2,
-                              double noise, const void* noise_dev, int mode, void* lam_dev, void* w_dev, double* sums_dev, void* stream)
+                              double noise, const void* noise_dev, int mode, void* lam_dev, void* w_dev, double* sums_dev, void* stream,
+                              bool kd_entry = false, const void* kdiag_dev = nullptr)
 {
     CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(a_dev && lam_dev && w_dev && sums_dev, fn, "null pointer");
     CIMRGP_REQUIRE(!dev_entry || noise_dev, fn, "null pointer (noise)");
+    CIMRGP_REQUIRE(!kd_entry || kdiag_dev, fn, "null pointer (kdiag)");
     CIMRGP_REQUIRE(n >= 1 && n < (1ll << 31) && m >= 1 && m < (1ll << 31) && lda >= m, fn, "bad dimensions");
     CIMRGP_REQUIRE(mode == 0 || mode == 1, fn, "mode must be 0 (FITC) or 1 (VFE)");
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         hipLaunchKernelGGL((k_sparse_rowsq<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream_of(stream), (const T*)a_dev, lda, (int)n,
-                           (int)m, sf2, noise, (const T*)noise_dev, mode, (T*)lam_dev, (T*)w_dev);
+                           (int)m, sf2, noise, (const T*)noise_dev, (const T*)kdiag_dev, mode, (T*)lam_dev, (T*)w_dev);
         CIMRGP_LAUNCH_CHECK(fn);
         hipLaunchKernelGGL((k_sparse_sums<T>), dim3(1), dim3(1024), 0, stream_of(stream), (const T*)lam_dev, (T*)w_dev, (int)n, sums_dev);
         CIMRGP_LAUNCH_CHECK(fn);
@@ -481,6 +486,13 @@ int cimrgp_sparse_lambda_dev(int dtype, const void* a_dev, int64_t n, int64_t m,
 {
     return sparse_lambda_impl("cimrgp_sparse_lambda_dev", true, dtype, a_dev, n, m, lda, sf2, 0.0, noise_dev, mode, lam_dev, w_dev,
                               sums_dev, stream);
+}
+
+int cimrgp_sparse_lambda_kd(int dtype, const void* a_dev, int64_t n, int64_t m, int64_t lda, const void* kdiag_dev, double noise, int mode,
+                            void* lam_dev, void* w_dev, double* sums_dev, void* stream)
+{
+    return sparse_lambda_impl("cimrgp_sparse_lambda_kd", false, dtype, a_dev, n, m, lda, 0.0, noise, nullptr, mode, lam_dev, w_dev, sums_dev,
+                              stream, true, kdiag_dev);
 }
 
 int cimrgp_sparse_tail(int dtype, const void* astar_dev, const void* wstar_dev, int64_t ns, int64_t m, int64_t lda,

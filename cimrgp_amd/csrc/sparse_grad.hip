@@ -1,5 +1,5 @@
-// Gradients of the sparse (inducing-point) objective: the three calls of include/cimrgp_sparse_grad.h and the ARD twin of
-// the first (include/cimrgp_sparse_ard.h).
+// Gradients of the sparse (inducing-point) objective: the three calls of include/cimrgp_sparse_grad.h, the ARD twin of the
+// first (include/cimrgp_sparse_ard.h) and its twin with a linear term (include/cimrgp_sparse_linear.h).
 //   cov_pair_grad        k_cov_pair_grad    one tile of 128 columns of G and one slice of its rows per workgroup: k, g and
 //                                           dk/dlog l recomputed per pair, the products with G and every sum in FP64;
 //                                           the partial db and the two partial scalar sums go to scratch
@@ -20,6 +20,10 @@
 // The ARD arm keeps d more FP64 sums per lane, sum G g df_e^2 (= sum G dk/dlog l_e at equal length-scales), in place of
 // sum G dk/dlog l: the product wg df_e that db adds is multiplied by df_e once more.  k, g and db are the same
 // instructions in both arms.
+// The LIN arm (cimrgp_cov_pair_grad_lin, include/cimrgp_sparse_linear.h: k = k_cov + sum_e lin_e a_e b_e) keeps EPL x d more
+// FP64 sums per lane, P_je = sum_i G_ij xa_ie, filled from the same single read of G; their partials go to scratch beside
+// the partial db, and the LIN arm of the reduce kernel folds them into db (lin_e P_je) and into lsums (sum_j xb_je P_je).
+// k, g, the scalar sums and the covariance part of db are the same instructions as without it.
 #include "abi.hpp"
 #include "reduce.hpp"
 
@@ -55,10 +59,16 @@ static inline int pg_nsums(int d, bool ard) { return ard ? 1 + d : 2; }
 // k, g (dk/da_e = -g (a_e - b_e)) and dk/dlog l of one pair: the policy's pair() (common.hpp), in the dtype.
 // blockIdx.x = tile + tiles * slice.  A workgroup's scalar sums: [sum G k, sum G dk/dlog l], or with ARD
 // [sum G k, sum G g df_0^2, .., sum G g df_{d-1}^2].
-template <typename T, int COV, int D, bool ARD>
+// The LIN arm's two more arguments: want_p says whether the partial P (ppart, laid out as dbpart) is written.  Without the
+// arm the struct is empty, and the kernel is the one it was before the arm existed, instruction for instruction.
+template <bool LIN> struct PairLin {};
+template <> struct PairLin<true> { int want_p; double* ppart; };
+
+template <typename T, int COV, int D, bool ARD, bool LIN = false>
 __global__ __launch_bounds__(256)
 void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb, int nb, int d, const T* __restrict__ G, int64_t ldg,
-                     T c, T sf2, int tiles, int slice_len, int want_db, double* __restrict__ dbpart, double* __restrict__ sumpart)
+                     T c, T sf2, int tiles, int slice_len, int want_db, double* __restrict__ dbpart, double* __restrict__ sumpart,
+                     PairLin<LIN> pl)
 {
     constexpr int EPL = 16 / (int)sizeof(T);    // elements per lane and row
     constexpr int LPR = PG_CT / EPL;            // lanes per tile row
@@ -104,6 +114,13 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
         for (int k = 0; k < DD; ++k) acc[b][k] = 0.0;
 #pragma unroll
     for (int k = 0; k < DD; ++k) sd[k] = 0.0;
+    double pacc[LIN ? EPL : 1][LIN ? DD : 1];           // LIN: sum_i G_ij xa_ie
+    if constexpr (LIN) {
+#pragma unroll
+        for (int b = 0; b < EPL; ++b)
+#pragma unroll
+            for (int k = 0; k < DD; ++k) pacc[b][k] = 0.0;
+    }
 
     T gcur[EPL], xcur[DD], gnext[EPL], xnext[DD];
     int i = r0 + phase;
@@ -129,6 +146,7 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
             for (int k = 0; k < DD; ++k) {
                 acc[b][k] += wg * (double)df[k];
                 if constexpr (ARD) sd[k] += (wg * (double)df[k]) * (double)df[k];
+                if constexpr (LIN) pacc[b][k] += w * (double)xcur[k];
             }
         }
         if (more) {
@@ -153,6 +171,26 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
     __syncthreads();
     const int ns = ARD ? 1 + d : 2;             // the sums of the dimensions >= d (all 0) are not written
     if (tid < ns) sumpart[(int64_t)blockIdx.x * ns + tid] = sum4(sred[0][tid], sred[1][tid], sred[2][tid], sred[3][tid]);
+    if constexpr (LIN) {
+        // P: the same phase-order sum as db below, into ppart
+        if (pl.want_p) {
+            double* pout = pl.ppart + (int64_t)blockIdx.x * PG_CT * d;
+#pragma unroll
+            for (int k = 0; k < DD; ++k) {
+                if (!(D || k < d)) break;
+#pragma unroll
+                for (int b = 0; b < EPL; ++b) red[phase * PG_CT + cx + b] = pacc[b][k];
+                __syncthreads();
+                if (tid < PG_CT) {
+                    double s = red[tid];
+#pragma unroll
+                    for (int p = 1; p < NPH; ++p) s += red[p * PG_CT + tid];
+                    pout[tid * d + k] = s;
+                }
+                __syncthreads();
+            }
+        }
+    }
     if (!want_db) return;
     // db: per dimension, the NPH row phases of a column are added in phase order
     double* out = dbpart + (int64_t)blockIdx.x * PG_CT * d;
@@ -175,10 +213,17 @@ void k_cov_pair_grad(const T* __restrict__ xa, int na, const T* __restrict__ xb,
 // blockIdx.x < dblocks: 256 elements of db, each the sum of its S partials in slice order; workgroup dblocks + c (sums
 // wanted, c < nsums): thread t adds the partials t, t + 256, .. of scalar sum c (tile-major within a slice), then the 256
 // partial sums are added pairwise in LDS (lds_tree, reduce.hpp).
-template <typename T>
+// LIN: db gets scale (covariance part + lin_k P_jk), P_jk the sum of its S partials of ppart in slice order; workgroup
+// dblocks + nsums_wg + k (k < d, lsums wanted; nsums_wg = nsums or 0 as the scalar sums are wanted): thread t adds
+// xb_jk P_jk over j = t, t + 256, .., then lds_tree; lsums is not scaled.
+template <typename T, bool LIN> struct ReduceLin {};
+template <typename T> struct ReduceLin<T, true> { const double* ppart; const double* lin; const T* xb; int nsums_wg; double* lsums; };
+
+template <typename T, bool LIN = false>
 __global__ __launch_bounds__(256)
 void k_pair_grad_reduce(const double* __restrict__ dbpart, const double* __restrict__ sumpart, int nb, int d, int tiles, int slices,
-                        int dblocks, int nsums, double scale, int accumulate, T* __restrict__ db, double* __restrict__ sums)
+                        int dblocks, int nsums, double scale, int accumulate, T* __restrict__ db, double* __restrict__ sums,
+                        ReduceLin<T, LIN> rl)
 {
     const int tid = threadIdx.x;
     if ((int)blockIdx.x < dblocks) {
@@ -189,12 +234,35 @@ void k_pair_grad_reduce(const double* __restrict__ dbpart, const double* __restr
         const double* p = dbpart + ((int64_t)tile * PG_CT + jj) * d + k;
         double s = p[0];
         for (int sl = 1; sl < slices; ++sl) s += p[(int64_t)sl * tiles * PG_CT * d];
+        if constexpr (LIN) {
+            const double* pp = rl.ppart + ((int64_t)tile * PG_CT + jj) * d + k;
+            double ps = pp[0];
+            for (int sl = 1; sl < slices; ++sl) ps += pp[(int64_t)sl * tiles * PG_CT * d];
+            s += rl.lin[k] * ps;
+        }
         s *= scale;
         db[e] = accumulate ? (T)((double)db[e] + s) : (T)s;
         return;
     }
     __shared__ double red[256];
     const int c = (int)blockIdx.x - dblocks;
+    if constexpr (LIN) {
+        if (c >= rl.nsums_wg) {
+            const int k = c - rl.nsums_wg;
+            double s = 0.0;
+            for (int j = tid; j < nb; j += 256) {
+                const int tile = j / PG_CT, jj = j - tile * PG_CT;
+                const double* pp = rl.ppart + ((int64_t)tile * PG_CT + jj) * d + k;
+                double ps = pp[0];
+                for (int sl = 1; sl < slices; ++sl) ps += pp[(int64_t)sl * tiles * PG_CT * d];
+                s += (double)rl.xb[(int64_t)j * d + k] * ps;
+            }
+            red[tid] = s;
+            lds_tree<256>(red, tid);
+            if (tid == 0) rl.lsums[k] = accumulate ? rl.lsums[k] + red[0] : red[0];
+            return;
+        }
+    }
     const int64_t parts = (int64_t)tiles * slices;
     double s = 0.0;
     for (int64_t p = tid; p < parts; p += 256) s += sumpart[nsums * p + c];
@@ -299,14 +367,42 @@ static int pair_grad_run_cov(const T* xa, int64_t na, const T* xb, int64_t nb, i
     const T c = (T)cov_scale(COV, ell);
     with_dim(d, [&](auto dd) {
         hipLaunchKernelGGL((k_cov_pair_grad<T, COV, decltype(dd)::value, ARD>), grid, dim3(256), 0, st, xa, (int)na, xb, (int)nb, d, g, ldg,
-                           c, (T)sf2, (int)tiles, (int)len, db != nullptr ? 1 : 0, dbpart, sumpart);
+                           c, (T)sf2, (int)tiles, (int)len, db != nullptr ? 1 : 0, dbpart, sumpart, PairLin<false>());
     });
     CIMRGP_LAUNCH_CHECK(fn);
     const int64_t dblocks = db != nullptr ? (nb * d + 255) / 256 : 0;
     const int nsums = pg_nsums(d, ARD);
     hipLaunchKernelGGL((k_pair_grad_reduce<T>), dim3((unsigned)(dblocks + (sums != nullptr ? nsums : 0))), dim3(256), 0, st,
                        (const double*)dbpart, (const double*)sumpart, (int)nb, d, (int)tiles, (int)slices, (int)dblocks, nsums, scale,
-                       accumulate, db, sums);
+                       accumulate, db, sums, ReduceLin<T, false>());
+    CIMRGP_LAUNCH_CHECK(fn);
+    return 0;
+}
+
+// The LIN arm: ppart lies behind the twin's two arrays.
+template <typename T, int COV, bool ARD>
+static int pair_grad_lin_run_cov(const T* xa, int64_t na, const T* xb, int64_t nb, int d, const T* g, int64_t ldg, double ell, double sf2,
+                                 const double* lin, double scale, int accumulate, double* sums, double* lsums, T* db, double* scratch,
+                                 hipStream_t st, const char* fn)
+{
+    const int64_t tiles = pg_tiles(nb), len = pg_slice_len(na, nb), slices = pg_slices(na, nb);
+    const int nsums = pg_nsums(d, ARD);
+    double* dbpart = scratch;
+    double* sumpart = dbpart + pg_dbpart_elems(na, nb, d);
+    double* ppart = sumpart + pg_sumpart_elems(na, nb, nsums);
+    const dim3 grid((unsigned)(tiles * slices));
+    const T c = (T)cov_scale(COV, ell);
+    with_dim(d, [&](auto dd) {
+        hipLaunchKernelGGL((k_cov_pair_grad<T, COV, decltype(dd)::value, ARD, true>), grid, dim3(256), 0, st, xa, (int)na, xb, (int)nb, d,
+                           g, ldg, c, (T)sf2, (int)tiles, (int)len, db != nullptr ? 1 : 0, dbpart, sumpart,
+                           PairLin<true>{(db != nullptr || lsums != nullptr) ? 1 : 0, ppart});
+    });
+    CIMRGP_LAUNCH_CHECK(fn);
+    const int64_t dblocks = db != nullptr ? (nb * d + 255) / 256 : 0;
+    const int nsums_wg = sums != nullptr ? nsums : 0;
+    hipLaunchKernelGGL((k_pair_grad_reduce<T, true>), dim3((unsigned)(dblocks + nsums_wg + (lsums != nullptr ? d : 0))), dim3(256), 0, st,
+                       (const double*)dbpart, (const double*)sumpart, (int)nb, d, (int)tiles, (int)slices, (int)dblocks, nsums, scale,
+                       accumulate, db, sums, ReduceLin<T, true>{(const double*)ppart, lin, xb, nsums_wg, lsums});
     CIMRGP_LAUNCH_CHECK(fn);
     return 0;
 }
@@ -317,26 +413,41 @@ static size_t pair_grad_scratch_bytes(int64_t na, int64_t nb, int d, bool ard)
     return (size_t)(pg_dbpart_elems(na, nb, d) + pg_sumpart_elems(na, nb, pg_nsums(d, ard))) * sizeof(double);
 }
 
-// The entry point of both contractions: `ard` selects the arm (sums_dev: 2 or 1 + d doubles), fn names it in errors.
+static size_t pair_grad_lin_scratch_bytes(int64_t na, int64_t nb, int d, bool ard)
+{
+    if (!pg_sizes_ok(na, nb, d)) return 0;
+    return pair_grad_scratch_bytes(na, nb, d, ard) + (size_t)pg_dbpart_elems(na, nb, d) * sizeof(double);
+}
+
+// The entry point of the contractions: `ard` selects the arm (sums_dev: 2 or 1 + d doubles), fn names it in errors.
+// lin_entry: cimrgp_cov_pair_grad_lin, with its weights lin_dev (required) and lsums_dev (d doubles, may be NULL).
 static int pair_grad_entry(const char* fn, bool ard, int dtype, int cov, const void* xa_dev, int64_t na, const void* xb_dev, int64_t nb,
                            int d, const void* g_dev, int64_t ldg, double ell, double sf2, double scale, int accumulate, double* sums_dev,
-                           void* db_dev, void* scratch_dev, size_t scratch_bytes, void* stream)
+                           void* db_dev, void* scratch_dev, size_t scratch_bytes, void* stream, bool lin_entry = false,
+                           const double* lin_dev = nullptr, double* lsums_dev = nullptr)
 {
     CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(cov_known(cov), fn, "unknown covariance");
     CIMRGP_REQUIRE(xa_dev && xb_dev && g_dev && scratch_dev, fn, "null pointer");
+    CIMRGP_REQUIRE(!lin_entry || lin_dev, fn, "null pointer (lin)");
     CIMRGP_REQUIRE(na >= 1 && na <= CIMRGP_PAIR_GRAD_MAX_NA, fn, "na must be in [1, 16777216]");
     CIMRGP_REQUIRE(nb >= 1 && nb <= CIMRGP_PAIR_GRAD_MAX_NB, fn, "nb must be in [1, 1048576]");
     CIMRGP_REQUIRE(d >= 1 && d <= MAXD, fn, "input dimension must be in [1, 8]");
     CIMRGP_REQUIRE(ldg >= nb, fn, "leading dimension too small");
     CIMRGP_REQUIRE(ell > 0.0 && sf2 > 0.0, fn, "kernel parameters must be positive");
     CIMRGP_REQUIRE((reinterpret_cast<uintptr_t>(scratch_dev) & 7u) == 0, fn, "scratch must be 8-byte aligned");
-    CIMRGP_REQUIRE(scratch_bytes >= pair_grad_scratch_bytes(na, nb, d, ard), fn, "scratch too small");
-    if (sums_dev == nullptr && db_dev == nullptr) return 0;
+    CIMRGP_REQUIRE(scratch_bytes >= (lin_entry ? pair_grad_lin_scratch_bytes(na, nb, d, ard) : pair_grad_scratch_bytes(na, nb, d, ard)), fn,
+                   "scratch too small");
+    if (sums_dev == nullptr && db_dev == nullptr && lsums_dev == nullptr) return 0;
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
         return with_cov(cov, [&](auto cv) {
             constexpr int COV = decltype(cv)::value;
+            if (lin_entry) {
+                auto run = ard ? pair_grad_lin_run_cov<T, COV, true> : pair_grad_lin_run_cov<T, COV, false>;
+                return run((const T*)xa_dev, na, (const T*)xb_dev, nb, d, (const T*)g_dev, ldg, ell, sf2, lin_dev, scale, accumulate,
+                           sums_dev, lsums_dev, (T*)db_dev, (double*)scratch_dev, stream_of(stream), fn);
+            }
             auto run = ard ? pair_grad_run_cov<T, COV, true> : pair_grad_run_cov<T, COV, false>;
             return run((const T*)xa_dev, na, (const T*)xb_dev, nb, d, (const T*)g_dev, ldg, ell, sf2, scale, accumulate, sums_dev,
                        (T*)db_dev, (double*)scratch_dev, stream_of(stream), fn);
@@ -368,6 +479,19 @@ int cimrgp_cov_pair_grad_ard(int dtype, int cov, const void* xa_dev, int64_t na,
 {
     return pair_grad_entry("cimrgp_cov_pair_grad_ard", true, dtype, cov, xa_dev, na, xb_dev, nb, d, g_dev, ldg, ell, sf2, scale, accumulate,
                            sums_dev, db_dev, scratch_dev, scratch_bytes, stream);
+}
+
+size_t cimrgp_cov_pair_grad_lin_scratch_bytes(int64_t na, int64_t nb, int d, int ard)
+{
+    return pair_grad_lin_scratch_bytes(na, nb, d, ard != 0);
+}
+
+int cimrgp_cov_pair_grad_lin(int dtype, int cov, const void* xa_dev, int64_t na, const void* xb_dev, int64_t nb, int d, const void* g_dev,
+                             int64_t ldg, double ell, double sf2, int ard, const double* lin_dev, double scale, int accumulate,
+                             double* sums_dev, double* lsums_dev, void* db_dev, void* scratch_dev, size_t scratch_bytes, void* stream)
+{
+    return pair_grad_entry("cimrgp_cov_pair_grad_lin", ard != 0, dtype, cov, xa_dev, na, xb_dev, nb, d, g_dev, ldg, ell, sf2, scale,
+                           accumulate, sums_dev, db_dev, scratch_dev, scratch_bytes, stream, true, lin_dev, lsums_dev);
 }
 
 int cimrgp_sparse_grad_rows(int dtype, const void* v_dev, int64_t n, int64_t m, int64_t ldv, const void* gamma_dev, const void* r_dev,

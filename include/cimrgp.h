@@ -502,4 +502,8 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
  * include/cimrgp_sparse_post.h. */
 #include "cimrgp_sparse_post.h"
 
+/* The sparse GP with a linear term added to its covariance (k(x, x) is then not the constant sf2): the Gram, lambda and
+ * pair-contraction twins: include/cimrgp_sparse_linear.h. */
+#include "cimrgp_sparse_linear.h"
+
 #endif /* CIMRGP_H */
