@@ -5,7 +5,7 @@ protocol of the reference's ``MaternKernel`` (KernelClass.py:40-65: attributes
 ``l``, ``sf``; methods ``kernel``, ``log_kernel``, ``spectral``,
 ``log_spectral``, ``estimate_kernel``) so that it can be passed as
 ``spectral_density_obj`` (scalar or per-layer list, MRGP.py:71-79), and adds
-the Gram builder that runs on the GPU.  ``DenseMaternKernel`` is its Matern twin for
+the Gram builder that runs on the GPU (``DeviceGram``, shared).  ``DenseMaternKernel`` is its Matern twin for
 half-integer nu (1/2, 3/2, 5/2) in closed form: the prior that the reduced-rank
 model approximates, on the same dense path.  ``MaternKernel`` and
 ``LaplacianEigenpairs`` are host-side restatements of the reference's
@@ -55,7 +55,32 @@ def _unit_inputs(kernel, x, x2):
     return xs, None if x2 is None else scaled(x2, scale), 1.0
 
 
-class RBFKernel(object):
+class DeviceGram(object):
+    """The dense Gram builder (device, HIP) of a covariance class with ``l``, ``sf``, ``ard`` and ``cov``, its covariance
+    id of the C ABI: :class:`RBFKernel`'s and :class:`DenseMaternKernel`'s."""
+
+    def gram(self, x, x2=None, diag_add=0.0, lower_only=False):
+        """Gram matrix on the GPU (k_gram).  ``x``/``x2``: CUDA tensors (n x d).  Returns a
+        torch view (n x n2) of the padded device buffer."""
+        from . import device as dev
+        x, x2, l = _unit_inputs(self, x, x2)
+        if x2 is None:
+            buf = dev.rbf_gram(x, l, self.sf, diag_add, lower_only, cov=self.cov)
+            return buf[:x.shape[0], :x.shape[0]]
+        buf = dev.rbf_cross(x, x2, l, self.sf, cov=self.cov)
+        return buf[:x.shape[0], :x2.shape[0]]
+
+    def K(self, x, x2=None, dtype='f64'):
+        """NumPy in / NumPy out convenience around :meth:`gram` (computed on the GPU)."""
+        from . import device as dev
+        device = dev.require_gpu()
+        tdt = dev.as_torch_dtype(dtype)
+        xd = dev.to_device(np.atleast_2d(x), tdt, device)
+        x2d = None if x2 is None else dev.to_device(np.atleast_2d(x2), tdt, device)
+        return self.gram(xd, x2d).cpu().numpy()
+
+
+class RBFKernel(DeviceGram):
     """k(r) = sf * exp(-r^2 / (2 l^2));  ``sf`` is the signal VARIANCE, as the
     reference's kernels multiply by ``sf`` directly (KernelClass.py:77).
     ``noise``: fixed Gaussian noise variance of the blocks using this kernel,
@@ -105,27 +130,6 @@ class RBFKernel(object):
         """Reduced-rank reconstruction sum_p S(sqrt(lambda_p)) phi_p(x) phi_p(x')."""
         weights = self.spectral(np.sqrt(np.asarray(lambdas, dtype=np.float64)))
         return np.einsum('np,np,p->n', phi_x1, phi_x2, weights)
-
-    # ---- dense Gram builder (device, HIP) ---------------------------------
-    def gram(self, x, x2=None, diag_add=0.0, lower_only=False):
-        """Gram matrix on the GPU.  ``x``/``x2``: CUDA tensors (n x d).  Returns a
-        torch view (n x n2) of the padded device buffer."""
-        from . import device as dev
-        x, x2, l = _unit_inputs(self, x, x2)
-        if x2 is None:
-            buf = dev.rbf_gram(x, l, self.sf, diag_add, lower_only)
-            return buf[:x.shape[0], :x.shape[0]]
-        buf = dev.rbf_cross(x, x2, l, self.sf)
-        return buf[:x.shape[0], :x2.shape[0]]
-
-    def K(self, x, x2=None, dtype='f64'):
-        """NumPy in / NumPy out convenience around :meth:`gram` (computed on the GPU)."""
-        from . import device as dev
-        device = dev.require_gpu()
-        tdt = dev.as_torch_dtype(dtype)
-        xd = dev.to_device(np.atleast_2d(x), tdt, device)
-        x2d = None if x2 is None else dev.to_device(np.atleast_2d(x2), tdt, device)
-        return self.gram(xd, x2d).cpu().numpy()
 
 
 class LaplacianEigenpairs(object):
@@ -186,7 +190,7 @@ class MaternKernel(object):
         return np.einsum('np,np,p->n', phi_x1, phi_x2, weights)
 
 
-class DenseMaternKernel(object):
+class DenseMaternKernel(DeviceGram):
     """Matern covariance of half-integer smoothness on the dense path, in closed form with
     t = sqrt(2 nu) r / l:
         nu = 1/2:  sf exp(-t)                  (the exponential covariance)
@@ -250,27 +254,6 @@ class DenseMaternKernel(object):
     def estimate_kernel(self, phi_x1, phi_x2, lambdas):
         """Reduced-rank reconstruction sum_p S(sqrt(lambda_p)) phi_p(x) phi_p(x')."""
         return self._matern().estimate_kernel(phi_x1, phi_x2, lambdas)
-
-    # ---- dense Gram builder (device, HIP) ---------------------------------
-    def gram(self, x, x2=None, diag_add=0.0, lower_only=False):
-        """Gram matrix on the GPU (k_gram).  ``x``/``x2``: CUDA tensors (n x d).  Returns a
-        torch view (n x n2) of the padded device buffer."""
-        from . import device as dev
-        x, x2, l = _unit_inputs(self, x, x2)
-        if x2 is None:
-            buf = dev.rbf_gram(x, l, self.sf, diag_add, lower_only, cov=self.cov)
-            return buf[:x.shape[0], :x.shape[0]]
-        buf = dev.rbf_cross(x, x2, l, self.sf, cov=self.cov)
-        return buf[:x.shape[0], :x2.shape[0]]
-
-    def K(self, x, x2=None, dtype='f64'):
-        """NumPy in / NumPy out convenience around :meth:`gram` (computed on the GPU)."""
-        from . import device as dev
-        device = dev.require_gpu()
-        tdt = dev.as_torch_dtype(dtype)
-        xd = dev.to_device(np.atleast_2d(x), tdt, device)
-        x2d = None if x2 is None else dev.to_device(np.atleast_2d(x2), tdt, device)
-        return self.gram(xd, x2d).cpu().numpy()
 
 
 class SparseKernel(object):

@@ -3,29 +3,39 @@
 With n training inputs X, m inducing inputs Z, covariance k (length-scale l, variance sf), noise s2 and relative jitter eps:
 
     K_uu + eps sf I = L_u L_u^T              A = K(X, Z) L_u^-T   (n x m)
-    q_i = sum_j A_ij^2                       lambda_i = sf - q_i + s2 (FITC)  |  s2 (VFE)
+    q_i = sum_j A_ij^2                       lambda_i = k(x_i, x_i) - q_i + s2 (FITC)  |  s2 (VFE)
     B = I + A^T Lambda^-1 A = L_B L_B^T      c = A^T Lambda^-1 r,  gamma = L_B^-1 c   (m x q)
     LML = -1/2 n q log 2 pi - 1/2 q sum log lambda_i - q sum log (L_B)_ii - 1/2 sum r_ic^2 / lambda_i + 1/2 |gamma|_F^2
-          - 1/2 q sum_i (sf - q_i) / s2      (VFE only: Titsias' trace term)
-    A* = K(X*, Z) L_u^-T,  W* = A* L_B^-T    mean* = W* gamma,  var* = sf - sum A*^2 + sum W*^2  (+ s2 with include_noise)
+          - 1/2 q sum_i (k(x_i, x_i) - q_i) / s2      (VFE only: Titsias' trace term)
+    A* = K(X*, Z) L_u^-T,  W* = A* L_B^-T    mean* = W* gamma,  var* = k(x*, x*) - sum A*^2 + sum W*^2  (+ s2 with include_noise)
 
-Cost n m^2 flop and n m memory, against n^3 / 3 and n^2 of an exact block.  Every step is a call of the C ABI:
-cimrgp_cov_gram, cimrgp_potrf, cimrgp_cov_cross, cimrgp_trsm_rows, cimrgp_sparse_lambda, cimrgp_wsyrk_tn, cimrgp_potrs,
-cimrgp_logdet_half and cimrgp_sparse_tail.  torch holds the buffers and adds up the two O(n q) scalars of the LML.
-``SparseBlock.lml_grad`` adds the analytic gradient w.r.t. (log sf, log l, log s2) and Z: cimrgp_trsm_rows_lt,
-cimrgp_sparse_grad_rows, cimrgp_sparse_grad_combine and cimrgp_cov_pair_grad on the n x m side, torch on the m x m side.
-``SparsePosterior`` makes such blocks a layer of ``MultiResolutionGaussianProcess`` (``KernelClass.SparseKernel``; DESIGN.md,
-"Sparse layers in the multiresolution model"): ``SparseBlock.fit_layer`` / ``predict_layer`` take the noise and the bias
-from device scalars (cimrgp_sparse_lambda_dev, cimrgp_sparse_tail_dev) and read nothing back.
-``SparseBlock(..., lengthscales=)`` gives every input dimension its own length-scale (ARD; DESIGN.md, "ARD length-scales for
-the sparse GP"): the block works on x / l and z / l with a unit length-scale, and ``lml_grad`` takes the d derivatives w.r.t.
-log l_e from cimrgp_cov_pair_grad_ard.
-After a fit the block also answers ``predict_grad``, ``loo`` and ``joint`` ("Posterior queries of the sparse GP":
-cimrgp_cov_cross_grad, cimrgp_sparse_tail_grad, cimrgp_sparse_loo, cimrgp_sparse_joint_cov); a model layer's block does not.
-``SparseBlock(..., linear=)`` adds a linear term to the covariance, k(x, x') = k_cov(x, x') + sum_e v_e x_e x'_e ("A
-linear term for the sparse GP"): k(x, x) is then not the constant sf, and the fit, the prediction and ``lml_grad`` take the
-calls of include/cimrgp_sparse_linear.h (cimrgp_cov_gram_lin, cimrgp_cov_cross_lin, cimrgp_sparse_lambda_kd,
-cimrgp_cov_pair_grad_lin); the posterior queries of such a block are not built.
+Cost n m^2 flop and n m memory, against n^3 / 3 and n^2 of an exact block.  Every step is a call of the C ABI; torch holds
+the buffers, adds up the two O(n q) scalars of the LML and does the m x m plumbing of the gradient.
+
+Two classes share the work.  :class:`BlockCovariance` is the covariance k as the device calls take it, and the only place
+that knows which of its arms a block is in:
+
+    plain         k = k_cov at the kernel's l                    cimrgp_cov_gram / _cross, cimrgp_sparse_lambda, cimrgp_cov_pair_grad
+    ARD           ``lengthscales=``: k_cov at l = 1 on x / l     the same calls on scaled inputs, cimrgp_cov_pair_grad_ard
+    linear        ``linear=``: k_cov + sum_e v_e x_e x'_e        cimrgp_cov_gram_lin / _cross_lin, cimrgp_sparse_lambda_kd,
+                                                                 cimrgp_cov_pair_grad_lin (include/cimrgp_sparse_linear.h)
+    ARD + linear  both: the weights on x / l are u = v l^2       the _lin calls with ``ard``
+
+It scales inputs into the block's units (``inputs``), builds K_uu and K(., Z) (``gram``, ``cross``), gives k(x, x) its
+linear share (``linear_diag``, ``lambda_pass``, ``seed_tail``), contracts a weight matrix with dK (``pair_grad``) and takes
+gradients back to the caller's units (``chain_rule``).  DESIGN.md, "ARD length-scales for the sparse GP" and "A linear term
+for the sparse GP", has the mathematics of the arms.
+
+:class:`SparseBlock` is the algebra above, written once over that object: ``fit`` / ``predict``
+(cimrgp_potrf, cimrgp_trsm_rows, cimrgp_wsyrk_tn, cimrgp_potrs, cimrgp_logdet_half, cimrgp_sparse_tail), ``lml_grad`` (the
+analytic gradient w.r.t. the hyper-parameters and Z: cimrgp_trsm_rows_lt, cimrgp_sparse_grad_rows,
+cimrgp_sparse_grad_combine on the n x m side; DESIGN.md, "Gradients of the sparse objective"), and ``predict_grad``,
+``loo`` and ``joint`` (DESIGN.md, "Posterior queries of the sparse GP": cimrgp_cov_cross_grad, cimrgp_sparse_tail_grad,
+cimrgp_sparse_loo, cimrgp_sparse_joint_cov), which are not built for a covariance with a linear term.
+:class:`SparsePosterior` makes such blocks a layer of ``MultiResolutionGaussianProcess`` (``KernelClass.SparseKernel``;
+DESIGN.md, "Sparse layers in the multiresolution model"): ``SparseBlock.fit_layer`` / ``predict_layer`` take the noise and
+the bias from device scalars (cimrgp_sparse_lambda_dev, cimrgp_sparse_tail_dev) and read nothing back; a layer's block is
+plain, and answers none of the posterior queries.
 """
 import numpy as np
 import torch
@@ -41,6 +51,117 @@ APPROXIMATIONS = {'fitc': 0, 'vfe': 1, 'dtc': 1}
 PREDICT_BUDGET_BYTES = 1 << 30
 
 
+def read_back(scalars, vectors):
+    """ONE copy to the host of named device tensors: ``scalars`` (name -> a tensor of one element) come back as floats,
+    ``vectors`` (name -> a 1-d tensor, or None: left out) as float64 arrays of their own length, in one dict."""
+    vectors = {name: t for name, t in vectors.items() if t is not None}
+    parts = [t.double().reshape(-1) for t in (*scalars.values(), *vectors.values())]
+    ends, host = np.cumsum([p.numel() for p in parts]), torch.cat(parts).cpu().numpy()      # the ends first: before the wait
+    return {k: float(host[e - 1]) if k in scalars else host[e - p.numel():e] for k, p, e in zip((*scalars, *vectors), parts, ends)}
+
+
+class BlockCovariance(object):
+    """The covariance of a sparse block as the device calls take it (module docstring): ``kernel``'s values, ``scale`` =
+    1 / l on the device under ARD (else None), and under a linear term the weights ``u`` = v l^2 on the host and ``lin``,
+    the same as a device float64 (d,) tensor (else None).  ``lengthscales`` and ``linear`` keep the caller's values."""
+
+    def __init__(self, kernel, x, lengthscales=None, linear=None, device_noise=False):
+        d = int(x.shape[1])
+        self.kernel = kernel
+        self.lengthscales = self.scale = self.linear = self.u = self.lin = None
+        if lengthscales is not None:
+            ls = np.asarray(lengthscales, dtype=np.float64)
+            if ls.shape != (d,) or not (np.isfinite(ls).all() and (ls > 0).all()):
+                raise ValueError('lengthscales must be %d positive numbers, one per input dimension' % d)
+            if kernel.l != 1.0:
+                raise ValueError('with lengthscales the kernel must have l = 1.0, got %r' % (kernel.l,))
+            if device_noise:
+                raise ValueError('lengthscales are not available to a model layer (device_noise=True)')
+            self.lengthscales = ls.copy()
+            self.scale = torch.as_tensor(1.0 / ls, dtype=x.dtype, device=x.device)       # as Hyper.unit_lengthscale forms it
+        if linear is not None:
+            v = np.asarray(linear, dtype=np.float64)
+            if v.shape != (d,) or not (np.isfinite(v).all() and (v > 0).all()):
+                raise ValueError('linear must be %d positive variances, one per input dimension' % d)
+            if device_noise:
+                raise ValueError('a linear term is not available to a model layer (device_noise=True)')
+            self.linear = v.copy()
+            self.u = v if self.lengthscales is None else v * self.lengthscales ** 2
+            self.lin = torch.as_tensor(self.u, dtype=torch.float64).to(x.device)
+
+    def inputs(self, x):
+        """``x`` in the block's units: ``x`` itself, or x / l under ARD.  Training, inducing and test inputs all pass here."""
+        return x if self.scale is None else scaled(x, self.scale)
+
+    def gram(self, zs, diag_add):
+        """The lower triangle of K(zs, zs) + diag_add I in a new padded buffer."""
+        k = self.kernel
+        if self.lin is None:
+            return dev.rbf_gram(zs, k.l, k.sf, diag_add, lower_only=True, cov=k.cov)
+        return devl.cov_gram_lin(zs, k.l, k.sf, self.lin, diag_add, lower_only=True, cov=k.cov)
+
+    def cross(self, xs, zs, out=None):
+        """K(xs, zs), into ``out`` or a new padded buffer."""
+        k = self.kernel
+        if self.lin is None:
+            return dev.rbf_cross(xs, zs, k.l, k.sf, out=out, cov=k.cov)
+        return devl.cov_cross_lin(xs, zs, k.l, k.sf, self.lin, out=out, cov=k.cov)
+
+    def linear_diag(self, xs):
+        """sum_e u_e xs_ie^2 of scaled inputs ``xs``: the linear term's share of k(x_i, x_i), FP64 (O(n d) torch arithmetic)."""
+        return (xs.double() ** 2 * self.lin).sum(dim=1)
+
+    def lambda_pass(self, a, n, m, xs, mode, noise_dev=None):
+        """(lambda, w = 1 / lambda, sums) of A = ``a`` (n x m) over the scaled inputs ``xs``, from k(x_i, x_i) = sf (+ the
+        linear share).  ``noise_dev``: the noise variance as a device scalar, in place of ``kernel.noise``."""
+        k = self.kernel
+        if self.lin is not None:
+            kdiag = (k.sf + self.linear_diag(xs)).to(xs.dtype)
+            return devl.sparse_lambda_kd(a, n, m, kdiag, k.noise, mode)
+        if noise_dev is not None:
+            return dev.sparse_lambda_dev(a, n, m, k.sf, noise_dev, mode)
+        return dev.sparse_lambda(a, n, m, k.sf, k.noise, mode)
+
+    def seed_tail(self, xs, mean, var):
+        """What cimrgp_sparse_tail starts from at the test inputs ``xs`` (the caller's units).  k(x*, x*) the constant sf:
+        nothing, the tail overwrites.  With a linear term, k(x*, x*) = sf + sum_e u_e x*_e^2: ``mean`` is zeroed, ``var``
+        takes the linear share, and the tail adds onto them.  Returns the tail's ``accumulate``."""
+        if self.lin is None:
+            return False
+        if mean is not None:
+            mean.zero_()
+        if var is not None:
+            var.copy_(self.linear_diag(self.inputs(xs)))
+        return True
+
+    def pair_grad(self, xa, xb, g, want_db, scale=1.0, into=None):
+        """``(sums, lsums, db)`` of the weight matrix ``g`` over the pairs (xa_i, xb_j): sums = [sum G o K_cov, sum G o
+        dK_cov/dlog l (ARD: one per length-scale)], lsums_e = sum G o dK/du_e (None without a linear term), db = scale
+        dF/dxb (None unless ``want_db``).  ``into``: an earlier call's result, which this call adds to."""
+        k = self.kernel
+        sums, lsums, db = into or (None, None, None)
+        kw = dict(scale=scale, accumulate=into is not None, sums=sums, db=db, want_db=want_db, cov=k.cov)
+        if self.lin is not None:
+            return devl.cov_pair_grad_lin(xa, xb, g, k.l, k.sf, self.lin, ard=self.scale is not None, lsums=lsums, **kw)
+        sums, db = (dev.cov_pair_grad if self.scale is None else dev.cov_pair_grad_ard)(xa, xb, g, k.l, k.sf, **kw)
+        return sums, None, db
+
+    def diag_grad(self, t, xs):
+        """sum_i t_i xs_ie^2 (FP64, (d,)): the share of k(x_i, x_i) in dF / du_e, t_i = dF / dk_ii; None without a linear term."""
+        return None if self.lin is None else (t.double()[:, None] * xs.double() ** 2).sum(dim=0)
+
+    def chain_rule(self, dz=None, mean_grad=None, var_grad=None):
+        """Gradients w.r.t. inputs in the block's units, taken to the caller's: d / dx_e = (d / d(x_e / l_e)) / l_e.
+        ``dz`` (m x d) is returned (a new tensor under ARD); ``mean_grad`` (ns, d, q) and ``var_grad`` (ns, d) change in place."""
+        if self.scale is None:
+            return dz
+        if mean_grad is not None:
+            mean_grad.mul_(self.scale[None, :, None])
+        if var_grad is not None:
+            var_grad.mul_(self.scale[None, :])
+        return None if dz is None else dz * self.scale
+
+
 class SparseBlock(object):
     """Device-resident state of one inducing-point block: L_u and L_B with their workspaces, and gamma."""
 
@@ -53,8 +174,8 @@ class SparseBlock(object):
         ``x``, ``z``, the test inputs of :meth:`predict` and the dZ of :meth:`lml_grad` stay in the caller's units.
         ``linear``: a (d,) array of positive variances v_e in the units of ``x``: the covariance is k_cov(x, x') +
         sum_e v_e x_e x'_e (GPy's ``Linear(d, ARD=True)`` added to the kernel); the jitter stays ``jitter * sf``.  On the
-        scaled inputs the same term has the weights u_e = v_e l_e^2, which the block forms; callers speak in v.  None: no
-        such term, and every call is the one made before the term existed."""
+        scaled inputs the same term has the weights u_e = v_e l_e^2, which ``cov`` (a :class:`BlockCovariance`) forms;
+        callers speak in v.  None: no such term."""
         key = str(approximation).lower()
         if key not in APPROXIMATIONS:
             raise ValueError("approximation must be 'fitc' or 'vfe', got %r" % (approximation,))
@@ -65,81 +186,39 @@ class SparseBlock(object):
         if x.shape[1] != z.shape[1] or x.dtype != z.dtype:
             raise ValueError('inducing inputs must have the dimension and dtype of the training inputs')
         self.x, self.z = x, z.contiguous()
-        self.lengthscales = self._scale = None
-        self._xs, self._zs = self.x, self.z              # what the covariance calls take: x / l and z / l with lengthscales
-        if lengthscales is not None:
-            ls = np.asarray(lengthscales, dtype=np.float64)
-            if ls.shape != (int(x.shape[1]),) or not (np.isfinite(ls).all() and (ls > 0).all()):
-                raise ValueError('lengthscales must be %d positive numbers, one per input dimension' % int(x.shape[1]))
-            if kernel.l != 1.0:
-                raise ValueError('with lengthscales the kernel must have l = 1.0, got %r' % (kernel.l,))
-            if device_noise:
-                raise ValueError('lengthscales are not available to a model layer (device_noise=True)')
-            self.lengthscales = ls.copy()
-            self._scale, self._xs = unit_lengthscale(self.x, ls)
-            self._zs = scaled(self.z, self._scale)
-        self.linear = self._u = self._lin = None         # v (caller's units), u = v l^2 (host), u as device float64 (d,)
-        if linear is not None:
-            v = np.asarray(linear, dtype=np.float64)
-            if v.shape != (int(x.shape[1]),) or not (np.isfinite(v).all() and (v > 0).all()):
-                raise ValueError('linear must be %d positive variances, one per input dimension' % int(x.shape[1]))
-            if device_noise:
-                raise ValueError('a linear term is not available to a model layer (device_noise=True)')
-            self.linear = v.copy()
-            self._u = v if self.lengthscales is None else v * self.lengthscales ** 2
-            self._lin = torch.as_tensor(self._u, dtype=torch.float64).to(x.device)
+        self.cov = BlockCovariance(kernel, x, lengthscales, linear, device_noise)
+        self.lengthscales, self.linear = self.cov.lengthscales, self.cov.linear
+        self._xs, self._zs = self.cov.inputs(self.x), self.cov.inputs(self.z)        # what the covariance calls take
         self.n, self.m = int(x.shape[0]), int(z.shape[0])
-        self.kernel = kernel
-        self.device_noise = bool(device_noise)
-        self.approximation = 'fitc' if key == 'fitc' else 'vfe'
-        self.mode = APPROXIMATIONS[key]
-        self.jitter = float(jitter)
-        self.lu = self.ws_u = self.info_u = None
-        self.lb = self.ws_b = self.info_b = None
-        self.gamma = None
-        self._terms = None               # device scalars of the LML
+        self.kernel, self.device_noise, self.jitter = kernel, bool(device_noise), float(jitter)
+        self.approximation, self.mode = 'fitc' if key == 'fitc' else 'vfe', APPROXIMATIONS[key]
+        self.lu = self.ws_u = self.info_u = self.lb = self.ws_b = self.info_b = self.gamma = None
+        self._terms = None               # (lambda sums, the device scalars of the LML by name, q)
         self.bias = self.noise = self.sums = None        # a layer's block (fit_layer): device (q,), (1,) and float64 (3,)
 
     def _enqueue_fit(self, r, noise_dev=None):
-        """The fit's device calls, nothing read back: (A, w, lambda sums).  A (n x m) is the caller's to free.
-        ``noise_dev``: the noise variance as a device scalar, in place of ``kernel.noise``."""
+        """The fit's device calls up to B = I + A^T W A (unfactored, in ``self.lb``), nothing read back: (A, w, lambda sums,
+        c = A^T W r).  A (n x m) is the caller's to free.  ``noise_dev``: the noise variance as a device scalar, in place
+        of ``kernel.noise``."""
         k, n, m = self.kernel, self.n, self.m
-        if self._lin is not None:
-            return self._enqueue_fit_linear()
-        self.lu = dev.rbf_gram(self._zs, k.l, k.sf, self.jitter * k.sf, lower_only=True, cov=k.cov)
+        self.lu = self.cov.gram(self._zs, self.jitter * k.sf)
         self.ws_u, self.info_u = dev.potrf(self.lu, m)
-        a = dev.rbf_cross(self._xs, self._zs, k.l, k.sf, cov=k.cov)
+        a = self.cov.cross(self._xs, self._zs)
         dev.trsm_rows(self.lu, m, self.ws_u, a, n)
-        if noise_dev is not None:
-            _, w, sums = dev.sparse_lambda_dev(a, n, m, k.sf, noise_dev, self.mode)
-        else:
-            _, w, sums = dev.sparse_lambda(a, n, m, k.sf, k.noise, self.mode)
-        return a, w, sums
+        _, w, sums = self.cov.lambda_pass(a, n, m, self._xs, self.mode, noise_dev)
+        self.lb, c = dev.wsyrk_tn(a, n, m, w, r, diag_add=1.0)
+        return a, w, sums, c
 
-    def _lin_diag(self, xs):
-        """sum_e u_e xs_ie^2 of scaled inputs ``xs``: the linear term's share of k(x_i, x_i), FP64 (O(n d) torch arithmetic)."""
-        return (xs.double() ** 2 * self._lin).sum(dim=1)
+    def _enqueue_solve(self, c):
+        """Factor L_B in place and gamma = L_B^-1 c; c is overwritten with b = B^-1 c = L_B^-T gamma."""
+        self.ws_b, self.info_b = dev.potrf(self.lb, self.m)
+        self.gamma = dev.potrs(self.lb, self.m, self.ws_b, c, want_z=True)
 
-    def _enqueue_fit_linear(self):
-        """:meth:`_enqueue_fit` with the linear term: the _lin Gram calls, and lambda from k(x_i, x_i) = sf + sum_e u_e x_ie^2."""
-        k, n, m = self.kernel, self.n, self.m
-        self.lu = devl.cov_gram_lin(self._zs, k.l, k.sf, self._lin, self.jitter * k.sf, lower_only=True, cov=k.cov)
-        self.ws_u, self.info_u = dev.potrf(self.lu, m)
-        a = devl.cov_cross_lin(self._xs, self._zs, k.l, k.sf, self._lin, cov=k.cov)
-        dev.trsm_rows(self.lu, m, self.ws_u, a, n)
-        kdiag = (k.sf + self._lin_diag(self._xs)).to(self._xs.dtype)
-        _, w, sums = devl.sparse_lambda_kd(a, n, m, kdiag, k.noise, self.mode)
-        return a, w, sums
-
-    def _enqueue_solve(self, r, c, w, sums):
-        """Factor L_B in place, gamma and the device scalars of the LML; c = A^T W r is overwritten with b = L_B^-T gamma."""
-        m, q = self.m, int(r.shape[1])
-        self.ws_b, self.info_b = dev.potrf(self.lb, m)
-        self.gamma = dev.potrs(self.lb, m, self.ws_b, c, want_z=True)
-        half_logdet_b = dev.logdet_half(self.lb, m)
-        rwr = (r.double() ** 2 * w.double()[:, None]).sum()
-        gg = (self.gamma.double() ** 2).sum()
-        self._terms = (sums, half_logdet_b, rwr, gg, q)
+    def _enqueue_lml_terms(self, r, w, sums):
+        """The device scalars of the LML, after :meth:`_enqueue_solve`."""
+        scalars = dict(half_logdet_b=dev.logdet_half(self.lb, self.m), rwr=(r.double() ** 2 * w.double()[:, None]).sum(),
+                       gg=(self.gamma.double() ** 2).sum())
+        self._terms = (sums, scalars, int(r.shape[1]))
 
     def _raise_if_failed(self, info_u, bad, info_b):
         dev.raise_if_not_pd(info_u)
@@ -150,12 +229,10 @@ class SparseBlock(object):
     def fit(self, r):
         """``r`` (n x q): residual targets on the device.  Nothing is read back but the two ``info`` words and the
         count of non-positive lambda."""
-        n, m = self.n, self.m
         r = r.contiguous()
-        a, w, sums = self._enqueue_fit(r)
-        self.lb, c = dev.wsyrk_tn(a, n, m, w, r, diag_add=1.0)
-        del a                                            # n x m: not needed after the fit
-        self._enqueue_solve(r, c, w, sums)
+        w, sums, c = self._enqueue_fit(r)[1:]            # A (n x m) is not needed after this: released here
+        self._enqueue_solve(c)
+        self._enqueue_lml_terms(r, w, sums)
         self._raise_if_failed(self.info_u, sums[2].item(), self.info_b)
         return self
 
@@ -167,14 +244,10 @@ class SparseBlock(object):
         prediction A b + bias, b = L_B^-T gamma (what cimrgp_potrs leaves in c), is added into ``train_out`` (n x q) by
         cimrgp_sparse_tail_dev with A as W*; then A is released.  What stays -- L_u, L_B, their workspaces, gamma, bias,
         noise -- is m x m or smaller, whatever the model's ``keep_factors`` says."""
-        k, n, m = self.kernel, self.n, self.m
-        self.bias, self.noise, r = block_targets(k, y, f_bar, shared_bias, shared_noise, noise_fraction, noise_floor)
-        a, w, self.sums = self._enqueue_fit(r, self.noise)
-        self.lb, c = dev.wsyrk_tn(a, n, m, w, r, diag_add=1.0)
-        self.ws_b, self.info_b = dev.potrf(self.lb, m)
-        self.gamma = dev.potrs(self.lb, m, self.ws_b, c, want_z=True)
-        dev.sparse_tail_dev(None, a, n, m, c, k.sf, bias=self.bias, mean_out=train_out, accumulate=True)
-        del a
+        self.bias, self.noise, r = block_targets(self.kernel, y, f_bar, shared_bias, shared_noise, noise_fraction, noise_floor)
+        a, _, self.sums, c = self._enqueue_fit(r, self.noise)
+        self._enqueue_solve(c)
+        dev.sparse_tail_dev(None, a, self.n, self.m, c, self.kernel.sf, bias=self.bias, mean_out=train_out, accumulate=True)
         return self
 
     def hand_over_to(self, stream):
@@ -184,9 +257,10 @@ class SparseBlock(object):
             if t is not None:
                 t.record_stream(stream)
 
-    def _lml_from(self, s0, s1, half_logdet_b, rwr, gg, q):
-        lml = (-0.5 * self.n * q * np.log(2 * np.pi) - 0.5 * q * s0 - q * float(half_logdet_b)
-               - 0.5 * float(rwr) + 0.5 * float(gg))
+    def _lml_from(self, s0, s1, h, q):
+        """The LML from host numbers: the first two lambda sums and ``h``, the scalars of :meth:`_enqueue_lml_terms` by name."""
+        lml = (-0.5 * self.n * q * np.log(2 * np.pi) - 0.5 * q * s0 - q * float(h['half_logdet_b'])
+               - 0.5 * float(h['rwr']) + 0.5 * float(h['gg']))
         if self.mode == 1:
             lml -= 0.5 * q * s1 / self.kernel.noise
         return float(lml)
@@ -194,57 +268,37 @@ class SparseBlock(object):
     def log_marginal_likelihood(self):
         if self._terms is None:
             raise RuntimeError('call fit() before log_marginal_likelihood()')
-        sums, half_logdet_b, rwr, gg, q = self._terms
+        sums, scalars, q = self._terms
         s = sums.cpu().numpy()
-        return self._lml_from(s[0], s[1], half_logdet_b.item(), rwr.item(), gg.item(), q)
+        return self._lml_from(s[0], s[1], {name: t.item() for name, t in scalars.items()}, q)
 
-    def lml_grad(self, r, want_z=True):
-        """Fit on ``r`` (n x q, device) and return ``(lml, dtheta, dZ)``: the objective :meth:`log_marginal_likelihood`
-        returns (bit for bit), its gradient w.r.t. (log sf, log l, log noise) as a NumPy (3,) array and, with ``want_z``,
-        w.r.t. the inducing inputs as a device tensor (m x d), else None (DESIGN.md, "Gradients of the sparse
-        objective").  With ``lengthscales`` the gradient is w.r.t. (log sf, log l_1 .. log l_d, log noise), a (d + 2,) array
-        (cimrgp_cov_pair_grad_ard in place of cimrgp_cov_pair_grad), and dZ is w.r.t. ``z`` in the caller's units.
-        The failure rules are :meth:`fit`'s.  A stays alive for the length of the call beside ONE more
-        n x m buffer (V, Y, G_A and G_fu in place of one another); one host read-back at the end (the info words, the
-        lambda count and the scalars).  g of Matern 1/2 is taken as 0 at r = 0 (an inducing input on a training input or
-        on another inducing input, where the objective has a kink): such pairs contribute nothing to dZ.
-        With ``linear`` the gradient has d more entries at its end, w.r.t. log v_1 .. log v_d (cimrgp_cov_pair_grad_lin in
-        place of either pair contraction; dZ carries the linear part), and d / dlog sf is taken in its pairwise form: the
-        closed form 1/2 tr M + sf sum t holds only while k is proportional to sf."""
-        k, n, m = self.kernel, self.n, self.m
-        q = int(r.shape[1])
-        r = r.contiguous()
-        dt, device = self.z.dtype, self.z.device
-        a, w, sums = self._enqueue_fit(r)
-        self.lb, c = dev.wsyrk_tn(a, n, m, w, r, diag_add=1.0)
-        eye = torch.eye(m, dtype=dt, device=device)
-        bmat = None
-        if self.mode == 1:                               # VFE: A^T diag(t) A = -(q / 2) (B - I), from B before it is factored
-            bmat = torch.tril(self.lb[:m, :m])
-            bmat = bmat + torch.tril(bmat, -1).t()
-        self._enqueue_solve(r, c, w, sums)
-        b = c                                            # potrs left B^-1 c = L_B^-T gamma in c
-        # the n x m chain, in place in ONE buffer beside A: V = A L_B^-T, Y = V L_B^-1, G_A, G_fu = G_A L_u^-1
+    def _enqueue_g_fu(self, a, w, r, b):
+        """The n x m chain in ONE buffer beside A: V = A L_B^-T, Y = V L_B^-1, G_A and G_fu = G_A L_u^-1 in place of one
+        another.  Returns (G_fu, t, [sum h, sum t])."""
+        n, m = self.n, self.m
         y = torch.empty_like(a)
         y.copy_(a)
         dev.trsm_rows(self.lb, m, self.ws_b, y, n)
-        beta, t, gsums = dev.sparse_grad_rows(y, n, m, self.gamma, r, w, self.mode, k.noise)
+        beta, t, gsums = dev.sparse_grad_rows(y, n, m, self.gamma, r, w, self.mode, self.kernel.noise)
         dev.trsm_rows_lt(self.lb, m, self.ws_b, y, n)
         dev.sparse_grad_combine(a, y, n, m, beta, b, w, t)
         dev.trsm_rows_lt(self.lu, m, self.ws_u, y, n)
-        # the m x m plumbing: B^-1 from the identity, M = b b^T - q (I - B^-1) - 2 A^T diag(t) A, G_uu = -1/2 L_u^-T M L_u^-1
+        return y, t, gsums
+
+    def _enqueue_g_uu(self, a, t, b, blow, q):
+        """The m x m side: B^-1 from the identity, M = b b^T - q (I - B^-1) - 2 A^T diag(t) A and G_uu = -1/2 L_u^-T M L_u^-1
+        (padded buffer).  A^T diag(t) A is cimrgp_wsyrk_tn with the signed weights t (FITC) or -(q / 2) (B - I) from
+        ``blow``, B's lower triangle copied before it was factored (VFE; None under FITC).  Returns (M, G_uu)."""
+        n, m, dt, device = self.n, self.m, self.z.dtype, self.z.device
+        eye = torch.eye(m, dtype=dt, device=device)
         binv = dev.alloc_matrix(m, m, dt, device)
         binv.zero_()
         binv[:m, :m].fill_diagonal_(1.0)
         dev.trsm_rows(self.lb, m, self.ws_b, binv, m)
         dev.trsm_rows_lt(self.lb, m, self.ws_b, binv, m)
-        if self.mode == 0:
-            ata, _ = dev.wsyrk_tn(a, n, m, t)
-            ata = torch.tril(ata[:m, :m])
-            ata = ata + torch.tril(ata, -1).t()
-        else:
-            ata = (-0.5 * q) * (bmat - eye)
-        del a
+        low = torch.tril(dev.wsyrk_tn(a, n, m, t)[0][:m, :m]) if blow is None else blow
+        full = low + torch.tril(low, -1).t()
+        ata = full if blow is None else (-0.5 * q) * (full - eye)
         mm = b @ b.t() - q * (eye - binv[:m, :m]) - 2.0 * ata
         guu = dev.alloc_matrix(m, m, dt, device)
         guu[:m, :m] = 0.5 * (mm + mm.t())
@@ -252,50 +306,70 @@ class SparseBlock(object):
         guu[:m, :m] = guu[:m, :m].t().clone()
         dev.trsm_rows_lt(self.lu, m, self.ws_u, guu, m)
         guu[:m, :m] = -0.25 * (guu[:m, :m] + guu[:m, :m].t())
-        # sum G o K, sum G o dK/dlog l and dZ: K_fu's pairs, then K_uu's added (G_uu symmetric: scale 2 = -2 x -1)
-        # with lengthscales: [sum G o K, sum G o dK/dlog l_e for every e] on the scaled inputs, and dZ of the scaled Z
-        lin_terms = []
-        if self._lin is None:
-            pair_grad = dev.cov_pair_grad if self._scale is None else dev.cov_pair_grad_ard
-            psums, dz = pair_grad(self._xs, self._zs, y, k.l, k.sf, want_db=want_z, cov=k.cov)
-            pair_grad(self._zs, self._zs, guu, k.l, k.sf, scale=2.0, accumulate=True, sums=psums, db=dz, want_db=want_z, cov=k.cov)
-        else:
-            # lsums_e = sum G o dK/du_e over both matrices; sum_i t_i x_ie^2 is the diagonal's share (t_i = dF / dk_ii)
-            ard = self._scale is not None
-            psums, lsums, dz = devl.cov_pair_grad_lin(self._xs, self._zs, y, k.l, k.sf, self._lin, ard=ard, want_db=want_z, cov=k.cov)
-            devl.cov_pair_grad_lin(self._zs, self._zs, guu, k.l, k.sf, self._lin, ard=ard, scale=2.0, accumulate=True, sums=psums,
-                                   lsums=lsums, db=dz, want_db=want_z, cov=k.cov)
-            lin_terms = [lsums, (t.double()[:, None] * self._xs.double() ** 2).sum(dim=0)]
-        del y
-        if dz is not None and self._scale is not None:
-            dz = dz * self._scale                        # d / dz_je = (d / d(z_je / l_e)) / l_e
-        _, half_logdet_b, rwr, gg, _ = self._terms
-        host = torch.cat([self.info_u.double(), self.info_b.double(), sums, half_logdet_b.reshape(1), rwr.reshape(1), gg.reshape(1),
-                          gsums, psums, torch.diagonal(mm).double().sum().reshape(1),
-                          torch.diagonal(guu[:m, :m]).double().sum().reshape(1)] + lin_terms).cpu().numpy()
-        info_u, info_b, s0, s1, bad, hld, rwr_h, gg_h, sum_h, sum_t, gk = host[:11]
-        ngl = int(psums.shape[0]) - 1
-        gl, (tr_m, tr_guu) = host[11:11 + ngl], host[11 + ngl:13 + ngl]      # gl: one entry, or one per length-scale
-        self._raise_if_failed(info_u, bad, info_b)
-        lml = self._lml_from(s0, s1, hld, rwr_h, gg_h, q)
+        return mm, guu
+
+    def _enqueue_pair_sums(self, g_fu, g_uu, want_z):
+        """sum G o K, sum G o dK/dlog l and dZ of the scaled Z: K_fu's pairs, then K_uu's added (G_uu symmetric: scale 2 =
+        -2 x -1).  Returns :meth:`BlockCovariance.pair_grad`'s (sums, lsums, dz)."""
+        pairs = self.cov.pair_grad
+        return pairs(self._zs, self._zs, g_uu, want_z, scale=2.0, into=pairs(self._xs, self._zs, g_fu, want_z))
+
+    def _gradient_from(self, h, q):
+        """``(lml, dtheta, grad_check)`` from the host values ``h`` of :meth:`lml_grad`'s read-back: host arithmetic only."""
+        k, u = self.kernel, self.cov.u
+        (s0, s1, _), (sum_h, sum_t) = h['sums'], h['gsums']
+        gk, gl = h['psums'][0], h['psums'][1:]               # gl: one entry, or one per length-scale
+        lml = self._lml_from(s0, s1, h, q)
         dnoise = k.noise * (sum_h + (0.5 * q / k.noise ** 2 * s1 if self.mode == 1 else 0.0))
-        if self._lin is None:
-            dsf = 0.5 * tr_m + k.sf * sum_t
-            #: the pairwise form of d F / d log sf, which the closed form above must equal (checked by the GPU tests)
-            self.grad_check = dict(closed=float(dsf), pairwise=float(gk + self.jitter * k.sf * tr_guu + k.sf * sum_t))
-            return lml, np.concatenate([[dsf], gl, [dnoise]]), dz
-        d = self._u.shape[0]
-        lsums_h, tx2 = host[13 + ngl:13 + ngl + d], host[13 + ngl + d:]
-        dsf = gk + self.jitter * k.sf * tr_guu + k.sf * sum_t
-        #: 1/2 tr M = sum G o K over both matrices, whatever K is: the covariance's, the jitter's and the linear term's shares
-        self.grad_check = dict(closed=float(0.5 * tr_m), pairwise=float(gk + self.jitter * k.sf * tr_guu + (self._u * lsums_h).sum()))
-        return lml, np.concatenate([[dsf], gl, [dnoise], self._u * (lsums_h + tx2)]), dz
+        jit = self.jitter * k.sf * h['tr_guu']
+        if u is None:
+            # k is proportional to sf: the closed form, which the pairwise form must equal (checked by the GPU tests)
+            dsf = 0.5 * h['tr_m'] + k.sf * sum_t
+            check = dict(closed=float(dsf), pairwise=float(gk + jit + k.sf * sum_t))
+            return lml, np.concatenate([[dsf], gl, [dnoise]]), check
+        # 1/2 tr M = sum G o K over both matrices, whatever K is: the covariance's, the jitter's and the linear term's shares
+        check = dict(closed=float(0.5 * h['tr_m']), pairwise=float(gk + jit + (u * h['lsums']).sum()))
+        return lml, np.concatenate([[gk + jit + k.sf * sum_t], gl, [dnoise], u * (h['lsums'] + h['tx2'])]), check
+
+    def lml_grad(self, r, want_z=True):
+        """Fit on ``r`` (n x q, device) and return ``(lml, dtheta, dZ)``: the objective :meth:`log_marginal_likelihood`
+        returns (bit for bit), its gradient w.r.t. (log sf, log l, log noise) as a NumPy (3,) array and, with ``want_z``,
+        w.r.t. the inducing inputs as a device tensor (m x d), else None (DESIGN.md, "Gradients of the sparse
+        objective").  With ``lengthscales`` the gradient is w.r.t. (log sf, log l_1 .. log l_d, log noise), a (d + 2,) array,
+        and dZ is w.r.t. ``z`` in the caller's units.  With ``linear`` the gradient has d more entries at its end, w.r.t.
+        log v_1 .. log v_d (dZ carries the linear part), and d / dlog sf is taken in its pairwise form: the closed form
+        1/2 tr M + sf sum t holds only while k is proportional to sf.  ``grad_check`` keeps both forms of 1/2 tr M.
+        The failure rules are :meth:`fit`'s.  A stays alive for the length of the call beside ONE more n x m buffer; one
+        host read-back at the end (the info words, the lambda count and the scalars).  g of Matern 1/2 is taken as 0 at
+        r = 0 (an inducing input on a training input or on another inducing input, where the objective has a kink): such
+        pairs contribute nothing to dZ."""
+        q, m = int(r.shape[1]), self.m
+        r = r.contiguous()
+        a, w, sums, b = self._enqueue_fit(r)
+        blow = torch.tril(self.lb[:m, :m]) if self.mode == 1 else None   # VFE: B's lower triangle, before it is factored
+        self._enqueue_solve(b)                           # potrs leaves B^-1 c = L_B^-T gamma in place of c
+        self._enqueue_lml_terms(r, w, sums)
+        g_fu, t, gsums = self._enqueue_g_fu(a, w, r, b)
+        mm, guu = self._enqueue_g_uu(a, t, b, blow, q)
+        del a                                            # n x m: not needed by the pair contractions
+        psums, lsums, dz = self._enqueue_pair_sums(g_fu, guu, want_z)
+        dz = self.cov.chain_rule(dz=dz)
+        h = read_back(dict(self._terms[1], info_u=self.info_u, info_b=self.info_b, tr_m=torch.diagonal(mm).double().sum(),
+                           tr_guu=torch.diagonal(guu[:m, :m]).double().sum()),
+                      dict(sums=sums, gsums=gsums, psums=psums, lsums=lsums, tx2=self.cov.diag_grad(t, self._xs)))
+        self._raise_if_failed(h['info_u'], h['sums'][2], h['info_b'])
+        lml, dtheta, self.grad_check = self._gradient_from(h, q)
+        return lml, dtheta, dz
+
+    def _rows_within(self, budget_bytes, slabs):
+        """Test rows per pass, a multiple of 256: ``slabs`` row blocks of A* and as many of W* (pitch padded_ld(m)) per test
+        row within ``budget_bytes`` (None: PREDICT_BUDGET_BYTES)."""
+        budget = PREDICT_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
+        return max(256, budget // (2 * slabs * dev.padded_ld(self.m) * self.z.element_size()) // 256 * 256)
 
     def chunk_rows(self, budget_bytes=None):
-        """Test rows per pass of ``predict``: A* and W* (pitch padded_ld(m)) within ``budget_bytes``, a multiple of 256."""
-        budget = PREDICT_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
-        per_row = 2 * dev.padded_ld(self.m) * self.z.element_size()
-        return max(256, budget // per_row // 256 * 256)
+        """Test rows per pass of ``predict``: A* and W* within ``budget_bytes``."""
+        return self._rows_within(budget_bytes, 1)
 
     def predict(self, xs, mean=None, var=None, include_noise=False, budget_bytes=None):
         """Predictive mean into ``mean`` (ns x q) and variance into ``var`` (ns,) at ``xs`` (ns x d, device); either may
@@ -303,14 +377,8 @@ class SparseBlock(object):
         chunking."""
         if self.gamma is None:
             raise RuntimeError('call fit() before predict()')
-        k, m = self.kernel, self.m
-        extra = k.noise if include_noise else 0.0
-        accumulate = self._lin is not None
-        if accumulate:                                   # k(x*, x*) = sf + sum_e u_e x*_e^2: the tail adds onto the linear share
-            if mean is not None:
-                mean.zero_()
-            if var is not None:
-                var.copy_(self._lin_diag(xs if self._scale is None else scaled(xs, self._scale)))
+        k, m, extra = self.kernel, self.m, self.kernel.noise if include_noise else 0.0
+        accumulate = self.cov.seed_tail(xs, mean, var)
         for s0, s1, astar, wstar in self._star_chunks(xs, budget_bytes):
             dev.sparse_tail(astar if var is not None else None, wstar, s1 - s0, m, self.gamma if mean is not None else None, k.sf,
                             extra, None if mean is None else mean[s0:s1], None if var is None else var[s0:s1], accumulate)
@@ -319,8 +387,7 @@ class SparseBlock(object):
     def _star_chunks(self, xs, budget_bytes=None):
         """(s0, s1, A*, W*) of every chunk of ``chunk_rows(budget_bytes)`` test rows: A* = K(xs[s0:s1], Z) L_u^-T and
         W* = A* L_B^-T in two work buffers that the next chunk overwrites."""
-        k, m = self.kernel, self.m
-        ns = int(xs.shape[0])
+        m, ns = self.m, int(xs.shape[0])
         step = self.chunk_rows(budget_bytes)
         astar = wstar = None
         for s0 in range(0, ns, step):
@@ -329,11 +396,7 @@ class SparseBlock(object):
             if astar is None:
                 astar = dev.alloc_matrix(min(step, ns), m, xs.dtype, xs.device)
                 wstar = torch.empty_like(astar)
-            xc = xs[s0:s1] if self._scale is None else scaled(xs[s0:s1], self._scale)
-            if self._lin is None:
-                dev.rbf_cross(xc, self._zs, k.l, k.sf, out=astar, cov=k.cov)
-            else:
-                devl.cov_cross_lin(xc, self._zs, k.l, k.sf, self._lin, out=astar, cov=k.cov)
+            self.cov.cross(self.cov.inputs(xs[s0:s1]), self._zs, out=astar)
             dev.trsm_rows(self.lu, m, self.ws_u, astar, rows)
             wstar[:rows].copy_(astar[:rows])
             dev.trsm_rows(self.lb, m, self.ws_b, wstar, rows)
@@ -344,16 +407,14 @@ class SparseBlock(object):
         a block with a linear term, before any device work."""
         if self.device_noise:
             raise TypeError('%s() of a sparse layer of the model (device_noise=True) is not yet supported' % what)
-        if self._lin is not None:
+        if self.cov.lin is not None:
             raise TypeError('%s() of a sparse block with a linear term is not yet supported' % what)
         if self.gamma is None:
             raise RuntimeError('call fit() before %s()' % what)
 
     def grad_chunk_rows(self, budget_bytes=None):
         """Test rows per pass of ``predict_grad``: the d + 1 slabs of A* and of W* within ``budget_bytes``, a multiple of 256."""
-        budget = PREDICT_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
-        per_row = 2 * (int(self.z.shape[1]) + 1) * dev.padded_ld(self.m) * self.z.element_size()
-        return max(256, budget // per_row // 256 * 256)
+        return self._rows_within(budget_bytes, int(self.z.shape[1]) + 1)
 
     def predict_grad(self, xs, mean_grad=None, var_grad=None, budget_bytes=None):
         """Gradients of :meth:`predict`'s mean and variance w.r.t. the test inputs ("Posterior queries of the
@@ -365,8 +426,7 @@ class SparseBlock(object):
         k, m = self.kernel, self.m
         ns, d = int(xs.shape[0]), int(xs.shape[1])
         step = self.grad_chunk_rows(budget_bytes)
-        ld = dev.padded_ld(m)
-        cap = min(step, max(ns, 1))
+        ld, cap = dev.padded_ld(m), min(step, max(ns, 1))
         abuf = torch.empty((d + 1) * cap * ld, dtype=xs.dtype, device=xs.device)
         wbuf = torch.empty_like(abuf)
         for s0 in range(0, ns, step):
@@ -374,18 +434,13 @@ class SparseBlock(object):
             rows = s1 - s0
             a = abuf[:(d + 1) * rows * ld].view(d + 1, rows, ld)         # the slabs lie back to back: one operand of
             w = wbuf[:(d + 1) * rows * ld].view(d + 1, rows, ld)         # (d + 1) rows x m for the row solves
-            xc = xs[s0:s1] if self._scale is None else scaled(xs[s0:s1], self._scale)
-            dev.cov_cross_grad(xc.contiguous(), self._zs, k.l, k.sf, a, cov=k.cov)
+            dev.cov_cross_grad(self.cov.inputs(xs[s0:s1]).contiguous(), self._zs, k.l, k.sf, a, cov=k.cov)
             dev.trsm_rows(self.lu, m, self.ws_u, a.view(-1, ld), (d + 1) * rows)
             w.copy_(a)
             dev.trsm_rows(self.lb, m, self.ws_b, w.view(-1, ld), (d + 1) * rows)
             dev.sparse_tail_grad(a if var_grad is not None else None, w, rows, m, self.gamma if mean_grad is not None else None,
                                  None if mean_grad is None else mean_grad[s0:s1], None if var_grad is None else var_grad[s0:s1])
-        if self._scale is not None:                      # d / dx_e = (d / d(x_e / l_e)) / l_e
-            if mean_grad is not None:
-                mean_grad.mul_(self._scale[None, :, None])
-            if var_grad is not None:
-                var_grad.mul_(self._scale[None, :])
+        self.cov.chain_rule(mean_grad=mean_grad, var_grad=var_grad)
         return mean_grad, var_grad
 
     def loo(self, r, mean=None, var=None, budget_bytes=None):
@@ -396,8 +451,7 @@ class SparseBlock(object):
         :meth:`predict` over the training inputs; a row's result does not depend on the chunking.  One host read at the
         end: a row with 1 - h_i <= 0 raises LinAlgError."""
         self._ready_for('loo')
-        k = self.kernel
-        r = r.contiguous()
+        k, r = self.kernel, r.contiguous()
         bad = torch.zeros(1, dtype=torch.int32, device=r.device)
         for s0, s1, a, v in self._star_chunks(self.x, budget_bytes):
             dev.sparse_loo(a, v, s1 - s0, self.m, self.gamma, r[s0:s1], k.sf, k.noise, self.mode, bad,
@@ -414,13 +468,12 @@ class SparseBlock(object):
         (cimrgp_normal_fill), with the escalation rule of the exact blocks (``Posteriors.joint_blocks``, the same code).
         The ns x ns matrix and the rows A*, W* are held whole.  Returns the largest relative jitter used."""
         self._ready_for('joint')
-        k, m = self.kernel, self.m
-        ns = int(xs.shape[0])
+        k, m, ns = self.kernel, self.m, int(xs.shape[0])
         if ns == 0:
             return 0.0
-        xc = (xs if self._scale is None else scaled(xs, self._scale)).contiguous()
+        xc = self.cov.inputs(xs).contiguous()
         astar = torch.empty((ns, dev.joint_ld(m, xs.dtype)), dtype=xs.dtype, device=xs.device)
-        dev.rbf_cross(xc, self._zs, k.l, k.sf, out=astar, cov=k.cov)
+        self.cov.cross(xc, self._zs, out=astar)
         dev.trsm_rows(self.lu, m, self.ws_u, astar, ns)
         wstar = astar.clone()
         dev.trsm_rows(self.lb, m, self.ws_b, wstar, ns)

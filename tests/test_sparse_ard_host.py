@@ -144,9 +144,12 @@ def test_block_constructor_refusals():
     unit = RBFKernel(l=1.0, sf=1.3, noise=0.02)
     blk = SparseBlock(x, z, unit, 'fitc', 1e-6, False, (0.5, 1.0, 2.0))              # the new argument is the last
     assert np.array_equal(blk.lengthscales, [0.5, 1.0, 2.0]) and blk.x is x
-    assert torch.equal(blk._scale, torch.tensor([2.0, 1.0, 0.5], dtype=torch.float64))
+    assert torch.equal(blk.cov.scale, torch.tensor([2.0, 1.0, 0.5], dtype=torch.float64))
+    assert torch.equal(blk.cov.inputs(x + 1.0), torch.tensor([[2.0, 1.0, 0.5]] * 10, dtype=torch.float64))
     plain = SparseBlock(x, z, unit)
-    assert plain.lengthscales is None and plain._xs is plain.x and plain._zs is plain.z
+    assert plain.lengthscales is None and plain.cov.scale is None
+    assert plain.cov.inputs(plain.x) is plain.x and plain.cov.inputs(plain.z) is plain.z      # the caller's tensors, no copies
+    assert plain._xs is plain.x and plain._zs is plain.z
     for bad in ((0.5, 1.0), (0.5, 1.0, 2.0, 3.0), 0.5, [[0.5, 1.0, 2.0]], (0.5, 0.0, 2.0), (0.5, -1.0, 2.0), (0.5, np.nan, 2.0),
                 (0.5, np.inf, 2.0)):
         with pytest.raises(ValueError, match="lengthscales"):

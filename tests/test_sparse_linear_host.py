@@ -380,7 +380,8 @@ def test_queries_that_are_not_built_raise_type_error():
     # the block's: refused before any device work (the tensors here are the host's)
     x, z = torch.zeros(8, 2, dtype=torch.float64), torch.zeros(3, 2, dtype=torch.float64)
     blk = SparseBlock(x, z, ca.RBFKernel(l=1.0, sf=1.0, noise=0.1), 'vfe', lengthscales=[0.7, 1.3], linear=[0.5, 0.2])
-    assert np.allclose(blk._u, [0.5 * 0.49, 0.2 * 1.69]) and np.array_equal(blk.linear, [0.5, 0.2])
+    assert np.allclose(blk.cov.u, [0.5 * 0.49, 0.2 * 1.69]) and np.array_equal(blk.linear, [0.5, 0.2])
+    assert blk.cov.lin.dtype == torch.float64 and np.array_equal(blk.cov.lin.numpy(), blk.cov.u)
     blk.gamma = torch.zeros(3, 1, dtype=torch.float64)   # as after a fit
     for call in (lambda: blk.predict_grad(x), lambda: blk.loo(x[:, :1]), lambda: blk.joint(x)):
         with pytest.raises(TypeError, match='with a linear term is not yet supported'):
@@ -399,4 +400,5 @@ def test_sparse_block_linear_refusals():
             SparseBlock(x, z, k, linear=bad)
     with pytest.raises(ValueError, match='not available to a model layer'):
         SparseBlock(x, z, k, device_noise=True, linear=[0.5, 0.2])
-    assert SparseBlock(x, z, k).linear is None and SparseBlock(x, z, k)._lin is None
+    plain = SparseBlock(x, z, k)
+    assert plain.linear is None and plain.cov.lin is None and plain.cov.u is None        # no linear term, no weights

@@ -2,7 +2,7 @@
 after warm-up, median of --reps, the routes alternating in one process, at (n, m) = (65536, 1024) and (262144, 1000),
 d = 2, q = 1, FITC and VFE:
   * one SparseBlock.lml_grad call (3 + m d derivatives) against one objective evaluation (fit + log_marginal_likelihood),
-    of which two-point differences spend four per step on theta alone;
+    of which two-point differences spend four per step on theta alone (``*_spread_ms``: max - min over the repetitions);
   * the entry points of the call on the call's own operands: cimrgp_trsm_rows, cimrgp_trsm_rows_lt (with L_B and with
     L_u), cimrgp_wsyrk_tn, cimrgp_sparse_grad_rows, cimrgp_sparse_grad_combine, cimrgp_cov_pair_grad;
   * cimrgp_cov_pair_grad against cimrgp_cov_cross at the same shape (the same pairs and exponentials, a read of G instead
@@ -40,7 +40,7 @@ def emit(rec):
             f.write(line + "\n")
 
 
-def timed(fns, reps, warmup=2):
+def timed(fns, reps, warmup=2, spread=None):
     """Median times (ms) of the callables, alternating, device events around each call (a call that reads back, as the
     two routes do, ends inside its events)."""
     for _ in range(warmup):
@@ -56,6 +56,8 @@ def timed(fns, reps, warmup=2):
             b.record()
             torch.cuda.synchronize()
             ts[k].append(a.elapsed_time(b))
+    if spread is not None:          # max - min of each callable's times: what a later comparison of medians can tell apart
+        spread.extend(float(max(t) - min(t)) for t in ts)
     return [float(np.median(t)) for t in ts]
 
 
@@ -80,8 +82,9 @@ for n, m in ((65536, 1024), (262144, 1000)):
         new_block().fit(g._y).log_marginal_likelihood()
         torch.cuda.synchronize()
         peak_fit = torch.cuda.max_memory_allocated() - base
+        spread = []
         t_grad, t_theta, t_eval = timed((lambda: new_block().lml_grad(g._y), lambda: new_block().lml_grad(g._y, want_z=False),
-                                         lambda: new_block().fit(g._y).log_marginal_likelihood()), args.reps)
+                                         lambda: new_block().fit(g._y).log_marginal_likelihood()), args.reps, spread=spread)
         # the entry points on the call's own operands
         blk = g.block
         a0 = dev.rbf_cross(blk.x, blk.z, k.l, k.sf, cov=k.cov)
@@ -114,6 +117,7 @@ for n, m in ((65536, 1024), (262144, 1000)):
         g_bytes = 8.0 * n * m
         emit({"case": "sparse_lml_grad", "device": dev_name, "dtype": "f64", "approximation": g.approximation, "n": n, "m": m,
               "d": d, "q": q, "lml_grad_ms": t_grad, "lml_grad_theta_only_ms": t_theta, "evaluation_ms": t_eval,
+              "lml_grad_spread_ms": spread[0], "lml_grad_theta_only_spread_ms": spread[1], "evaluation_spread_ms": spread[2],
               "lml_grad_over_evaluation": t_grad / t_eval, "below_four_evaluations": bool(t_grad < 4 * t_eval),
               "trsm_rows_ms": t_fwd - t_copy, "trsm_rows_lt_lb_ms": t_lt_b - t_copy, "trsm_rows_lt_lu_ms": t_lt_u - t_copy,
               "wsyrk_tn_ms": t_wsyrk, "sparse_grad_rows_ms": t_rows, "sparse_grad_combine_ms": t_comb,

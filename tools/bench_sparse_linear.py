@@ -7,7 +7,9 @@ length-scales, VFE (the reference plugin's kernel and bound):
   * one evaluation of the objective (fit + log_marginal_likelihood) with ``linear``.
 The one condition: the time the term adds to a gradient call (lml_grad with linear minus lml_grad without) is less than d
 evaluations of the same run, what two-point differences over the d new parameters would spend instead
-("added_below_d_evaluations").  One JSON line per d on stdout, appended to the file named by the first argument if given."""
+("added_below_d_evaluations").  The ``*_spread_ms`` fields are max - min over the repetitions of the four block-level times:
+what a comparison of two runs' medians can tell apart.  One JSON line per d on stdout, appended to the file named by the
+first argument if given."""
 import argparse
 import json
 import os
@@ -39,7 +41,7 @@ def emit(rec):
             f.write(line + "\n")
 
 
-def timed(fns, reps, warmup=2):
+def timed(fns, reps, warmup=2, spread=None):
     """Median times (ms) of the callables, alternating, device events around each call (a call that reads back ends inside
     its events)."""
     for _ in range(warmup):
@@ -55,6 +57,8 @@ def timed(fns, reps, warmup=2):
             b.record()
             torch.cuda.synchronize()
             ts[k].append(a.elapsed_time(b))
+    if spread is not None:          # max - min of each callable's times: what a later comparison of medians can tell apart
+        spread.extend(float(max(t) - min(t)) for t in ts)
     return [float(np.median(t)) for t in ts]
 
 
@@ -70,9 +74,10 @@ for d in (2, 8):
     noise = 0.01
     lin_block = lambda: SparseBlock(x, z, RBFKernel(l=1.0, sf=1.0, noise=noise), 'vfe', 1e-6, lengthscales=ells, linear=v)
     cov_block = lambda: SparseBlock(x, z, RBFKernel(l=1.0, sf=1.0, noise=noise), 'vfe', 1e-6, lengthscales=ells)
+    spread = []
     t_lin, t_cov, t_eval_lin, t_eval_cov = timed((lambda: lin_block().lml_grad(y), lambda: cov_block().lml_grad(y),
                                                   lambda: lin_block().fit(y).log_marginal_likelihood(),
-                                                  lambda: cov_block().fit(y).log_marginal_likelihood()), args.reps)
+                                                  lambda: cov_block().fit(y).log_marginal_likelihood()), args.reps, spread=spread)
     # the kernels on the same operands: the scaled inputs, an output / a weight matrix of the size and pitch of K_fu / G_fu
     xs, zs = (x / torch.as_tensor(ells).to("cuda")).contiguous(), (z / torch.as_tensor(ells).to("cuda")).contiguous()
     lin = torch.as_tensor(v * ells ** 2).to("cuda")
@@ -94,6 +99,8 @@ for d in (2, 8):
           "d": d, "q": q, "cov_cross_lin_ms": t_cross_lin, "cov_cross_ms": t_cross, "cov_cross_lin_over_twin": t_cross_lin / t_cross,
           "cov_pair_grad_lin_ms": t_pair_lin, "cov_pair_grad_ard_ms": t_pair_ard, "cov_pair_grad_lin_over_twin": t_pair_lin / t_pair_ard,
           "lml_grad_linear_ms": t_lin, "lml_grad_ms": t_cov, "evaluation_linear_ms": t_eval_lin, "evaluation_ms": t_eval_cov,
+          "lml_grad_linear_spread_ms": spread[0], "lml_grad_spread_ms": spread[1], "evaluation_linear_spread_ms": spread[2],
+          "evaluation_spread_ms": spread[3],
           "added_by_linear_ms": added, "d_evaluations_ms": d * t_eval_lin, "added_below_d_evaluations": bool(added < d * t_eval_lin),
           "same_sums_bits": bool(torch.equal(s_l.view(torch.int64), s_a.view(torch.int64)))})
     del x, y, z, kbuf, gbuf, xs, zs, scr_l, scr_a
