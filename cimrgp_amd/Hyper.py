@@ -1,7 +1,8 @@
 """Hyper-parameter learning on the host: the rules every plugin and the model share ("Hyper-parameter learning on
 the host").  One place each for the ARD input scaling, the optimisers' parameter vector [log sf, log l .., log noise, (log v ..), (Z)],
 the L-BFGS-B call with its score of a failed trial point, and the sum of a layer's per-block objectives with its failure
-codes.  Host only: nothing here calls the library."""
+codes; and for the variational sparse GP the vector's further part [mu.ravel(), vech(P) per output] with its driver
+(:func:`pack_posterior`, :func:`maximize_elbo`).  Host only: nothing here calls the library."""
 import numpy as np
 import torch
 
@@ -67,6 +68,65 @@ def minimize_lml(objective, theta0, max_iters, jac=True):
         return -lml, -grad
 
     return minimize(negated, theta0, jac=jac, method='L-BFGS-B', options=dict(maxiter=max_iters))
+
+
+def pack_posterior(mu, p):
+    """The variational part of the parameter vector [log sf, log l .., log s2, (log v ..), mu.ravel(), vech(P_0), vech(P_1) ..]
+    of the variational sparse GP (``SVGP.SVGPBlock``): ``mu`` (q, m), then per output the lower triangle of ``p[c]`` (m x m)
+    row by row, its diagonal as logarithms, which keeps it positive."""
+    mu, p = np.asarray(mu, dtype=np.float64), np.asarray(p, dtype=np.float64)
+    rows, cols = np.tril_indices(p.shape[1])
+    parts = [mu.ravel()]
+    for pc in p:
+        v = pc[rows, cols].copy()
+        v[rows == cols] = np.log(v[rows == cols])
+        parts.append(v)
+    return np.concatenate(parts)
+
+
+def unpack_posterior(vec, q, m):
+    """``(mu (q, m), P (q, m, m) lower triangular)`` of a vector laid out by :func:`pack_posterior`."""
+    vec = np.asarray(vec, dtype=np.float64)
+    rows, cols = np.tril_indices(m)
+    mu = vec[:q * m].reshape(q, m).copy()
+    tri = vec[q * m:].reshape(q, rows.shape[0])
+    p = np.zeros((q, m, m))
+    for c in range(q):
+        v = tri[c].copy()
+        v[rows == cols] = np.exp(v[rows == cols])
+        p[c][rows, cols] = v
+    return mu, p
+
+
+def posterior_gradient(dmu, dp, p):
+    """The gradient w.r.t. :func:`pack_posterior`'s vector from dF/dmu (q, m), dF/dP (q, m, m) and P: the diagonal's
+    entries are w.r.t. log P_ii, P_ii dF/dP_ii."""
+    dmu, dp, p = (np.asarray(a, dtype=np.float64) for a in (dmu, dp, p))
+    rows, cols = np.tril_indices(p.shape[1])
+    parts = [dmu.ravel()]
+    for gc, pc in zip(dp, p):
+        v = gc[rows, cols].copy()
+        v[rows == cols] *= np.diagonal(pc)
+        parts.append(v)
+    return np.concatenate(parts)
+
+
+def maximize_elbo(elbo_grad, theta0, mu0, p0, max_iters):
+    """L-BFGS-B over the whole vector [theta, mu.ravel(), vech(P) per output] on the analytic gradient: ``elbo_grad(theta,
+    mu, P)`` -> ``(F, dtheta, dmu, dP)`` in NumPy.  A trial point that raises LinAlgError scores as :func:`minimize_lml` has
+    it.  Returns (SciPy's result of the negated objective, theta, mu, P) at the optimum."""
+    theta0 = np.asarray(theta0, dtype=np.float64)
+    nt = theta0.shape[0]
+    q, m = np.shape(mu0)
+
+    def objective(vec):
+        mu, p = unpack_posterior(vec[nt:], q, m)
+        f, dtheta, dmu, dp = elbo_grad(vec[:nt], mu, p)
+        return f, np.concatenate([dtheta, posterior_gradient(dmu, dp, p)])
+
+    res = minimize_lml(objective, np.concatenate([theta0, pack_posterior(mu0, p0)]), max_iters)
+    mu, p = unpack_posterior(res.x[nt:], q, m)
+    return res, res.x[:nt].copy(), mu, p
 
 
 def sum_block_objectives(regions, evaluate, n_grad=3):

@@ -25,7 +25,8 @@ import torch
 
 from . import device as dev
 from ._lib import COV_RBF
-from .Hyper import append_linear, minimize_lml, pack_theta, scaled, split_linear, unit_lengthscale, unpack_theta
+from .Hyper import (append_linear, maximize_elbo, minimize_lml, pack_posterior, pack_theta, posterior_gradient, scaled, split_linear,
+                    unit_lengthscale, unpack_posterior, unpack_theta)
 from .KernelClass import RBFKernel, DenseMaternKernel
 from .Posteriors import DenseBlock, NOISE_FRACTION, joint_run
 
@@ -659,6 +660,177 @@ class SparseGP_RBFLinear(SparseGP):
 
     def _not_built(self, what):
         raise TypeError('%s() of %s (a covariance with a linear term) is not yet supported' % (what, self.name))
+
+    def predictive_gradients(self, test_data, budget_bytes=None):
+        self._not_built('predictive_gradients')
+
+    def leave_one_out(self, budget_bytes=None):
+        self._not_built('leave_one_out')
+
+    def loo_log_predictive_density(self, budget_bytes=None):
+        self._not_built('loo_log_predictive_density')
+
+    def predict_with_covariance(self, test_data):
+        self._not_built('predict_with_covariance')
+
+    def posterior_samples_f(self, test_data, size=1, seed=0):
+        self._not_built('posterior_samples_f')
+
+
+class SVIGP_RBF(RegressionMethod):
+    """The reference's ``SVIGP_RBF`` plugin: GPy's ``SVGP`` with the kernel ``RBF(ARD) + Linear(ARD) + White(0.01)`` and a
+    Student-t likelihood (``deg_free`` = 3), optimised on the full batch, predicting the latent function
+    (:class:`~cimrgp_amd.SVGP.SVGPBlock`; DESIGN.md, "Variational sparse GP with a Student-t likelihood").  It is the one
+    plugin whose fit a few gross outliers do not drag.  Inputs and labels are z-scored; ``Z`` follows :class:`SparseGP`'s
+    rule and stays fixed; the likelihood's scale starts at 0.01 (the labels are z-scored); ``white_variance`` is fixed.
+    ``optimize=True`` (the reference's behaviour): L-BFGS-B with the analytic gradient over [log sf, log l .., log s2,
+    log v .., mu.ravel(), vech(P) per output], started from the optimal Gaussian posterior of the VFE fit at the initial
+    hyper-parameters; ``optimize=False`` keeps those hyper-parameters and that posterior.  ``likelihood='gaussian'``,
+    ``ARD=False``, ``linear=False`` and ``nu`` (a Matern covariance) leave the reference's model.  After the fit:
+    ``lengthscales`` ((d,) under ARD, else None), ``linear_variances``, ``likelihood_scale``, ``optimizer_result`` and
+    ``params``, the optimiser's whole vector.  Float32 and the five posterior queries beyond ``predict`` /
+    ``predict_with_variance`` are not built and raise TypeError."""
+    name = 'SVIGP_RBF'
+    INITIAL_SCALE = 0.01
+
+    def __init__(self, num_inducing=100, lengthscale=1., variance=1., linear_variance=1., white_variance=0.01,
+                 likelihood='student_t', deg_free=3., nu=None, Z=None, seed=0, jitter=1e-6, dtype='f64', device=None, optimize=True,
+                 max_iters=1000, ARD=True, linear=True):
+        super(SVIGP_RBF, self).__init__()
+        from .SVGP import LIKELIHOODS
+        if str(likelihood).lower() not in LIKELIHOODS:
+            raise ValueError("likelihood must be 'student_t' or 'gaussian', got %r" % (likelihood,))
+        if int(num_inducing) < 1:
+            raise ValueError('num_inducing must be at least 1')
+        for value, what in ((lengthscale, 'lengthscale'), (variance, 'variance'), (linear_variance, 'linear_variance'),
+                            (deg_free, 'deg_free')):
+            if np.ndim(value) != 0 or not (np.isfinite(value) and value > 0):
+                raise ValueError('%s must be a positive number, got %r' % (what, value))
+        if not (np.isfinite(white_variance) and white_variance >= 0) or not jitter >= 0:
+            raise ValueError('white_variance and jitter must not be negative')
+        self.dtype = dev.as_torch_dtype(dtype)
+        if self.dtype != torch.float64:
+            raise TypeError("%s with dtype='f32' is not yet supported" % self.name)
+        self.nu = None if nu is None else float(nu)
+        self.kernel = self._make_kernel(1.0, variance)           # ValueError for an unsupported nu
+        self.num_inducing, self.likelihood = int(num_inducing), str(likelihood).lower()
+        self._initial = (float(lengthscale), float(variance), float(linear_variance))
+        self.white_variance, self.deg_free, self.jitter = float(white_variance), float(deg_free), float(jitter)
+        self.Z = None if Z is None else np.atleast_2d(np.asarray(Z, dtype=np.float64))
+        self.seed, self.device, self.optimize, self.max_iters = seed, device, optimize, max_iters
+        self.ARD, self.linear = bool(ARD), bool(linear)
+        self.block = self.lengthscales = self.linear_variances = self.likelihood_scale = self.optimizer_result = None
+        self.params = self.inducing_inputs = self.inducing_ids = None
+
+    _make_kernel = SparseGP._make_kernel
+    inducing_draw = SparseGP.inducing_draw
+    _inducing_inputs = SparseGP._inducing_inputs
+
+    def _block(self, theta):
+        """The block at theta = [log sf, log l (1, or d under ARD), log s2, (log v_1 .. log v_d)]."""
+        from .SVGP import SVGPBlock
+        d = int(self._x.shape[1])
+        n_ell = d if self.ARD else None
+        head, lin, _ = split_linear(np.asarray(theta, dtype=np.float64), d if self.linear else 0, n_ell)
+        ell, sf, s2 = unpack_theta(head, n_ell)
+        return SVGPBlock(self._x, self._z, self._make_kernel(1.0 if self.ARD else ell, sf), self.likelihood, self.deg_free, s2,
+                         self.white_variance, self.jitter, lengthscales=ell if self.ARD else None, linear=lin if self.linear else None)
+
+    def _vfe_posterior(self, theta):
+        """(mu (q, m), P (q, m, m)) of the optimal Gaussian q(v) at ``theta``: P = L_B and mu = L_B^-T gamma of the VFE fit
+        with noise s2, on the same L_u (the white variance rides in the fit's jitter)."""
+        from .Sparse import SparseBlock
+        blk = self._block(theta)
+        k, m, q = blk.kernel, blk.m, int(self._y.shape[1])
+        vfe = SparseBlock(self._x, self._z, self._make_kernel(k.l, k.sf, blk.scale), 'vfe', self.jitter + self.white_variance / k.sf,
+                          lengthscales=blk.lengthscales, linear=blk.linear).fit(self._y)
+        lb = torch.tril(vfe.lb[:m, :m])
+        mu = torch.linalg.solve_triangular(lb.t(), vfe.gamma, upper=True)
+        return mu.t().double().cpu().numpy(), np.repeat(lb.double().cpu().numpy()[None], q, axis=0)
+
+    def _elbo_grad(self, theta, mu, p):
+        """``SVGPBlock.elbo_grad`` in NumPy."""
+        to = lambda a: dev.to_device(a, self.dtype, self._x.device)
+        f, dtheta, dmu, dp = self._block(theta).elbo_grad(self._y, to(mu), to(p))
+        return f, dtheta, dmu.double().cpu().numpy(), dp.double().cpu().numpy()
+
+    def _split(self, params):
+        nt = self._n_theta
+        q, m = int(self._y.shape[1]), int(self._z.shape[0])
+        params = np.asarray(params, dtype=np.float64)
+        if params.shape != self.params.shape:
+            raise ValueError('params must have the %d entries of the fitted vector' % self.params.shape[0])
+        return (params[:nt],) + unpack_posterior(params[nt:], q, m)
+
+    def elbo_grad(self, params=None):
+        """``(F, gradient)`` of the evidence lower bound of the fitted data at ``params`` (default: the fitted ``params``):
+        the whole vector [log sf, log l .., log s2, (log v ..), mu.ravel(), vech(P) per output, log-diagonal] and the
+        analytic gradient w.r.t. it.  Raises LinAlgError as :meth:`~cimrgp_amd.SVGP.SVGPBlock.elbo_grad` does."""
+        if self.block is None:
+            raise RuntimeError('call fit() before elbo_grad()')
+        theta, mu, p = self._split(self.params if params is None else params)
+        f, dtheta, dmu, dp = self._elbo_grad(theta, mu, p)
+        return f, np.concatenate([dtheta, posterior_gradient(dmu, dp, p)])
+
+    def elbo(self, params=None):
+        """The evidence lower bound of :meth:`elbo_grad`."""
+        if self.block is None:
+            raise RuntimeError('call fit() before elbo()')
+        return self.elbo_grad(params)[0]
+
+    def _fit(self, train_data):
+        inputs, labels = train_data
+        device = dev.require_gpu(self.device)
+        inputs = np.atleast_2d(np.asarray(inputs, dtype=np.float64))
+        labels = np.atleast_2d(np.asarray(labels, dtype=np.float64))
+        d = inputs.shape[1]
+        self.block = None
+        self._x = dev.to_device(inputs, self.dtype, device)
+        self._y = dev.to_device(labels, self.dtype, device)
+        self._z = dev.to_device(self._inducing_inputs(inputs), self.dtype, device)
+        ell0, sf0, lin0 = self._initial
+        theta = pack_theta(sf0, [ell0] * d if self.ARD else ell0, self.INITIAL_SCALE)
+        if self.linear:
+            theta = append_linear(theta, np.full(d, lin0))
+        self._n_theta = theta.shape[0]
+        mu, p = self._vfe_posterior(theta)
+        if self.optimize:
+            self.optimizer_result, theta, mu, p = maximize_elbo(self._elbo_grad, theta, mu, p, self.max_iters)
+        self.params = np.concatenate([theta, pack_posterior(mu, p)])
+        blk = self._block(theta)
+        self.kernel, self.lengthscales, self.linear_variances = blk.kernel, blk.lengthscales, blk.linear
+        self.likelihood_scale = blk.scale
+        self.block = blk.set_posterior(dev.to_device(mu, self.dtype, device), dev.to_device(p, self.dtype, device))
+        z = self._z.double().cpu().numpy()
+        self.inducing_inputs = z * self.data_std + self.data_mean if self.preprocess else z
+        return True
+
+    def _predict_mean_var(self, test_data, want_var, budget_bytes=None):
+        if self.block is None:
+            raise RuntimeError('call fit() before predict()')
+        xs = dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, self._x.device)
+        shape = (int(xs.shape[0]), int(self._y.shape[1]))
+        mean = torch.empty(shape, dtype=self.dtype, device=xs.device)
+        var = torch.empty(shape, dtype=self.dtype, device=xs.device) if want_var else None
+        self.block.predict(xs, mean, var, budget_bytes=budget_bytes)
+        return mean.double().cpu().numpy(), None if var is None else var.double().cpu().numpy()
+
+    def _predict(self, test_data):
+        """The latent mean, as the reference predicts (``include_likelihood=False``)."""
+        return self._predict_mean_var(test_data, False)[0]
+
+    def predict_with_variance(self, test_data, budget_bytes=None):
+        """Mean (un-z-scored) and the latent variance per output (ns, q), left in z-scored label units as the other
+        plugins leave it.  ``budget_bytes``: work area of the chunked prediction."""
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        mean, var = self._predict_mean_var(test_data, True, budget_bytes)
+        if self.preprocess:
+            mean = self._reverse_trans_labels(mean)
+        return mean, var
+
+    def _not_built(self, what):
+        raise TypeError('%s() of %s (a variational posterior) is not yet supported' % (what, self.name))
 
     def predictive_gradients(self, test_data, budget_bytes=None):
         self._not_built('predictive_gradients')

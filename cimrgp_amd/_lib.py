@@ -172,6 +172,16 @@ SPARSE_LINEAR_SIGNATURES = {
                                         _vp, _vp, _sz, _vp]),
 }
 
+# include/cimrgp_svgp.h: the variational sparse GP with a non-conjugate likelihood
+LIK_GAUSSIAN, LIK_STUDENT_T = 0, 1
+SVGP_SUM_CHUNK = 2048
+SVGP_SIGNATURES = {
+    "cimrgp_svgp_rows": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _dbl, _dbl, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp]),
+    "cimrgp_svgp_moments_scratch_bytes": (_sz, [_i32, _i64, _i64, _i32]),
+    "cimrgp_svgp_moments": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
+}
+
 #: header -> its table, in the include order of include/cimrgp.h
 HEADERS = {
     "cimrgp.h": SIGNATURES,
@@ -186,6 +196,7 @@ HEADERS = {
     "cimrgp_layer_ard.h": LAYER_ARD_SIGNATURES,
     "cimrgp_sparse_post.h": SPARSE_POST_SIGNATURES,
     "cimrgp_sparse_linear.h": SPARSE_LINEAR_SIGNATURES,
+    "cimrgp_svgp.h": SVGP_SIGNATURES,
 }
 
 

@@ -6,6 +6,7 @@
 //                                     (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32, Mx<T> in common.hpp); the partial
 //                                     tile goes to scratch
 //                    k_wsyrk_reduce   adds the slices' partials in slice order, adds diag_add, writes lower(C) and g
+//                  cimrgp_svgp_moments (include/cimrgp_svgp.h) is the same pair with g = A^T r, r not weighted (RAW)
 //   sparse_lambda  k_sparse_rowsq (a wave per row: q_i, lambda_i) and k_sparse_sums (one workgroup: the three sums in a
 //                  fixed order, w = 1 / lambda)
 //   sparse_tail    k_sparse_tail (a wave per test row: W* gamma, sum A*^2, sum W*^2)
@@ -100,7 +101,8 @@ static __device__ __forceinline__ uint2 frag(const T* __restrict__ op, int pitch
 
 // blockIdx.x = tile + tiles * slice; tiles run down the columns of the lower triangle: (0,0) (1,0) .. (t-1,0) (1,1) ..
 // EDGE: the tile touches column m or the slice touches row n (ragged m, the last slice): bounds logic on every load.
-template <typename T, bool EDGE>
+// RAW (cimrgp_svgp_moments, include/cimrgp_svgp.h): the g operand is r itself, not w r.
+template <typename T, bool EDGE, bool RAW>
 static __device__ __forceinline__ void wsyrk_tile(T* __restrict__ smem, const T* __restrict__ A, int64_t lda, int n, int m,
                                                   const T* __restrict__ w, const T* __restrict__ r, int q, int ti, int tj, int k0,
                                                   int k1, T* __restrict__ ctile, T* __restrict__ gtile)
@@ -153,7 +155,8 @@ static __device__ __forceinline__ void wsyrk_tile(T* __restrict__ smem, const T*
 #pragma unroll
             for (int e = 0; e < G::GPT; ++e) {
                 const int idx = tid + 256 * e, kk = kb + idx / WS_GQ, c = idx % WS_GQ;
-                rg[e] = (c < q && kk < k1) ? w[kk] * r[(int64_t)kk * q + c] : (T)0;
+                if constexpr (RAW) rg[e] = (c < q && kk < k1) ? r[(int64_t)kk * q + c] : (T)0;
+                else rg[e] = (c < q && kk < k1) ? w[kk] * r[(int64_t)kk * q + c] : (T)0;
             }
         }
     };
@@ -233,7 +236,7 @@ static __device__ __forceinline__ void wsyrk_tile(T* __restrict__ smem, const T*
     }
 }
 
-template <typename T>
+template <typename T, bool RAW = false>
 __global__ __launch_bounds__(256, 2)
 void k_wsyrk_tn(const T* __restrict__ A, int64_t lda, int n, int m, const T* __restrict__ w, const T* __restrict__ r, int q,
                 int tiles1d, int tiles, int slice_len, T* __restrict__ cpart, T* __restrict__ gpart)
@@ -249,8 +252,8 @@ void k_wsyrk_tn(const T* __restrict__ A, int64_t lda, int n, int m, const T* __r
     T* ctile = cpart + ((int64_t)slice * tiles + tile) * (WS_GT * WS_GT);
     T* gtile = (r != nullptr && tj == 0) ? gpart + ((int64_t)slice * tiles1d + ti) * (WS_GT * MAXQ) : nullptr;
     const bool edge = (ti + 1) * WS_GT > m || (k1 - k0) % G::KC != 0;
-    if (edge) wsyrk_tile<T, true>(smem, A, lda, n, m, w, r, q, ti, tj, k0, k1, ctile, gtile);
-    else      wsyrk_tile<T, false>(smem, A, lda, n, m, w, r, q, ti, tj, k0, k1, ctile, gtile);
+    if (edge) wsyrk_tile<T, true, RAW>(smem, A, lda, n, m, w, r, q, ti, tj, k0, k1, ctile, gtile);
+    else      wsyrk_tile<T, false, RAW>(smem, A, lda, n, m, w, r, q, ti, tj, k0, k1, ctile, gtile);
 }
 
 // blockIdx.x < tiles * 64: 256 elements of one tile (two rows of it); beyond: 256 elements of g.  Slices are added in
@@ -378,14 +381,14 @@ static inline int64_t ws_gpart_elems(int64_t n, int64_t m) { return ws_slices(n,
 
 }  // namespace
 
-template <typename T>
+template <typename T, bool RAW = false>
 static int wsyrk_tn_run(const T* a, int64_t n, int64_t m, int64_t lda, const T* w, const T* r, int q, double diag_add, T* c, int64_t ldc,
                         T* g, T* scratch, hipStream_t st, const char* fn)
 {
     const int64_t t1 = ws_tiles_1d(m), tiles = ws_tiles(m), len = ws_slice_len(n, m), slices = ws_slices(n, m);
     T* cpart = scratch;
     T* gpart = scratch + ws_cpart_elems(n, m);
-    hipLaunchKernelGGL((k_wsyrk_tn<T>), dim3((unsigned)(tiles * slices)), dim3(256), 0, st, a, lda, (int)n, (int)m, w, r, q, (int)t1,
+    hipLaunchKernelGGL((k_wsyrk_tn<T, RAW>), dim3((unsigned)(tiles * slices)), dim3(256), 0, st, a, lda, (int)n, (int)m, w, r, q, (int)t1,
                        (int)tiles, (int)len, cpart, gpart);
     CIMRGP_LAUNCH_CHECK(fn);
     const int64_t gblocks = r ? (m * q + 255) / 256 : 0;
@@ -407,10 +410,12 @@ size_t cimrgp_wsyrk_tn_scratch_bytes(int dtype, int64_t n, int64_t m, int q)
     return (size_t)(ws_cpart_elems(n, m) + (q > 0 ? ws_gpart_elems(n, m) : 0)) * elem_bytes(dtype);
 }
 
-int cimrgp_wsyrk_tn(int dtype, const void* a_dev, int64_t n, int64_t m, int64_t lda, const void* w_dev, const void* r_dev, int q,
-                    double diag_add, void* c_dev, int64_t ldc, void* g_dev, void* scratch_dev, size_t scratch_bytes, void* stream)
+// cimrgp_wsyrk_tn and, with `raw` (g = A^T r, r not weighted), cimrgp_svgp_moments (include/cimrgp_svgp.h).  Without r the
+// two are the same launch of the same instance.
+static int wsyrk_tn_impl(const char* fn, bool raw, int dtype, const void* a_dev, int64_t n, int64_t m, int64_t lda, const void* w_dev,
+                         const void* r_dev, int q, double diag_add, void* c_dev, int64_t ldc, void* g_dev, void* scratch_dev,
+                         size_t scratch_bytes, void* stream)
 {
-    const char* fn = "cimrgp_wsyrk_tn";
     CIMRGP_REQUIRE(dtype_known(dtype), fn, "unknown dtype");
     CIMRGP_REQUIRE(a_dev && w_dev && c_dev && scratch_dev, fn, "null pointer");
     CIMRGP_REQUIRE(r_dev == nullptr || g_dev != nullptr, fn, "null pointer (g)");
@@ -424,9 +429,31 @@ int cimrgp_wsyrk_tn(int dtype, const void* a_dev, int64_t n, int64_t m, int64_t 
     CIMRGP_REQUIRE(scratch_bytes >= cimrgp_wsyrk_tn_scratch_bytes(dtype, n, m, q), fn, "scratch too small");
     return with_dtype(dtype, fn, [&](auto tag) {
         using T = decltype(tag);
+        if (raw && r_dev != nullptr)
+            return wsyrk_tn_run<T, true>((const T*)a_dev, n, m, lda, (const T*)w_dev, (const T*)r_dev, q, diag_add, (T*)c_dev, ldc,
+                                         (T*)g_dev, (T*)scratch_dev, stream_of(stream), fn);
         return wsyrk_tn_run<T>((const T*)a_dev, n, m, lda, (const T*)w_dev, (const T*)r_dev, q, diag_add, (T*)c_dev, ldc, (T*)g_dev,
                                (T*)scratch_dev, stream_of(stream), fn);
     });
+}
+
+int cimrgp_wsyrk_tn(int dtype, const void* a_dev, int64_t n, int64_t m, int64_t lda, const void* w_dev, const void* r_dev, int q,
+                    double diag_add, void* c_dev, int64_t ldc, void* g_dev, void* scratch_dev, size_t scratch_bytes, void* stream)
+{
+    return wsyrk_tn_impl("cimrgp_wsyrk_tn", false, dtype, a_dev, n, m, lda, w_dev, r_dev, q, diag_add, c_dev, ldc, g_dev, scratch_dev,
+                         scratch_bytes, stream);
+}
+
+size_t cimrgp_svgp_moments_scratch_bytes(int dtype, int64_t n, int64_t m, int q)
+{
+    return cimrgp_wsyrk_tn_scratch_bytes(dtype, n, m, q);
+}
+
+int cimrgp_svgp_moments(int dtype, const void* a_dev, int64_t n, int64_t m, int64_t lda, const void* w_dev, const void* r_dev, int q,
+                        void* c_dev, int64_t ldc, void* g_dev, void* scratch_dev, size_t scratch_bytes, void* stream)
+{
+    return wsyrk_tn_impl("cimrgp_svgp_moments", true, dtype, a_dev, n, m, lda, w_dev, r_dev, q, 0.0, c_dev, ldc, g_dev, scratch_dev,
+                         scratch_bytes, stream);
 }
 
 // cimrgp_sparse_lambda and cimrgp_sparse_lambda_dev: `dev_entry` says which; the first takes `noise`, the second noise_dev.

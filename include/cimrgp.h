@@ -506,4 +506,8 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
  * pair-contraction twins: include/cimrgp_sparse_linear.h. */
 #include "cimrgp_sparse_linear.h"
 
+/* The variational sparse GP with a non-conjugate likelihood (Gaussian or Student-t): the Gauss-Hermite row pass over A
+ * and W: include/cimrgp_svgp.h. */
+#include "cimrgp_svgp.h"
+
 #endif /* CIMRGP_H */
