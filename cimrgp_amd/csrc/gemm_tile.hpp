@@ -103,8 +103,16 @@ static __device__ __forceinline__ void gemm_tile(unsigned char* smem, T* __restr
     // chain itself computes C - A B^T: the 64 C loads per lane are independent and in flight
     // together with the first operand tiles, and the epilogue is stores only.  (A read-modify-
     // write epilogue serialises 64 dependent load->store round trips per lane.)
+    // FP32 (C - A B^T only): the C tile is loaded here all the same but kept APART, the accumulators start at zero and C is
+    // added once in the epilogue.  Started as C, an entry of size one took every one of its K products with a rounding at its
+    // own ulp -- n roundings over a factorisation where one subtraction per panel makes n / 256: the diagonal of an FP32
+    // factor drifted to 12 x LAPACK's forward error at n = 10240 (HISTORY.md, dense SPD tests).  FP64 keeps the chain on C.
+    // (not the 128-tile, W = 4: a second set of 64 registers per lane does not fit beside its accumulators without spilling;
+    //  it serves the few FP32 updates too large for the 64-tiles and too small for the persistent kernel)
+    constexpr bool APART = sizeof(T) == 4 && !ADD && W <= 2;
     const bool diag_tile = LOWER && (ti == tj);
     acc_t acc[W][W];
+    acc_t cini[APART ? W : 1][APART ? W : 1];
 #pragma unroll
     for (int mi = 0; mi < W; ++mi) {
 #pragma unroll
@@ -114,12 +122,15 @@ static __device__ __forceinline__ void gemm_tile(unsigned char* smem, T* __restr
             for (int r = 0; r < 4; ++r) {
                 const int gr = row0 + wr * 16 * W + mi * 16 + X::crow(lane, r);
                 // unconditional load from a clamped (always valid) address, then select
+                T v;
                 if (EDGE) {
-                    const T v = C[(int64_t)min(gr, M - 1) * ldc + min(gc, N - 1)];
-                    acc[mi][ni][r] = (gr < M && gc < N && (!diag_tile || gc <= gr)) ? v : (T)0;
+                    v = C[(int64_t)min(gr, M - 1) * ldc + min(gc, N - 1)];
+                    v = (gr < M && gc < N && (!diag_tile || gc <= gr)) ? v : (T)0;
                 } else {
-                    acc[mi][ni][r] = C[(int64_t)gr * ldc + gc];     // junk above the diagonal is never stored
+                    v = C[(int64_t)gr * ldc + gc];                  // junk above the diagonal is never stored
                 }
+                if constexpr (APART) { cini[mi][ni][r] = v; acc[mi][ni][r] = (T)0; }
+                else acc[mi][ni][r] = v;
             }
         }
     }
@@ -129,7 +140,10 @@ static __device__ __forceinline__ void gemm_tile(unsigned char* smem, T* __restr
 #pragma unroll
     for (int mi = 0; mi < W; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < W; ++ni) asm volatile("" : "+v"(acc[mi][ni]));
+        for (int ni = 0; ni < W; ++ni) {
+            if constexpr (APART) asm volatile("" : "+v"(cini[mi][ni]));
+            else asm volatile("" : "+v"(acc[mi][ni]));
+        }
     __syncthreads();
 
     for (int kt = 0; kt < nkt; ++kt) {
@@ -171,7 +185,9 @@ static __device__ __forceinline__ void gemm_tile(unsigned char* smem, T* __restr
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int gr = row0 + wr * 16 * W + mi * 16 + X::crow(lane, r);
-                if ((!EDGE || (gr < Mv && gc < Nv)) && (!diag_tile || gc <= gr)) C[(int64_t)gr * ldc + gc] = acc[mi][ni][r];
+                T out = acc[mi][ni][r];
+                if constexpr (APART) out += cini[mi][ni][r];        // acc holds -A B^T
+                if ((!EDGE || (gr < Mv && gc < Nv)) && (!diag_tile || gc <= gr)) C[(int64_t)gr * ldc + gc] = out;
             }
         }
     }

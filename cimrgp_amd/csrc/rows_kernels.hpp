@@ -108,13 +108,20 @@ void k_rows_step(T* __restrict__ P, int64_t ldp, int M, const T* __restrict__ Lr
 #pragma unroll
         for (int i = 0; i < RS::NCP / 2; ++i) stg[i] = *reinterpret_cast<const v4u*>(src + (i * 16 + st16) * X::EPC);
     }
+    // FP32: B is kept apart and the products are accumulated from zero, B added once where T_j is formed (gemm_tile.hpp has
+    // the reason: started as B, every entry took each of its products with a rounding at its own size)
+    constexpr bool APART = sizeof(T) == 4;
     acc_t acc[4];
+    acc_t bini[APART ? 4 : 1];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-            acc[j][r] = (b_zero == 0) ? Prow[(int64_t)min(X::crow(lane, r), mrows - 1) * ldp + SB * j + ctile]
+        for (int r = 0; r < 4; ++r) {
+            const T v = (b_zero == 0) ? Prow[(int64_t)min(X::crow(lane, r), mrows - 1) * ldp + SB * j + ctile]
                       : (b_zero == 2 && row0 + X::crow(lane, r) == SB * j + ctile) ? (T)1 : (T)0;
+            if constexpr (APART) { bini[j][r] = v; acc[j][r] = (T)0; }
+            else acc[j][r] = v;
+        }
 
     // right-operand rows of this lane: rows SB j + ctile of the panel's row block of L, and of the inverses
     const T* lp[4];
@@ -205,8 +212,11 @@ void k_rows_step(T* __restrict__ P, int64_t ldp, int M, const T* __restrict__ Lr
             if (pos + RS::RING2 < RS::P2_TOTAL) ROWS_P2_LOAD(pos + RS::RING2)
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-            *reinterpret_cast<T*>(tbuf + X::crow(lane, r) * RS::TSTR + ctile * (int)sizeof(T)) = acc[j][r];
+        for (int r = 0; r < 4; ++r) {
+            T tj = acc[j][r];
+            if constexpr (APART) tj += bini[j][r];
+            *reinterpret_cast<T*>(tbuf + X::crow(lane, r) * RS::TSTR + ctile * (int)sizeof(T)) = tj;
+        }
         lds_barrier();                                                   // T_j complete
         acc_t x = acc_zero<T>();
         const unsigned char* tbase = tbuf + fn * RS::TSTR + fq * 32;
