@@ -846,3 +846,155 @@ class SVIGP_RBF(RegressionMethod):
 
     def posterior_samples_f(self, test_data, size=1, seed=0):
         self._not_built('posterior_samples_f')
+
+
+class BGPLVM(PosteriorQueries):
+    """The reference's ``BGPLVM`` plugin: gpflow's ``BayesianGPLVM`` used as a sparse VFE regression whose inputs are not
+    points but Gaussians x_i ~ N(inputs_i, diag X_var_i) (:class:`~cimrgp_amd.Psi.UncertainInputBlock`; DESIGN.md, "Sparse GP
+    regression on uncertain inputs").  The defaults are the reference's: ``num_inducing`` = 100 rows drawn as
+    :meth:`SparseGP.inducing_draw` draws them, the unit RBF with one length-scale per dimension (``ARD=True``), gpflow's
+    likelihood variance ``noise`` = 1.0 (on the z-scored labels), ``X_var=None`` = ``inputs.var() * 0.01`` over all entries of
+    the z-scored inputs, and no optimisation.  ``X_var``: the variances of the inputs in the caller's (squared) units, a
+    scalar, a (d,) vector or an (n, d) array, checked finite and not negative; it is scaled with the z-scoring.  A scalar or
+    a vector takes the shared-variance route (existing covariance and matrix-core calls), an (n, d) array the psi kernels
+    (cimrgp_psi1, cimrgp_psi2).  ``optimize=True``: L-BFGS-B over [log sf, log l_1 .. log l_d, log noise] (one log l without
+    ARD) on SciPy's two-point differences of the bound, Z and the inputs' distributions fixed.  After the fit:
+    ``lengthscales`` ((d,) under ARD, else None), ``inducing_inputs`` (Z in the caller's units), ``kernel``,
+    ``optimizer_result``.  ``predict(test, test_var=)`` takes uncertain test inputs too.  Float32, the five posterior
+    queries beyond ``predict`` / ``predict_with_variance`` and the variance at uncertain test inputs are not built and
+    raise TypeError."""
+    name = 'BGPLVM'
+    X_VAR_FRACTION = 0.01
+
+    def __init__(self, num_inducing=100, X_var=None, noise=1.0, lengthscale=1., variance=1., ARD=True, Z=None, seed=0, jitter=1e-6,
+                 device=None, optimize=False, max_iters=200):
+        super(BGPLVM, self).__init__()
+        if int(num_inducing) < 1:
+            raise ValueError('num_inducing must be at least 1')
+        for value, what in ((noise, 'noise'), (variance, 'variance')):
+            if np.ndim(value) != 0 or not (np.isfinite(value) and value > 0):
+                raise ValueError('%s must be a positive number, got %r' % (what, value))
+        ls = np.asarray(lengthscale, dtype=np.float64)
+        if ls.ndim > 1 or ls.size == 0 or not (np.isfinite(ls).all() and (ls > 0).all()):
+            raise ValueError('lengthscale must be positive and finite in every entry, got %r' % (lengthscale,))
+        if ls.ndim == 1 and not ARD:
+            raise ValueError('a sequence of length-scales needs ARD=True')
+        if not jitter >= 0:
+            raise ValueError('jitter must not be negative')
+        if X_var is not None:
+            X_var = np.asarray(X_var, dtype=np.float64)
+            if X_var.ndim > 2 or not (np.isfinite(X_var).all() and (X_var >= 0).all()):
+                raise ValueError('X_var must be a scalar, a (d,) vector or an (n, d) array of finite variances, none negative')
+        self.num_inducing, self.X_var, self.ARD = int(num_inducing), X_var, bool(ARD)
+        self._initial = (ls.copy() if ls.ndim else float(ls), float(variance), float(noise))
+        self.Z = None if Z is None else np.atleast_2d(np.asarray(Z, dtype=np.float64))
+        self.seed, self.jitter, self.device, self.optimize, self.max_iters = seed, float(jitter), device, optimize, max_iters
+        self.dtype = torch.float64
+        self.nu = None
+        self.kernel = RBFKernel(l=1.0 if self.ARD else self._initial[0], sf=variance, noise=noise)
+        self.block = self.lengthscales = self.inducing_inputs = self.inducing_ids = self.optimizer_result = None
+
+    inducing_draw = SparseGP.inducing_draw
+    _inducing_inputs = SparseGP._inducing_inputs
+
+    def _variances(self, var, rows, d, what):
+        """``var`` (the caller's units; a scalar, (d,) or (rows, d)) in the z-scored units: a host (d,) vector, or a
+        (rows, d) device tensor."""
+        var = np.asarray(var, dtype=np.float64)
+        if var.ndim > 2 or (var.ndim == 1 and var.shape != (d,)) or (var.ndim == 2 and var.shape != (rows, d)):
+            raise ValueError('%s must be a scalar, a (%d,) vector or a (%d, %d) array, got shape %r' % (what, d, rows, d, var.shape))
+        if not (np.isfinite(var).all() and (var >= 0).all()):
+            raise ValueError('%s must be finite and not negative' % what)
+        if self.preprocess:
+            var = var / np.asarray(self.data_std, dtype=np.float64) ** 2
+        if var.ndim == 2:
+            return dev.to_device(var, self.dtype, self._x.device)
+        return np.full(d, float(var)) if var.ndim == 0 else var
+
+    def _block(self, ell, sf, noise):
+        """The block at (ell, sf, noise); ARD: ``ell`` is the (d,) vector and the kernel's own length-scale 1."""
+        from .Psi import UncertainInputBlock
+        if self.ARD:
+            return UncertainInputBlock(self._x, self._var, self._z, RBFKernel(l=1.0, sf=sf, noise=noise), self.jitter, lengthscales=ell)
+        return UncertainInputBlock(self._x, self._var, self._z, RBFKernel(l=ell, sf=sf, noise=noise), self.jitter)
+
+    def _fit(self, train_data):
+        inputs, labels = train_data
+        device = dev.require_gpu(self.device)
+        inputs = np.atleast_2d(np.asarray(inputs, dtype=np.float64))
+        labels = np.atleast_2d(np.asarray(labels, dtype=np.float64))
+        n, d = inputs.shape
+        ell, sf, noise = self._initial
+        if np.ndim(ell) > 0 and ell.shape[0] != d:
+            raise ValueError('lengthscale has %d entries, the inputs have %d dimensions' % (ell.shape[0], d))
+        if self.ARD:
+            ell = np.full(d, ell) if np.ndim(ell) == 0 else ell.copy()
+        self.block = None
+        self._x = dev.to_device(inputs, self.dtype, device)
+        self._y = dev.to_device(labels, self.dtype, device)
+        self._z = dev.to_device(self._inducing_inputs(inputs), self.dtype, device)
+        if self.X_var is None:
+            self._var = np.full(d, float(inputs.var()) * self.X_VAR_FRACTION)         # of the inputs as the model sees them
+        else:
+            self._var = self._variances(self.X_var, n, d, 'X_var')
+        if self.optimize:
+            n_ell = d if self.ARD else None
+            objective = lambda theta: self._block(*unpack_theta(theta, n_ell)).fit(self._y).bound()
+            self.optimizer_result = minimize_lml(objective, pack_theta(sf, ell, noise), self.max_iters, jac=None)
+            ell, sf, noise = unpack_theta(self.optimizer_result.x, n_ell)
+        self.block = self._block(ell, sf, noise).fit(self._y)
+        self.kernel, self.lengthscales = self.block.kernel, ell if self.ARD else None
+        z = self._z.double().cpu().numpy()
+        self.inducing_inputs = z * self.data_std + self.data_mean if self.preprocess else z
+        return True
+
+    def elbo(self):
+        """The evidence lower bound of the fitted data, F - KL (z-scored units)."""
+        return self._fitted_block('elbo').elbo()
+
+    def kl_divergence(self):
+        """KL(q(X) || N(0, I)) of the (z-scored) inputs' distributions: gpflow's default prior."""
+        return self._fitted_block('kl_divergence').kl()
+
+    def predict(self, test_data, test_var=None, budget_bytes=None):
+        """The predictive mean; ``test_var`` (a scalar, (d,) or (ns, d), the caller's units): the test inputs are Gaussians
+        N(test_data, diag test_var) and the mean is taken under them (Psi1 of the test inputs in place of K(X*, Z))."""
+        blk = self._fitted_block('predict')
+        if test_var is None:
+            return super(BGPLVM, self).predict(test_data)
+        test_data = np.atleast_2d(np.asarray(test_data, dtype=np.float64))
+        xs_var = self._variances(test_var, test_data.shape[0], test_data.shape[1], 'test_var')
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        xs = self._test_inputs(test_data)
+        mean = torch.empty((xs.shape[0], self._y.shape[1]), dtype=self.dtype, device=xs.device)
+        blk.predict(xs, mean, None, budget_bytes=budget_bytes, xs_var=xs_var)
+        mean = mean.double().cpu().numpy()
+        return self._reverse_trans_labels(mean) if self.preprocess else mean
+
+    def predict_with_variance(self, test_data, include_noise=False, test_var=None, budget_bytes=None):
+        """Mean (un-z-scored) and predictive variance, left in z-scored label units as the other plugins leave it (latent;
+        ``include_noise`` adds the noise).  With ``test_var`` the variance is not built: TypeError (:meth:`predict` gives
+        the mean)."""
+        if test_var is not None:
+            raise TypeError('the predictive variance of %s at uncertain test inputs is not yet supported' % self.name)
+        self._fitted_block('predict_with_variance')
+        return self._predict_with_variance(test_data, include_noise=include_noise, budget_bytes=budget_bytes)
+
+    def _not_built(self, what):
+        raise TypeError('%s() of %s (uncertain inputs) is not yet supported' % (what, self.name))
+
+    def predictive_gradients(self, test_data, budget_bytes=None):
+        self._not_built('predictive_gradients')
+
+    def leave_one_out(self, budget_bytes=None):
+        self._not_built('leave_one_out')
+
+    def loo_log_predictive_density(self, budget_bytes=None):
+        self._not_built('loo_log_predictive_density')
+
+    def predict_with_covariance(self, test_data):
+        self._not_built('predict_with_covariance')
+
+    def posterior_samples_f(self, test_data, size=1, seed=0):
+        self._not_built('posterior_samples_f')

@@ -384,9 +384,10 @@ class SparseBlock(object):
                             extra, None if mean is None else mean[s0:s1], None if var is None else var[s0:s1], accumulate)
         return mean, var
 
-    def _star_chunks(self, xs, budget_bytes=None):
+    def _star_chunks(self, xs, budget_bytes=None, cross=None):
         """(s0, s1, A*, W*) of every chunk of ``chunk_rows(budget_bytes)`` test rows: A* = K(xs[s0:s1], Z) L_u^-T and
-        W* = A* L_B^-T in two work buffers that the next chunk overwrites."""
+        W* = A* L_B^-T in two work buffers that the next chunk overwrites.  ``cross(s0, s1, out)``: what fills ``out`` with
+        the chunk's rows in place of K(xs[s0:s1], Z) (``Psi.UncertainInputBlock``: Psi1 of uncertain test inputs)."""
         m, ns = self.m, int(xs.shape[0])
         step = self.chunk_rows(budget_bytes)
         astar = wstar = None
@@ -396,7 +397,10 @@ class SparseBlock(object):
             if astar is None:
                 astar = dev.alloc_matrix(min(step, ns), m, xs.dtype, xs.device)
                 wstar = torch.empty_like(astar)
-            self.cov.cross(self.cov.inputs(xs[s0:s1]), self._zs, out=astar)
+            if cross is None:
+                self.cov.cross(self.cov.inputs(xs[s0:s1]), self._zs, out=astar)
+            else:
+                cross(s0, s1, astar)
             dev.trsm_rows(self.lu, m, self.ws_u, astar, rows)
             wstar[:rows].copy_(astar[:rows])
             dev.trsm_rows(self.lb, m, self.ws_b, wstar, rows)

@@ -9,13 +9,14 @@ GPU, computing does.
 from .IndexSetGenerator import IndexSetUniform
 from .KernelClass import RBFKernel, DenseMaternKernel, MaternKernel, LaplacianEigenpairs, SparseKernel
 from .BasisInterval import BasisInterval
-from .RegressionInput import RegressionMethod, GP_RBF, GP_Matern, SparseGP, SGP_FITC, SparseGP_RBF, SparseGP_RBFLinear, SVIGP_RBF
+from .RegressionInput import RegressionMethod, GP_RBF, GP_Matern, SparseGP, SGP_FITC, SparseGP_RBF, SparseGP_RBFLinear, SVIGP_RBF, BGPLVM
 from .Inputs import space_filling_order
 from .Posteriors import DensePosterior, DenseBlock
 from .Sparse import SparseBlock, SparsePosterior
 from .SVGP import SVGPBlock
+from .Psi import UncertainInputBlock
 from .MRGP import MultiResolutionGaussianProcess
 from . import _lib, device, dist
 
 __all__ = ["IndexSetUniform", "RBFKernel", "DenseMaternKernel", "MaternKernel", "LaplacianEigenpairs", "BasisInterval", "RegressionMethod",
-           "GP_RBF", "GP_Matern", "SparseGP", "SGP_FITC", "SparseGP_RBF", "SparseGP_RBFLinear", "SVIGP_RBF", "DensePosterior", "DenseBlock", "SparseBlock", "SVGPBlock", "SparseKernel", "SparsePosterior", "MultiResolutionGaussianProcess", "space_filling_order", "device", "dist"]
+           "GP_RBF", "GP_Matern", "SparseGP", "SGP_FITC", "SparseGP_RBF", "SparseGP_RBFLinear", "SVIGP_RBF", "BGPLVM", "DensePosterior", "DenseBlock", "SparseBlock", "SVGPBlock", "UncertainInputBlock", "SparseKernel", "SparsePosterior", "MultiResolutionGaussianProcess", "space_filling_order", "device", "dist"]

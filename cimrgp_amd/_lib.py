@@ -182,6 +182,15 @@ SVGP_SIGNATURES = {
     "cimrgp_svgp_moments": (_i32, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
 }
 
+# include/cimrgp_psi.h: the psi statistics of the RBF covariance under Gaussian inputs
+PSI2_TILE, PSI2_TARGET_WGS, PSI2_MIN_SLICE, PSI2_SLICE_ALIGN = 64, 2048, 64, 16
+PSI_SIGNATURES = {
+    "cimrgp_psi1": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _dbl, _vp, _i64, _vp]),
+    "cimrgp_psi2_slices": (_i32, [_i64, _i64]),
+    "cimrgp_psi2_scratch_bytes": (_sz, [_i32, _i64, _i64, _i32]),
+    "cimrgp_psi2": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _dbl, _vp, _i64, _vp, _sz, _vp, _vp]),
+}
+
 #: header -> its table, in the include order of include/cimrgp.h
 HEADERS = {
     "cimrgp.h": SIGNATURES,
@@ -196,6 +205,7 @@ HEADERS = {
     "cimrgp_layer_ard.h": LAYER_ARD_SIGNATURES,
     "cimrgp_sparse_post.h": SPARSE_POST_SIGNATURES,
     "cimrgp_sparse_linear.h": SPARSE_LINEAR_SIGNATURES,
+    "cimrgp_psi.h": PSI_SIGNATURES,
     "cimrgp_svgp.h": SVGP_SIGNATURES,
 }
 

@@ -1,0 +1,49 @@
+"""Wrappers of include/cimrgp_psi.h: the psi statistics of the RBF covariance under Gaussian inputs ("Sparse GP
+regression on uncertain inputs").  Each is one ``device._call``, as the wrappers of ``device.py`` are."""
+import torch
+
+from .device import _byte_scratch, _call, _given, _size, alloc_matrix
+
+
+def _operands(mu, s, z, ell):
+    """(n, m, d) of the operands, which must be contiguous and of one dtype; ``ell``: device float64 (d,)."""
+    if mu.dim() != 2 or s.shape != mu.shape or z.dim() != 2 or z.shape[1] != mu.shape[1]:
+        raise ValueError("mu and s must be (n, d) and z (m, d)")
+    if s.dtype != mu.dtype or z.dtype != mu.dtype:
+        raise ValueError("mu, s and z must have one dtype")
+    if not (mu.is_contiguous() and s.is_contiguous() and z.is_contiguous()):
+        raise ValueError("mu, s and z must be contiguous")
+    if ell.dtype != torch.float64 or ell.numel() != mu.shape[1] or not ell.is_contiguous() or ell.device != mu.device:
+        raise ValueError("ell must hold the d length-scales as float64 on the operands' device")
+    return int(mu.shape[0]), int(z.shape[0]), int(mu.shape[1])
+
+
+def psi1(mu, s, z, ell, sf2, out=None):
+    """Psi1 (n x m) = E k(x, Z) for x_i ~ N(mu_i, diag s_i) into ``out`` or a new padded buffer (cimrgp_psi1)."""
+    n, m, d = _operands(mu, s, z, ell)
+    if out is None:
+        out = alloc_matrix(n, m, mu.dtype, mu.device)
+    _call("cimrgp_psi1", mu.dtype, mu, s, z, n, m, d, ell, sf2, out, out.stride(0))
+    return out
+
+
+def psi2_slices(n, m):
+    """The number of row slices cimrgp_psi2 cuts n rows into for m inducing inputs (the header's rule); 0 outside its limits."""
+    return _size("cimrgp_psi2_slices", n, m)
+
+
+def psi2_scratch_bytes(n, m, d, dtype):
+    return _size("cimrgp_psi2_scratch_bytes", dtype, n, m, d)
+
+
+def psi2(mu, s, z, ell, sf2, out=None, scratch=None, bad=None):
+    """lower(out)[:m, :m] = Psi2 = sum_i E k(Z, x_i) k(x_i, Z) (cimrgp_psi2).  Returns (out, bad): out is allocated with a
+    padded pitch if None, the scratch for this call only if None; bad: device float64 (1,), the number of rows with a
+    negative or non-finite variance (they add nothing)."""
+    n, m, d = _operands(mu, s, z, ell)
+    if out is None:
+        out = alloc_matrix(m, m, mu.dtype, mu.device)
+    bad = _given(bad, (1,), mu, torch.float64)
+    scratch = _byte_scratch(psi2_scratch_bytes(n, m, d, mu.dtype), mu.device, scratch)
+    _call("cimrgp_psi2", mu.dtype, mu, s, z, n, m, d, ell, sf2, out, out.stride(0), scratch, scratch.numel(), bad)
+    return out, bad

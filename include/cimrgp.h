@@ -506,6 +506,10 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
  * pair-contraction twins: include/cimrgp_sparse_linear.h. */
 #include "cimrgp_sparse_linear.h"
 
+/* The psi statistics of the RBF covariance under Gaussian inputs, for sparse GP regression on uncertain inputs:
+ * include/cimrgp_psi.h. */
+#include "cimrgp_psi.h"
+
 /* The variational sparse GP with a non-conjugate likelihood (Gaussian or Student-t): the Gauss-Hermite row pass over A
  * and W: include/cimrgp_svgp.h. */
 #include "cimrgp_svgp.h"
