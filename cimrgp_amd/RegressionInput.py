@@ -1,9 +1,26 @@
-"""Exact-GP regression plugin: the drop-in boundary of the dense path.
+"""The regression plugins: the drop-in boundary of the package.
 
 ``RegressionMethod`` mirrors the reference's plugin base class
 (RegressionInput.py:10-52): ``fit(train_data=[X, Y]) -> bool`` and
 ``predict(test_data) -> ndarray`` with column-wise z-scoring of inputs and
-labels (population std) done by the base class.  ``GP_RBF`` replaces the
+labels (population std) done by the base class.  Nine plugins stand on it, over two bases:
+
+    PosteriorQueries          a plugin that holds one fitted block: predict_with_variance and the five further queries
+                              (predictive_gradients, leave_one_out, loo_log_predictive_density, predict_with_covariance,
+                              posterior_samples_f), each written once; a plugin whose block does not answer the five names
+                              the reason in ``unsupported`` and they raise TypeError, from one place
+      GP_RBF, GP_Matern       the exact GP (Posteriors.DenseBlock)
+      InducingPointMethod     a plugin with m inducing inputs Z: their draw or z-scoring, the upload of X, Y, Z, ``inducing_inputs``
+                              after the fit, the ARD rule of the covariance, and the queries' ``budget_bytes`` of the chunked blocks
+        SparseGP              FITC / VFE (Sparse.SparseBlock); SGP_FITC and SparseGP_RBF fix the approximation,
+                              SparseGP_RBFLinear adds the reference's linear term
+        SVIGP_RBF             variational, Student-t likelihood (SVGP.SVGPBlock)
+        BGPLVM                uncertain (Gaussian) inputs (Psi.UncertainInputBlock)
+
+The constructors and ``_fit`` check their arguments through four functions (``positive_scalar``, ``non_negative``,
+``lengthscale_argument``, ``per_dimension``).
+
+``GP_RBF`` replaces the
 GPy-backed subclass (RegressionInput.py:55-67) with the HIP kernels: isotropic
 RBF (GPy defaults l = 1, variance = 1 on the z-scored inputs), Gaussian noise
 ``labels.var() * 0.01`` on the z-scored labels.  ``optimize=True`` reproduces the
@@ -68,6 +85,50 @@ def log_marginal_likelihood(x, y, ell, sf, noise, cov=COV_RBF, want_grad=True):
     return lml, grad.cpu().numpy()
 
 
+# ---- the argument checks of the constructors and of ``_fit`` ---------------------------------------------------------------
+def positive_scalar(value, what):
+    """``value`` as a float: one positive finite number."""
+    if np.ndim(value) != 0 or not (np.isfinite(value) and value > 0):
+        raise ValueError('%s must be a positive number, got %r' % (what, value))
+    return float(value)
+
+
+def non_negative(value, what, finite=False):
+    """``value`` as a float: a number >= 0 (NaN is refused, and with ``finite`` infinity); ``what`` names it in the message."""
+    if not value >= 0 or (finite and not np.isfinite(value)):
+        raise ValueError('%s must not be negative' % what)
+    return float(value)
+
+
+def lengthscale_argument(lengthscale, ard, strict=False):
+    """A constructor's ``lengthscale``: a float, or a 1-d float64 array (one entry per input dimension), which needs ``ard``.
+    With ``ard`` the plugin builds its kernel at l = 1, which cannot refuse the values itself: they are checked here,
+    positive and finite in every entry.  ``strict``: they are checked first and in any case (``BGPLVM``, which takes no
+    other covariance), else a scalar without ``ard`` is left to the kernel."""
+    ls = np.asarray(lengthscale, dtype=np.float64)
+    bad = ls.size == 0 or not (np.isfinite(ls).all() and (ls > 0).all())
+    if strict and (ls.ndim > 1 or bad):
+        raise ValueError('lengthscale must be positive and finite in every entry, got %r' % (lengthscale,))
+    if ls.ndim > 0 and not ard:
+        raise ValueError('a sequence of length-scales needs ARD=True')
+    if ls.ndim > 1:
+        raise ValueError('lengthscale must be a scalar or a sequence with one entry per input dimension')
+    if ard and bad:
+        raise ValueError('lengthscale must be positive and finite in every entry, got %r' % (lengthscale,))
+    return ls.copy() if ls.ndim else float(ls)
+
+
+def per_dimension(value, d, what=None):
+    """``value`` as a fresh (d,) float64 vector: a scalar stands for every dimension.  ``what`` names a vector that must
+    have d entries (else its length is left to the block's own check)."""
+    if np.ndim(value) == 0:
+        return np.full(d, float(value))
+    value = np.array(value, dtype=np.float64)
+    if what is not None and value.shape[0] != d:
+        raise ValueError('%s has %d entries, the inputs have %d dimensions' % (what, value.shape[0], d))
+    return value
+
+
 class RegressionMethod(object):
     __metaclass__ = abc.ABCMeta
 
@@ -121,13 +182,25 @@ class PosteriorQueries(RegressionMethod):
     supplies ``_joint``; ``_accumulates`` says whether the block's ``predict`` / ``predict_grad`` add into their outputs
     (which are then zeroed first) or overwrite them; ``_test_inputs`` and ``_grad_scale`` are overridden by the plugin
     that rescales its inputs itself.  The public methods here have the exact plugin's signatures; keyword arguments that
-    a plugin's own public methods add (``budget_bytes``, ``include_noise``) go to the block's method unchanged."""
+    a plugin's own public methods add (``budget_bytes``, ``include_noise``) go to the block's method unchanged.
+    ``unsupported``: why the plugin's block does not answer the five queries beyond ``predict`` /
+    ``predict_with_variance`` (they raise TypeError, fitted or not), or None."""
     _accumulates = False
+    unsupported = None
 
     def _fitted_block(self, what):
         if self.block is None:
             raise RuntimeError('call fit() before %s()' % what)
         return self.block
+
+    def _refuse_unsupported(self, what):
+        """The first step of each of the five further queries; ``what``: the public method that was called."""
+        if self.unsupported is not None:
+            raise TypeError('%s() of %s (%s) is not yet supported' % (what, self.name, self.unsupported))
+
+    def _variance_shape(self, ns):
+        """The shape of the predictive variance at ``ns`` test inputs: one per input, shared by the outputs."""
+        return (ns,)
 
     def _test_inputs(self, test_data):
         """The (preprocessed) test inputs on the block's device, in the block's units."""
@@ -151,7 +224,7 @@ class PosteriorQueries(RegressionMethod):
         blk = self._fitted_block('predict')
         xs = self._test_inputs(test_data)
         mean = self._outputs((xs.shape[0], self._y.shape[1]), xs.device)
-        var = self._outputs(xs.shape[0], xs.device) if want_var else None
+        var = self._outputs(self._variance_shape(xs.shape[0]), xs.device) if want_var else None
         blk.predict(xs, mean, var, **block_kw)
         return mean.double().cpu().numpy(), None if var is None else var.double().cpu().numpy()
 
@@ -169,6 +242,7 @@ class PosteriorQueries(RegressionMethod):
         return self._predict_with_variance(test_data)
 
     def _predictive_gradients(self, test_data, **block_kw):
+        self._refuse_unsupported('predictive_gradients')
         blk = self._fitted_block('predictive_gradients')
         if self.preprocess:
             test_data = self._preprocess(test_data, False)
@@ -195,8 +269,9 @@ class PosteriorQueries(RegressionMethod):
         as ``predict_with_variance`` leaves the variance."""
         return self._predictive_gradients(test_data)
 
-    def _loo_z(self, **block_kw):
-        """(labels, LOO mean, LOO variance) in the (z-scored) units of the fit, NumPy."""
+    def _loo_z(self, what, **block_kw):
+        """(labels, LOO mean, LOO variance) in the (z-scored) units of the fit, NumPy, for the public method ``what``."""
+        self._refuse_unsupported(what)
         blk = self._fitted_block('leave_one_out')
         y = self._y
         mean = torch.empty_like(y)
@@ -205,7 +280,7 @@ class PosteriorQueries(RegressionMethod):
         return y.double().cpu().numpy(), mean.double().cpu().numpy(), var.double().cpu().numpy()
 
     def _leave_one_out(self, **block_kw):
-        _, mean, var = self._loo_z(**block_kw)
+        _, mean, var = self._loo_z('leave_one_out', **block_kw)
         if self.preprocess:
             mean = self._reverse_trans_labels(mean)
         return mean, var
@@ -218,7 +293,7 @@ class PosteriorQueries(RegressionMethod):
         return self._leave_one_out()
 
     def _loo_log_predictive_density(self, **block_kw):
-        y, mean, var = self._loo_z(**block_kw)
+        y, mean, var = self._loo_z('loo_log_predictive_density', **block_kw)
         q = y.shape[1]
         return -0.5 * q * np.log(2 * np.pi * var) - 0.5 * ((y - mean) ** 2).sum(axis=1) / var
 
@@ -230,6 +305,7 @@ class PosteriorQueries(RegressionMethod):
     def predict_with_covariance(self, test_data):
         """Mean (un-z-scored) and the latent joint predictive covariance (N* x N*, z-scored label units like
         ``predict_with_variance``'s variance, which is its diagonal)."""
+        self._refuse_unsupported('predict_with_covariance')
         blk = self._fitted_block('predict_with_covariance')
         if self.preprocess:
             test_data = self._preprocess(test_data, False)
@@ -247,6 +323,7 @@ class PosteriorQueries(RegressionMethod):
         """``size`` draws (size, N*, q) of the latent function in the original label units: the z-scored draw
         mean + chol(Sigma + 1e-6 sf2 I) Z (Z_c = phi(seed, 0, c, .), c = sample * q + output; include/cimrgp_joint.h)
         times labels_std, plus labels_mean, per output."""
+        self._refuse_unsupported('posterior_samples_f')
         blk = self._fitted_block('posterior_samples_f')
         if int(size) < 1:
             raise ValueError('size must be at least 1')
@@ -332,7 +409,7 @@ class GP_RBF(PosteriorQueries):
         if self.optimize:
             self._optimize(x, y, self.kernel.noise)
         elif self.ARD:
-            self.lengthscales = np.full(x.shape[1], self.kernel.l)
+            self.lengthscales = per_dimension(self.kernel.l, x.shape[1])
             self.kernel = self._make_kernel(1.0, self.kernel.sf, self.kernel.noise)
         if self.ARD:
             self._scale, x = unit_lengthscale(x, self.lengthscales)          # unit length-scale from here on
@@ -375,7 +452,98 @@ class GP_Matern(GP_RBF):
         return DenseMaternKernel(nu=self.nu, l=l, sf=sf, noise=noise)
 
 
-class SparseGP(PosteriorQueries):
+class InducingPointMethod(PosteriorQueries):
+    """A plugin whose block stands on m = ``num_inducing`` inducing inputs.  ``Z=None`` draws them from the z-scored
+    training inputs (:meth:`inducing_draw`; ``inducing_ids`` then holds the rows); a given ``Z`` (m x d) is in the caller's
+    units and is z-scored with the inputs.  After the fit ``inducing_inputs`` holds Z in the caller's units.  A subclass
+    sets ``ARD`` and, for a Matern covariance, ``nu``; its ``_fit`` goes through :meth:`_upload` and
+    :meth:`_publish_inducing_inputs`, its ``_block`` through :meth:`_covariance`.  Every such block predicts in chunks, so
+    the public queries here take ``budget_bytes``, the work area of a chunk."""
+    nu = None
+
+    def __init__(self, num_inducing, Z, seed, jitter, device):
+        super(InducingPointMethod, self).__init__()
+        if int(num_inducing) < 1:
+            raise ValueError('num_inducing must be at least 1')
+        self.num_inducing = int(num_inducing)
+        self.Z = None if Z is None else np.atleast_2d(np.asarray(Z, dtype=np.float64))
+        self.seed, self.jitter, self.device = seed, float(jitter), device
+        self.block = self.optimizer_result = None
+        self.lengthscales = None             # ARD: (d,) vector after fit
+        self.inducing_ids = None             # rows of the training set drawn as inducing inputs (Z=None)
+        self.inducing_inputs = None          # Z of the fitted model, in the caller's units
+
+    def _make_kernel(self, l, sf, noise=None):
+        if self.nu is None:
+            return RBFKernel(l=l, sf=sf, noise=noise)
+        return DenseMaternKernel(nu=self.nu, l=l, sf=sf, noise=noise)
+
+    def _covariance(self, ell, sf, noise=None):
+        """``(kernel, the block's keyword arguments)`` at (ell, sf, noise).  ARD: ``ell`` is the (d,) vector, which the block
+        takes as ``lengthscales=`` beside a kernel at l = 1; else the kernel is at ``ell``."""
+        if self.ARD:
+            return self._make_kernel(1.0, sf, noise), dict(lengthscales=ell)
+        return self._make_kernel(ell, sf, noise), {}
+
+    def inducing_draw(self, n):
+        """The documented draw of inducing rows among n training rows."""
+        return np.random.RandomState(self.seed).permutation(n)[:min(n, self.num_inducing)]
+
+    def _inducing_inputs(self, inputs):
+        """Z in the (z-scored) units of ``inputs``."""
+        if self.Z is None:
+            self.inducing_ids = self.inducing_draw(inputs.shape[0])
+            return inputs[self.inducing_ids]
+        self.inducing_ids = None
+        if self.Z.shape[1] != inputs.shape[1]:
+            raise ValueError('Z must have the dimension of the inputs')
+        return (self.Z - self.data_mean) / self.data_std if self.preprocess else self.Z
+
+    def _upload(self, train_data):
+        """The first step of a fit: forget the block, leave the (z-scored) inputs, labels and inducing inputs on the device
+        as ``_x``, ``_y``, ``_z``.  Returns ``(inputs, labels, d)``, the host arrays as float64 matrices."""
+        inputs, labels = train_data
+        device = dev.require_gpu(self.device)
+        inputs = np.atleast_2d(np.asarray(inputs, dtype=np.float64))
+        labels = np.atleast_2d(np.asarray(labels, dtype=np.float64))
+        self.block = None
+        self._x = dev.to_device(inputs, self.dtype, device)
+        self._y = dev.to_device(labels, self.dtype, device)
+        self._z = dev.to_device(self._inducing_inputs(inputs), self.dtype, device)
+        return inputs, labels, inputs.shape[1]
+
+    def _publish_inducing_inputs(self):
+        """The last step of a fit: ``inducing_inputs``, Z (as fitted: it may have been learned) in the caller's units."""
+        z = self._z.double().cpu().numpy()
+        self.inducing_inputs = z * self.data_std + self.data_mean if self.preprocess else z
+
+    # ---- the posterior queries: PosteriorQueries', with the block's own keyword arguments -----------------------
+    def predict_with_variance(self, test_data, include_noise=False, budget_bytes=None):
+        """Mean (un-z-scored) and predictive variance, left in z-scored label units as ``GP_RBF.predict_with_variance``
+        leaves it (latent; ``include_noise`` adds the noise).  ``budget_bytes``: work area of the chunked prediction."""
+        return self._predict_with_variance(test_data, include_noise=include_noise, budget_bytes=budget_bytes)
+
+    def predictive_gradients(self, test_data, budget_bytes=None):
+        """``GP_RBF.predictive_gradients`` for the sparse posterior: ``(dmu_dX (N*, d, q), dvar_dX (N*, d))`` with respect
+        to the original test inputs.  The mean gradient is in the original label units, the variance gradient in z-scored
+        label units, as ``predict_with_variance`` leaves the variance (:meth:`~cimrgp_amd.Sparse.SparseBlock.predict_grad`;
+        ARD's 1 / lengthscale is applied by the block)."""
+        return self._predictive_gradients(test_data, budget_bytes=budget_bytes)
+
+    def leave_one_out(self, budget_bytes=None):
+        """Closed-form leave-one-out prediction of every training label from the other n - 1 under the fitted sparse
+        model (exact for FITC's covariance Q_ff + Lambda; VFE / DTC: the same formula with Lambda = noise I):
+        ``(mean (n, q), var (n,))``, at the cost of one prediction pass over the training set.  The mean is in the original
+        label units; the variance is left in z-scored label units and includes the noise, as ``GP_RBF.leave_one_out``'s."""
+        return self._leave_one_out(budget_bytes=budget_bytes)
+
+    def loo_log_predictive_density(self, budget_bytes=None):
+        """(n,) log densities of each training label under its leave-one-out predictive Gaussian, in z-scored label
+        units, summed over the outputs; their sum scores the fit -- and the choice of m -- without a held-out set."""
+        return self._loo_log_predictive_density(budget_bytes=budget_bytes)
+
+
+class SparseGP(InducingPointMethod):
     """Inducing-point GP regression plugin (:class:`~cimrgp_amd.Sparse.SparseBlock`): ``approximation='fitc'`` or
     ``'vfe'``, cost n m^2 for m = ``num_inducing`` inducing inputs.  ``Z=None`` draws them from the z-scored training
     inputs, ``numpy.random.RandomState(seed).permutation(n)[:min(n, num_inducing)]``; a given ``Z`` (m x d) is in the
@@ -399,112 +567,68 @@ class SparseGP(PosteriorQueries):
 
     def __init__(self, num_inducing=1000, approximation='fitc', lengthscale=1., variance=1., nu=None, Z=None, seed=0, jitter=1e-6,
                  dtype='f64', device=None, optimize=False, max_iters=200, jac='2-point', optimize_inducing=False, ARD=False):
-        super(SparseGP, self).__init__()
         from .Sparse import APPROXIMATIONS
         if str(approximation).lower() not in APPROXIMATIONS:
             raise ValueError("approximation must be 'fitc' or 'vfe', got %r" % (approximation,))
-        if int(num_inducing) < 1:
-            raise ValueError('num_inducing must be at least 1')
+        super(SparseGP, self).__init__(num_inducing, Z, seed, jitter, device)
         if jac not in ('2-point', 'analytic'):
             raise ValueError("jac must be '2-point' or 'analytic', got %r" % (jac,))
         if optimize_inducing and not (optimize and jac == 'analytic'):
             raise ValueError("optimize_inducing=True needs optimize=True and jac='analytic'")
         self.jac = jac
         self.optimize_inducing = bool(optimize_inducing)
-        self.inducing_inputs = None          # Z of the fitted model, in the caller's units
-        self.num_inducing = int(num_inducing)
         self.approximation = str(approximation).lower()
         self.nu = None if nu is None else float(nu)
         self.ARD = bool(ARD)
-        self.lengthscales = None             # ARD: (d,) vector after fit
-        if np.ndim(lengthscale) > 0:
-            if not self.ARD:
-                raise ValueError('a sequence of length-scales needs ARD=True')
-            if np.ndim(lengthscale) != 1:
-                raise ValueError('lengthscale must be a scalar or a sequence with one entry per input dimension')
-            self._initial = (np.array(lengthscale, dtype=np.float64), float(variance))
-        else:
-            self._initial = (float(lengthscale), float(variance))
-        if self.ARD:                         # the kernel is built at l = 1 and cannot refuse these itself
-            ls = np.atleast_1d(self._initial[0])
-            if ls.size == 0 or not (np.isfinite(ls).all() and (ls > 0).all()):
-                raise ValueError('lengthscale must be positive and finite in every entry, got %r' % (lengthscale,))
-        self.kernel = self._make_kernel(1.0 if self.ARD else lengthscale, variance)      # ValueError for an unsupported nu
-        self.Z = None if Z is None else np.atleast_2d(np.asarray(Z, dtype=np.float64))
-        self.seed = seed
-        self.jitter = float(jitter)
+        self._initial = (lengthscale_argument(lengthscale, self.ARD), float(variance))
+        self.kernel = self._covariance(*self._initial)[0]          # ValueError for an unsupported nu
         self.dtype = dev.as_torch_dtype(dtype)
-        self.device = device
         self.optimize = optimize
         self.max_iters = max_iters
-        self.optimizer_result = None
-        self.block = None
-        self.inducing_ids = None             # rows of the training set drawn as inducing inputs (Z=None)
         self.linear_variances = None         # SparseGP_RBFLinear: (d,) variances of the linear term after fit
         self._initial_linear = None          # ... and their starting value, a scalar or a (d,) vector
 
-    def _make_kernel(self, l, sf, noise=None):
-        if self.nu is None:
-            return RBFKernel(l=l, sf=sf, noise=noise)
-        return DenseMaternKernel(nu=self.nu, l=l, sf=sf, noise=noise)
-
-    def inducing_draw(self, n):
-        """The documented draw of inducing rows among n training rows."""
-        return np.random.RandomState(self.seed).permutation(n)[:min(n, self.num_inducing)]
-
-    def _inducing_inputs(self, inputs):
-        """Z in the (z-scored) units of ``inputs``."""
-        if self.Z is None:
-            self.inducing_ids = self.inducing_draw(inputs.shape[0])
-            return inputs[self.inducing_ids]
-        self.inducing_ids = None
-        if self.Z.shape[1] != inputs.shape[1]:
-            raise ValueError('Z must have the dimension of the inputs')
-        return (self.Z - self.data_mean) / self.data_std if self.preprocess else self.Z
-
     def _block(self, ell, sf, noise, linear=None):
-        """The block at (ell, sf, noise); ARD: ``ell`` is the (d,) vector and the kernel's own length-scale 1.  A model with a
-        linear term carries its variances: ``linear``, or the fitted ones."""
+        """The block at (ell, sf, noise) (:meth:`_covariance`).  A model with a linear term carries its variances:
+        ``linear``, or the fitted ones."""
         from .Sparse import SparseBlock
+        kernel, kw = self._covariance(ell, sf, noise)
         if linear is None:
             linear = self.linear_variances
-        kw = {} if linear is None else dict(linear=linear)
-        if self.ARD:
-            return SparseBlock(self._x, self._z, self._make_kernel(1.0, sf, noise), self.approximation, self.jitter,
-                               lengthscales=ell, **kw)
-        return SparseBlock(self._x, self._z, self._make_kernel(ell, sf, noise), self.approximation, self.jitter, **kw)
+        if linear is not None:
+            kw['linear'] = linear
+        return SparseBlock(self._x, self._z, kernel, self.approximation, self.jitter, **kw)
 
-    def _ell(self, ell):
+    def _set_covariance(self, ell, sf, noise):
+        """``kernel`` and, under ARD, ``lengthscales`` of the model at (ell, sf, noise)."""
+        self.kernel, kw = self._covariance(ell, sf, noise)
+        self.lengthscales = kw.get('lengthscales')
+
+    def _ell(self, ell=None):
         """The ``ell=`` argument of the two objective calls: the fitted value by default; ARD: a scalar stands for all
         dimensions."""
         if not self.ARD:
             return self.kernel.l if ell is None else float(ell)
-        if ell is None:
-            return self.lengthscales
-        return np.full(self.lengthscales.shape[0], float(ell)) if np.ndim(ell) == 0 else np.asarray(ell, dtype=np.float64)
+        return self.lengthscales if ell is None else per_dimension(ell, self.lengthscales.shape[0])
 
-    def _linear(self, linear):
-        """The ``linear=`` argument of the two objective calls: the (d,) variances of the linear term, a scalar standing for
-        all dimensions; refused by a model without the term."""
-        if linear is None:
-            return None
-        if self.linear_variances is None:
-            raise TypeError('%s has no linear term' % type(self).__name__)
-        d = self.linear_variances.shape[0]
-        return np.full(d, float(linear)) if np.ndim(linear) == 0 else np.asarray(linear, dtype=np.float64)
+    def _block_at(self, ell, sf, noise, linear):
+        """The block of the two objective calls: at their arguments, each the fitted value by default.  ``linear``: the (d,)
+        variances of the linear term, a scalar standing for all dimensions; refused by a model without the term."""
+        if linear is not None:
+            if self.linear_variances is None:
+                raise TypeError('%s has no linear term' % type(self).__name__)
+            linear = per_dimension(linear, self.linear_variances.shape[0])
+        k = self.kernel
+        return self._block(self._ell(ell), k.sf if sf is None else float(sf), k.noise if noise is None else float(noise), linear)
 
     def log_marginal_likelihood(self, ell=None, sf=None, noise=None, linear=None):
         """The FITC marginal likelihood / the VFE bound of the fitted data at (ell, sf, noise); the fitted values by
         default.  Raises LinAlgError if a factorisation fails or a lambda_i is not positive.  ``linear``: the variances of
         the linear term of a model that has one (``SparseGP_RBFLinear``)."""
-        if self.block is None:
-            raise RuntimeError('call fit() before log_marginal_likelihood()')
+        blk = self._fitted_block('log_marginal_likelihood')
         if ell is None and sf is None and noise is None and linear is None:
-            return self.block.log_marginal_likelihood()
-        k = self.kernel
-        blk = self._block(self._ell(ell), k.sf if sf is None else float(sf), k.noise if noise is None else float(noise),
-                          self._linear(linear))
-        return blk.fit(self._y).log_marginal_likelihood()
+            return blk.log_marginal_likelihood()
+        return self._block_at(ell, sf, noise, linear).fit(self._y).log_marginal_likelihood()
 
     def log_marginal_likelihood_grad(self, ell=None, sf=None, noise=None, want_z=True, linear=None):
         """``(lml, dtheta, dZ)`` of the fitted data at (ell, sf, noise), the fitted values by default: the objective of
@@ -513,12 +637,8 @@ class SparseGP(PosteriorQueries):
         an (m, d) array, else None.  A model with a linear term has d more entries at the end of dtheta, w.r.t.
         (log v_1 .. log v_d), taken at ``linear`` (default: the fitted variances).
         Raises as :meth:`log_marginal_likelihood` does."""
-        if self.block is None:
-            raise RuntimeError('call fit() before log_marginal_likelihood_grad()')
-        k = self.kernel
-        blk = self._block(self._ell(ell), k.sf if sf is None else float(sf), k.noise if noise is None else float(noise),
-                          self._linear(linear))
-        lml, dtheta, dz = blk.lml_grad(self._y, want_z=want_z)
+        self._fitted_block('log_marginal_likelihood_grad')
+        lml, dtheta, dz = self._block_at(ell, sf, noise, linear).lml_grad(self._y, want_z=want_z)
         return lml, dtheta, None if dz is None else dz.double().cpu().numpy()
 
     def _optimize(self, noise0):
@@ -555,64 +675,23 @@ class SparseGP(PosteriorQueries):
         return unpack_theta(res.x, n_ell)
 
     def _fit(self, train_data):
-        inputs, labels = train_data
-        d = np.atleast_2d(np.asarray(inputs)).shape[1]
-        if self.ARD and np.ndim(self._initial[0]) > 0 and self._initial[0].shape[0] != d:
-            raise ValueError('lengthscale has %d entries, the inputs have %d dimensions' % (self._initial[0].shape[0], d))
-        if self._initial_linear is not None:
-            v = self._initial_linear
-            if np.ndim(v) > 0 and v.shape[0] != d:
-                raise ValueError('linear_variance has %d entries, the inputs have %d dimensions' % (v.shape[0], d))
-            self.linear_variances = np.full(d, float(v)) if np.ndim(v) == 0 else v.copy()
-        device = dev.require_gpu(self.device)
-        inputs = np.atleast_2d(np.asarray(inputs, dtype=np.float64))
-        labels = np.atleast_2d(np.asarray(labels, dtype=np.float64))
-        self.block = None
+        ell, sf = self._initial
+        d = np.atleast_2d(np.asarray(train_data[0])).shape[1]          # a wrong length is refused before the device is asked for
         if self.ARD:
-            self.lengthscales = np.full(d, self._initial[0]) if np.ndim(self._initial[0]) == 0 else self._initial[0].copy()
-            self.kernel = self._make_kernel(1.0, self._initial[1], float(labels.var()) * NOISE_FRACTION)
-        else:
-            self.kernel = self._make_kernel(self._initial[0], self._initial[1], float(labels.var()) * NOISE_FRACTION)
-        self._x = dev.to_device(inputs, self.dtype, device)
-        self._y = dev.to_device(labels, self.dtype, device)
-        self._z = dev.to_device(self._inducing_inputs(inputs), self.dtype, device)
+            ell = per_dimension(ell, d, 'lengthscale')
+        if self._initial_linear is not None:
+            self.linear_variances = per_dimension(self._initial_linear, d, 'linear_variance')
+        _, labels, _ = self._upload(train_data)
+        self._set_covariance(ell, sf, float(labels.var()) * NOISE_FRACTION)
         if self.optimize:
-            ell, sf, noise = self._optimize(self.kernel.noise)
-            if self.ARD:
-                self.lengthscales, ell = ell, 1.0
-            self.kernel = self._make_kernel(ell, sf, noise)
-        self.block = self._block(self.lengthscales if self.ARD else self.kernel.l, self.kernel.sf, self.kernel.noise).fit(self._y)
-        z = self._z.double().cpu().numpy()
-        self.inducing_inputs = z * self.data_std + self.data_mean if self.preprocess else z
+            self._set_covariance(*self._optimize(self.kernel.noise))
+        self.block = self._block(self._ell(), self.kernel.sf, self.kernel.noise).fit(self._y)
+        self._publish_inducing_inputs()
         return True
 
-    # ---- the posterior queries: PosteriorQueries', with the block's own keyword arguments -----------------------
     def _joint(self, blk, xs, cov_out=None, samples=None, seed=0):
         blk.joint(xs, cov_out=cov_out, samples=samples, seed=seed)
 
-    def predict_with_variance(self, test_data, include_noise=False, budget_bytes=None):
-        """Mean (un-z-scored) and predictive variance, left in z-scored label units as ``GP_RBF.predict_with_variance``
-        leaves it (latent; ``include_noise`` adds the noise).  ``budget_bytes``: work area of the chunked prediction."""
-        return self._predict_with_variance(test_data, include_noise=include_noise, budget_bytes=budget_bytes)
-
-    def predictive_gradients(self, test_data, budget_bytes=None):
-        """``GP_RBF.predictive_gradients`` for the sparse posterior: ``(dmu_dX (N*, d, q), dvar_dX (N*, d))`` with respect
-        to the original test inputs.  The mean gradient is in the original label units, the variance gradient in z-scored
-        label units, as ``predict_with_variance`` leaves the variance (:meth:`~cimrgp_amd.Sparse.SparseBlock.predict_grad`;
-        ARD's 1 / lengthscale is applied by the block)."""
-        return self._predictive_gradients(test_data, budget_bytes=budget_bytes)
-
-    def leave_one_out(self, budget_bytes=None):
-        """Closed-form leave-one-out prediction of every training label from the other n - 1 under the fitted sparse
-        model (exact for FITC's covariance Q_ff + Lambda; VFE / DTC: the same formula with Lambda = noise I):
-        ``(mean (n, q), var (n,))``, at the cost of one prediction pass over the training set.  The mean is in the original
-        label units; the variance is left in z-scored label units and includes the noise, as ``GP_RBF.leave_one_out``'s."""
-        return self._leave_one_out(budget_bytes=budget_bytes)
-
-    def loo_log_predictive_density(self, budget_bytes=None):
-        """(n,) log densities of each training label under its leave-one-out predictive Gaussian, in z-scored label
-        units, summed over the outputs; their sum scores the fit -- and the choice of m -- without a held-out set."""
-        return self._loo_log_predictive_density(budget_bytes=budget_bytes)
 
 class SGP_FITC(SparseGP):
     """The reference's ``SGP_FITC`` plugin: :class:`SparseGP` with ``approximation='fitc'``."""
@@ -646,6 +725,7 @@ class SparseGP_RBFLinear(SparseGP):
     (Z.ravel())].  Everything else is :class:`SparseGP`'s, ``nu`` and ``approximation='fitc'`` included.  The five posterior
     queries beyond ``predict`` / ``predict_with_variance`` are not built for this kernel and raise TypeError."""
     name = 'SparseGP_RBFLinear'
+    unsupported = 'a covariance with a linear term'
 
     def __init__(self, num_inducing=1000, lengthscale=1., variance=1., linear_variance=1., nu=None, Z=None, seed=0, jitter=1e-6,
                  dtype='f64', device=None, optimize=False, max_iters=200, jac='2-point', optimize_inducing=False, ARD=True,
@@ -658,26 +738,8 @@ class SparseGP_RBFLinear(SparseGP):
                              % (linear_variance,))
         self._initial_linear = float(v) if v.ndim == 0 else v.copy()
 
-    def _not_built(self, what):
-        raise TypeError('%s() of %s (a covariance with a linear term) is not yet supported' % (what, self.name))
 
-    def predictive_gradients(self, test_data, budget_bytes=None):
-        self._not_built('predictive_gradients')
-
-    def leave_one_out(self, budget_bytes=None):
-        self._not_built('leave_one_out')
-
-    def loo_log_predictive_density(self, budget_bytes=None):
-        self._not_built('loo_log_predictive_density')
-
-    def predict_with_covariance(self, test_data):
-        self._not_built('predict_with_covariance')
-
-    def posterior_samples_f(self, test_data, size=1, seed=0):
-        self._not_built('posterior_samples_f')
-
-
-class SVIGP_RBF(RegressionMethod):
+class SVIGP_RBF(InducingPointMethod):
     """The reference's ``SVIGP_RBF`` plugin: GPy's ``SVGP`` with the kernel ``RBF(ARD) + Linear(ARD) + White(0.01)`` and a
     Student-t likelihood (``deg_free`` = 3), optimised on the full batch, predicting the latent function
     (:class:`~cimrgp_amd.SVGP.SVGPBlock`; DESIGN.md, "Variational sparse GP with a Student-t likelihood").  It is the one
@@ -692,39 +754,28 @@ class SVIGP_RBF(RegressionMethod):
     ``predict_with_variance`` are not built and raise TypeError."""
     name = 'SVIGP_RBF'
     INITIAL_SCALE = 0.01
+    unsupported = 'a variational posterior'
 
     def __init__(self, num_inducing=100, lengthscale=1., variance=1., linear_variance=1., white_variance=0.01,
                  likelihood='student_t', deg_free=3., nu=None, Z=None, seed=0, jitter=1e-6, dtype='f64', device=None, optimize=True,
                  max_iters=1000, ARD=True, linear=True):
-        super(SVIGP_RBF, self).__init__()
         from .SVGP import LIKELIHOODS
         if str(likelihood).lower() not in LIKELIHOODS:
             raise ValueError("likelihood must be 'student_t' or 'gaussian', got %r" % (likelihood,))
-        if int(num_inducing) < 1:
-            raise ValueError('num_inducing must be at least 1')
-        for value, what in ((lengthscale, 'lengthscale'), (variance, 'variance'), (linear_variance, 'linear_variance'),
-                            (deg_free, 'deg_free')):
-            if np.ndim(value) != 0 or not (np.isfinite(value) and value > 0):
-                raise ValueError('%s must be a positive number, got %r' % (what, value))
-        if not (np.isfinite(white_variance) and white_variance >= 0) or not jitter >= 0:
-            raise ValueError('white_variance and jitter must not be negative')
+        super(SVIGP_RBF, self).__init__(num_inducing, Z, seed, jitter, device)
+        self._initial = (positive_scalar(lengthscale, 'lengthscale'), positive_scalar(variance, 'variance'),
+                         positive_scalar(linear_variance, 'linear_variance'))
+        self.deg_free = positive_scalar(deg_free, 'deg_free')
+        self.white_variance = non_negative(white_variance, 'white_variance and jitter', finite=True)
+        non_negative(jitter, 'white_variance and jitter')
         self.dtype = dev.as_torch_dtype(dtype)
         if self.dtype != torch.float64:
             raise TypeError("%s with dtype='f32' is not yet supported" % self.name)
         self.nu = None if nu is None else float(nu)
         self.kernel = self._make_kernel(1.0, variance)           # ValueError for an unsupported nu
-        self.num_inducing, self.likelihood = int(num_inducing), str(likelihood).lower()
-        self._initial = (float(lengthscale), float(variance), float(linear_variance))
-        self.white_variance, self.deg_free, self.jitter = float(white_variance), float(deg_free), float(jitter)
-        self.Z = None if Z is None else np.atleast_2d(np.asarray(Z, dtype=np.float64))
-        self.seed, self.device, self.optimize, self.max_iters = seed, device, optimize, max_iters
+        self.likelihood, self.optimize, self.max_iters = str(likelihood).lower(), optimize, max_iters
         self.ARD, self.linear = bool(ARD), bool(linear)
-        self.block = self.lengthscales = self.linear_variances = self.likelihood_scale = self.optimizer_result = None
-        self.params = self.inducing_inputs = self.inducing_ids = None
-
-    _make_kernel = SparseGP._make_kernel
-    inducing_draw = SparseGP.inducing_draw
-    _inducing_inputs = SparseGP._inducing_inputs
+        self.linear_variances = self.likelihood_scale = self.params = None
 
     def _block(self, theta):
         """The block at theta = [log sf, log l (1, or d under ARD), log s2, (log v_1 .. log v_d)]."""
@@ -733,8 +784,9 @@ class SVIGP_RBF(RegressionMethod):
         n_ell = d if self.ARD else None
         head, lin, _ = split_linear(np.asarray(theta, dtype=np.float64), d if self.linear else 0, n_ell)
         ell, sf, s2 = unpack_theta(head, n_ell)
-        return SVGPBlock(self._x, self._z, self._make_kernel(1.0 if self.ARD else ell, sf), self.likelihood, self.deg_free, s2,
-                         self.white_variance, self.jitter, lengthscales=ell if self.ARD else None, linear=lin if self.linear else None)
+        kernel, kw = self._covariance(ell, sf)
+        return SVGPBlock(self._x, self._z, kernel, self.likelihood, self.deg_free, s2, self.white_variance, self.jitter,
+                         linear=lin if self.linear else None, **kw)
 
     def _vfe_posterior(self, theta):
         """(mu (q, m), P (q, m, m)) of the optimal Gaussian q(v) at ``theta``: P = L_B and mu = L_B^-T gamma of the VFE fit
@@ -766,32 +818,23 @@ class SVIGP_RBF(RegressionMethod):
         """``(F, gradient)`` of the evidence lower bound of the fitted data at ``params`` (default: the fitted ``params``):
         the whole vector [log sf, log l .., log s2, (log v ..), mu.ravel(), vech(P) per output, log-diagonal] and the
         analytic gradient w.r.t. it.  Raises LinAlgError as :meth:`~cimrgp_amd.SVGP.SVGPBlock.elbo_grad` does."""
-        if self.block is None:
-            raise RuntimeError('call fit() before elbo_grad()')
+        self._fitted_block('elbo_grad')
         theta, mu, p = self._split(self.params if params is None else params)
         f, dtheta, dmu, dp = self._elbo_grad(theta, mu, p)
         return f, np.concatenate([dtheta, posterior_gradient(dmu, dp, p)])
 
     def elbo(self, params=None):
         """The evidence lower bound of :meth:`elbo_grad`."""
-        if self.block is None:
-            raise RuntimeError('call fit() before elbo()')
+        self._fitted_block('elbo')
         return self.elbo_grad(params)[0]
 
     def _fit(self, train_data):
-        inputs, labels = train_data
-        device = dev.require_gpu(self.device)
-        inputs = np.atleast_2d(np.asarray(inputs, dtype=np.float64))
-        labels = np.atleast_2d(np.asarray(labels, dtype=np.float64))
-        d = inputs.shape[1]
-        self.block = None
-        self._x = dev.to_device(inputs, self.dtype, device)
-        self._y = dev.to_device(labels, self.dtype, device)
-        self._z = dev.to_device(self._inducing_inputs(inputs), self.dtype, device)
+        d = self._upload(train_data)[2]
+        device = self._x.device
         ell0, sf0, lin0 = self._initial
-        theta = pack_theta(sf0, [ell0] * d if self.ARD else ell0, self.INITIAL_SCALE)
+        theta = pack_theta(sf0, per_dimension(ell0, d) if self.ARD else ell0, self.INITIAL_SCALE)
         if self.linear:
-            theta = append_linear(theta, np.full(d, lin0))
+            theta = append_linear(theta, per_dimension(lin0, d))
         self._n_theta = theta.shape[0]
         mu, p = self._vfe_posterior(theta)
         if self.optimize:
@@ -801,58 +844,25 @@ class SVIGP_RBF(RegressionMethod):
         self.kernel, self.lengthscales, self.linear_variances = blk.kernel, blk.lengthscales, blk.linear
         self.likelihood_scale = blk.scale
         self.block = blk.set_posterior(dev.to_device(mu, self.dtype, device), dev.to_device(p, self.dtype, device))
-        z = self._z.double().cpu().numpy()
-        self.inducing_inputs = z * self.data_std + self.data_mean if self.preprocess else z
+        self._publish_inducing_inputs()
         return True
 
-    def _predict_mean_var(self, test_data, want_var, budget_bytes=None):
-        if self.block is None:
-            raise RuntimeError('call fit() before predict()')
-        xs = dev.to_device(np.atleast_2d(np.asarray(test_data, dtype=np.float64)), self.dtype, self._x.device)
-        shape = (int(xs.shape[0]), int(self._y.shape[1]))
-        mean = torch.empty(shape, dtype=self.dtype, device=xs.device)
-        var = torch.empty(shape, dtype=self.dtype, device=xs.device) if want_var else None
-        self.block.predict(xs, mean, var, budget_bytes=budget_bytes)
-        return mean.double().cpu().numpy(), None if var is None else var.double().cpu().numpy()
-
-    def _predict(self, test_data):
-        """The latent mean, as the reference predicts (``include_likelihood=False``)."""
-        return self._predict_mean_var(test_data, False)[0]
+    def _variance_shape(self, ns):
+        """The latent variance differs between the outputs: each has its own q(v_c)."""
+        return (ns, int(self._y.shape[1]))
 
     def predict_with_variance(self, test_data, budget_bytes=None):
-        """Mean (un-z-scored) and the latent variance per output (ns, q), left in z-scored label units as the other
-        plugins leave it.  ``budget_bytes``: work area of the chunked prediction."""
-        if self.preprocess:
-            test_data = self._preprocess(test_data, False)
-        mean, var = self._predict_mean_var(test_data, True, budget_bytes)
-        if self.preprocess:
-            mean = self._reverse_trans_labels(mean)
-        return mean, var
-
-    def _not_built(self, what):
-        raise TypeError('%s() of %s (a variational posterior) is not yet supported' % (what, self.name))
-
-    def predictive_gradients(self, test_data, budget_bytes=None):
-        self._not_built('predictive_gradients')
-
-    def leave_one_out(self, budget_bytes=None):
-        self._not_built('leave_one_out')
-
-    def loo_log_predictive_density(self, budget_bytes=None):
-        self._not_built('loo_log_predictive_density')
-
-    def predict_with_covariance(self, test_data):
-        self._not_built('predict_with_covariance')
-
-    def posterior_samples_f(self, test_data, size=1, seed=0):
-        self._not_built('posterior_samples_f')
+        """Mean (un-z-scored, the latent mean, as the reference predicts: ``include_likelihood=False``) and the latent
+        variance per output (ns, q), left in z-scored label units as the other plugins leave it.  ``budget_bytes``: work
+        area of the chunked prediction."""
+        return self._predict_with_variance(test_data, budget_bytes=budget_bytes)
 
 
-class BGPLVM(PosteriorQueries):
+class BGPLVM(InducingPointMethod):
     """The reference's ``BGPLVM`` plugin: gpflow's ``BayesianGPLVM`` used as a sparse VFE regression whose inputs are not
     points but Gaussians x_i ~ N(inputs_i, diag X_var_i) (:class:`~cimrgp_amd.Psi.UncertainInputBlock`; DESIGN.md, "Sparse GP
     regression on uncertain inputs").  The defaults are the reference's: ``num_inducing`` = 100 rows drawn as
-    :meth:`SparseGP.inducing_draw` draws them, the unit RBF with one length-scale per dimension (``ARD=True``), gpflow's
+    :meth:`InducingPointMethod.inducing_draw` draws them, the unit RBF with one length-scale per dimension (``ARD=True``), gpflow's
     likelihood variance ``noise`` = 1.0 (on the z-scored labels), ``X_var=None`` = ``inputs.var() * 0.01`` over all entries of
     the z-scored inputs, and no optimisation.  ``X_var``: the variances of the inputs in the caller's (squared) units, a
     scalar, a (d,) vector or an (n, d) array, checked finite and not negative; it is scaled with the z-scoring.  A scalar or
@@ -865,37 +875,22 @@ class BGPLVM(PosteriorQueries):
     raise TypeError."""
     name = 'BGPLVM'
     X_VAR_FRACTION = 0.01
+    unsupported = 'uncertain inputs'
 
     def __init__(self, num_inducing=100, X_var=None, noise=1.0, lengthscale=1., variance=1., ARD=True, Z=None, seed=0, jitter=1e-6,
                  device=None, optimize=False, max_iters=200):
-        super(BGPLVM, self).__init__()
-        if int(num_inducing) < 1:
-            raise ValueError('num_inducing must be at least 1')
-        for value, what in ((noise, 'noise'), (variance, 'variance')):
-            if np.ndim(value) != 0 or not (np.isfinite(value) and value > 0):
-                raise ValueError('%s must be a positive number, got %r' % (what, value))
-        ls = np.asarray(lengthscale, dtype=np.float64)
-        if ls.ndim > 1 or ls.size == 0 or not (np.isfinite(ls).all() and (ls > 0).all()):
-            raise ValueError('lengthscale must be positive and finite in every entry, got %r' % (lengthscale,))
-        if ls.ndim == 1 and not ARD:
-            raise ValueError('a sequence of length-scales needs ARD=True')
-        if not jitter >= 0:
-            raise ValueError('jitter must not be negative')
+        super(BGPLVM, self).__init__(num_inducing, Z, seed, jitter, device)
+        noise, variance = positive_scalar(noise, 'noise'), positive_scalar(variance, 'variance')
+        self.ARD = bool(ARD)
+        self._initial = (lengthscale_argument(lengthscale, self.ARD, strict=True), variance, noise)
+        non_negative(jitter, 'jitter')
         if X_var is not None:
             X_var = np.asarray(X_var, dtype=np.float64)
             if X_var.ndim > 2 or not (np.isfinite(X_var).all() and (X_var >= 0).all()):
                 raise ValueError('X_var must be a scalar, a (d,) vector or an (n, d) array of finite variances, none negative')
-        self.num_inducing, self.X_var, self.ARD = int(num_inducing), X_var, bool(ARD)
-        self._initial = (ls.copy() if ls.ndim else float(ls), float(variance), float(noise))
-        self.Z = None if Z is None else np.atleast_2d(np.asarray(Z, dtype=np.float64))
-        self.seed, self.jitter, self.device, self.optimize, self.max_iters = seed, float(jitter), device, optimize, max_iters
+        self.X_var, self.optimize, self.max_iters = X_var, optimize, max_iters
         self.dtype = torch.float64
-        self.nu = None
-        self.kernel = RBFKernel(l=1.0 if self.ARD else self._initial[0], sf=variance, noise=noise)
-        self.block = self.lengthscales = self.inducing_inputs = self.inducing_ids = self.optimizer_result = None
-
-    inducing_draw = SparseGP.inducing_draw
-    _inducing_inputs = SparseGP._inducing_inputs
+        self.kernel = self._covariance(*self._initial)[0]
 
     def _variances(self, var, rows, d, what):
         """``var`` (the caller's units; a scalar, (d,) or (rows, d)) in the z-scored units: a host (d,) vector, or a
@@ -909,34 +904,24 @@ class BGPLVM(PosteriorQueries):
             var = var / np.asarray(self.data_std, dtype=np.float64) ** 2
         if var.ndim == 2:
             return dev.to_device(var, self.dtype, self._x.device)
-        return np.full(d, float(var)) if var.ndim == 0 else var
+        return per_dimension(var, d)
 
     def _block(self, ell, sf, noise):
-        """The block at (ell, sf, noise); ARD: ``ell`` is the (d,) vector and the kernel's own length-scale 1."""
+        """The block at (ell, sf, noise) (:meth:`_covariance`)."""
         from .Psi import UncertainInputBlock
-        if self.ARD:
-            return UncertainInputBlock(self._x, self._var, self._z, RBFKernel(l=1.0, sf=sf, noise=noise), self.jitter, lengthscales=ell)
-        return UncertainInputBlock(self._x, self._var, self._z, RBFKernel(l=ell, sf=sf, noise=noise), self.jitter)
+        kernel, kw = self._covariance(ell, sf, noise)
+        return UncertainInputBlock(self._x, self._var, self._z, kernel, self.jitter, **kw)
 
     def _fit(self, train_data):
-        inputs, labels = train_data
-        device = dev.require_gpu(self.device)
-        inputs = np.atleast_2d(np.asarray(inputs, dtype=np.float64))
-        labels = np.atleast_2d(np.asarray(labels, dtype=np.float64))
-        n, d = inputs.shape
         ell, sf, noise = self._initial
-        if np.ndim(ell) > 0 and ell.shape[0] != d:
-            raise ValueError('lengthscale has %d entries, the inputs have %d dimensions' % (ell.shape[0], d))
+        d = np.atleast_2d(np.asarray(train_data[0])).shape[1]          # a wrong length is refused before the device is asked for
         if self.ARD:
-            ell = np.full(d, ell) if np.ndim(ell) == 0 else ell.copy()
-        self.block = None
-        self._x = dev.to_device(inputs, self.dtype, device)
-        self._y = dev.to_device(labels, self.dtype, device)
-        self._z = dev.to_device(self._inducing_inputs(inputs), self.dtype, device)
+            ell = per_dimension(ell, d, 'lengthscale')
+        inputs = self._upload(train_data)[0]
         if self.X_var is None:
             self._var = np.full(d, float(inputs.var()) * self.X_VAR_FRACTION)         # of the inputs as the model sees them
         else:
-            self._var = self._variances(self.X_var, n, d, 'X_var')
+            self._var = self._variances(self.X_var, inputs.shape[0], d, 'X_var')
         if self.optimize:
             n_ell = d if self.ARD else None
             objective = lambda theta: self._block(*unpack_theta(theta, n_ell)).fit(self._y).bound()
@@ -944,8 +929,7 @@ class BGPLVM(PosteriorQueries):
             ell, sf, noise = unpack_theta(self.optimizer_result.x, n_ell)
         self.block = self._block(ell, sf, noise).fit(self._y)
         self.kernel, self.lengthscales = self.block.kernel, ell if self.ARD else None
-        z = self._z.double().cpu().numpy()
-        self.inducing_inputs = z * self.data_std + self.data_mean if self.preprocess else z
+        self._publish_inducing_inputs()
         return True
 
     def elbo(self):
@@ -980,21 +964,3 @@ class BGPLVM(PosteriorQueries):
             raise TypeError('the predictive variance of %s at uncertain test inputs is not yet supported' % self.name)
         self._fitted_block('predict_with_variance')
         return self._predict_with_variance(test_data, include_noise=include_noise, budget_bytes=budget_bytes)
-
-    def _not_built(self, what):
-        raise TypeError('%s() of %s (uncertain inputs) is not yet supported' % (what, self.name))
-
-    def predictive_gradients(self, test_data, budget_bytes=None):
-        self._not_built('predictive_gradients')
-
-    def leave_one_out(self, budget_bytes=None):
-        self._not_built('leave_one_out')
-
-    def loo_log_predictive_density(self, budget_bytes=None):
-        self._not_built('loo_log_predictive_density')
-
-    def predict_with_covariance(self, test_data):
-        self._not_built('predict_with_covariance')
-
-    def posterior_samples_f(self, test_data, size=1, seed=0):
-        self._not_built('posterior_samples_f')

@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from . import device as dev
 from . import device_svgp as devs
-from .Sparse import BlockCovariance, PREDICT_BUDGET_BYTES, read_back
+from .Sparse import BlockCovariance, read_back, rows_within, star_rows
 
 LIKELIHOODS = {'gaussian': _lib.LIK_GAUSSIAN, 'student_t': _lib.LIK_STUDENT_T}
 
@@ -207,28 +207,18 @@ class SVGPBlock(object):
 
     def chunk_rows(self, budget_bytes=None):
         """Test rows per pass of :meth:`predict`, a multiple of 256: A* and W* within ``budget_bytes``."""
-        budget = PREDICT_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
-        return max(256, budget // (2 * dev.padded_ld(self.m) * self.z.element_size()) // 256 * 256)
+        return rows_within(self.z, budget_bytes)
 
     def predict(self, xs, mean=None, var=None, budget_bytes=None):
         """The latent f at ``xs`` (ns x d, device): mean into ``mean`` (ns x q), variance per output into ``var`` (ns x q);
-        either may be None.  Chunks of ``chunk_rows(budget_bytes)`` test rows: a row's result does not depend on the
-        chunking."""
+        either may be None.  Chunks of ``chunk_rows(budget_bytes)`` test rows (``Sparse.star_rows``: A* = K(X*, Z) L_u^-T,
+        which every output then takes through its own P_c): a row's result does not depend on the chunking."""
         if self._columns is None:
             raise RuntimeError('call set_posterior() before predict()')
-        m, k, ns = self.m, self.kernel, int(xs.shape[0])
-        step = self.chunk_rows(budget_bytes)
-        astar = wstar = None
-        for s0 in range(0, ns, step):
-            s1 = min(ns, s0 + step)
+        m, k = self.m, self.kernel
+        for s0, s1, astar, wstar in star_rows(self.cov, self._zs, self.lu, self.ws_u, m, xs, self.chunk_rows(budget_bytes)):
             rows = s1 - s0
-            if astar is None:
-                astar = dev.alloc_matrix(min(step, ns), m, xs.dtype, xs.device)
-                wstar = torch.empty_like(astar)
-            xc = self.cov.inputs(xs[s0:s1])
-            self.cov.cross(xc, self._zs, out=astar)
-            dev.trsm_rows(self.lu, m, self.ws_u, astar, rows)
-            seed = None if self.cov.lin is None else self.cov.linear_diag(xc).to(xs.dtype)
+            seed = None if self.cov.lin is None else self.cov.linear_diag(self.cov.inputs(xs[s0:s1])).to(xs.dtype)
             for c, (pb, ws_p, _, gamma_c) in enumerate(self._columns):
                 wstar[:rows].copy_(astar[:rows])
                 dev.trsm_rows(pb, m, ws_p, wstar, rows)

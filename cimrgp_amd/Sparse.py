@@ -60,6 +60,34 @@ def read_back(scalars, vectors):
     return {k: float(host[e - 1]) if k in scalars else host[e - p.numel():e] for k, p, e in zip((*scalars, *vectors), parts, ends)}
 
 
+def rows_within(z, budget_bytes=None, slabs=1):
+    """Test rows per pass over the inducing inputs ``z`` (m x d), a multiple of 256: ``slabs`` row blocks of A* and as many
+    of W* (pitch padded_ld(m)) per test row within ``budget_bytes`` (None: PREDICT_BUDGET_BYTES)."""
+    budget = PREDICT_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
+    return max(256, budget // (2 * slabs * dev.padded_ld(int(z.shape[0])) * z.element_size()) // 256 * 256)
+
+
+def star_rows(cov, zs, lu, ws_u, m, xs, step, cross=None):
+    """(s0, s1, A*, W*) of every chunk of ``step`` rows of the test inputs ``xs``: A* = K(xs[s0:s1], Z) L_u^-T in the first
+    of two work buffers, allocated at the first chunk and overwritten by the next; W* is the second, left to the caller
+    (``SparseBlock``: A* L_B^-T; ``SVGP.SVGPBlock``: A* P_c^-T per output).  ``cov``: the block's BlockCovariance, ``zs``
+    its scaled inducing inputs, ``lu`` / ``ws_u``: L_u with its workspace.  ``cross(s0, s1, out)``: what fills ``out`` with
+    the chunk's rows in place of K(xs[s0:s1], Z) (``Psi.UncertainInputBlock``: Psi1 of uncertain test inputs)."""
+    ns = int(xs.shape[0])
+    astar = wstar = None
+    for s0 in range(0, ns, step):
+        s1 = min(ns, s0 + step)
+        if astar is None:
+            astar = dev.alloc_matrix(min(step, ns), m, xs.dtype, xs.device)
+            wstar = torch.empty_like(astar)
+        if cross is None:
+            cov.cross(cov.inputs(xs[s0:s1]), zs, out=astar)
+        else:
+            cross(s0, s1, astar)
+        dev.trsm_rows(lu, m, ws_u, astar, s1 - s0)
+        yield s0, s1, astar, wstar
+
+
 class BlockCovariance(object):
     """The covariance of a sparse block as the device calls take it (module docstring): ``kernel``'s values, ``scale`` =
     1 / l on the device under ARD (else None), and under a linear term the weights ``u`` = v l^2 on the host and ``lin``,
@@ -361,15 +389,9 @@ class SparseBlock(object):
         lml, dtheta, self.grad_check = self._gradient_from(h, q)
         return lml, dtheta, dz
 
-    def _rows_within(self, budget_bytes, slabs):
-        """Test rows per pass, a multiple of 256: ``slabs`` row blocks of A* and as many of W* (pitch padded_ld(m)) per test
-        row within ``budget_bytes`` (None: PREDICT_BUDGET_BYTES)."""
-        budget = PREDICT_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
-        return max(256, budget // (2 * slabs * dev.padded_ld(self.m) * self.z.element_size()) // 256 * 256)
-
     def chunk_rows(self, budget_bytes=None):
         """Test rows per pass of ``predict``: A* and W* within ``budget_bytes``."""
-        return self._rows_within(budget_bytes, 1)
+        return rows_within(self.z, budget_bytes)
 
     def predict(self, xs, mean=None, var=None, include_noise=False, budget_bytes=None):
         """Predictive mean into ``mean`` (ns x q) and variance into ``var`` (ns,) at ``xs`` (ns x d, device); either may
@@ -385,25 +407,11 @@ class SparseBlock(object):
         return mean, var
 
     def _star_chunks(self, xs, budget_bytes=None, cross=None):
-        """(s0, s1, A*, W*) of every chunk of ``chunk_rows(budget_bytes)`` test rows: A* = K(xs[s0:s1], Z) L_u^-T and
-        W* = A* L_B^-T in two work buffers that the next chunk overwrites.  ``cross(s0, s1, out)``: what fills ``out`` with
-        the chunk's rows in place of K(xs[s0:s1], Z) (``Psi.UncertainInputBlock``: Psi1 of uncertain test inputs)."""
-        m, ns = self.m, int(xs.shape[0])
-        step = self.chunk_rows(budget_bytes)
-        astar = wstar = None
-        for s0 in range(0, ns, step):
-            s1 = min(ns, s0 + step)
-            rows = s1 - s0
-            if astar is None:
-                astar = dev.alloc_matrix(min(step, ns), m, xs.dtype, xs.device)
-                wstar = torch.empty_like(astar)
-            if cross is None:
-                self.cov.cross(self.cov.inputs(xs[s0:s1]), self._zs, out=astar)
-            else:
-                cross(s0, s1, astar)
-            dev.trsm_rows(self.lu, m, self.ws_u, astar, rows)
-            wstar[:rows].copy_(astar[:rows])
-            dev.trsm_rows(self.lb, m, self.ws_b, wstar, rows)
+        """(s0, s1, A*, W*) of every chunk of ``chunk_rows(budget_bytes)`` test rows: :func:`star_rows`' A* and
+        W* = A* L_B^-T, in its two work buffers."""
+        for s0, s1, astar, wstar in star_rows(self.cov, self._zs, self.lu, self.ws_u, self.m, xs, self.chunk_rows(budget_bytes), cross):
+            wstar[:s1 - s0].copy_(astar[:s1 - s0])
+            dev.trsm_rows(self.lb, self.m, self.ws_b, wstar, s1 - s0)
             yield s0, s1, astar, wstar
 
     def _ready_for(self, what):
@@ -418,7 +426,7 @@ class SparseBlock(object):
 
     def grad_chunk_rows(self, budget_bytes=None):
         """Test rows per pass of ``predict_grad``: the d + 1 slabs of A* and of W* within ``budget_bytes``, a multiple of 256."""
-        return self._rows_within(budget_bytes, int(self.z.shape[1]) + 1)
+        return rows_within(self.z, budget_bytes, int(self.z.shape[1]) + 1)
 
     def predict_grad(self, xs, mean_grad=None, var_grad=None, budget_bytes=None):
         """Gradients of :meth:`predict`'s mean and variance w.r.t. the test inputs ("Posterior queries of the

@@ -13,7 +13,10 @@ the same bits in every file.
 Block level, per arm (plain, ARD, linear, ARD + linear), FITC and VFE, f64 and f32, RBF and Matern 3/2: the LML, predict
 (with and without the noise, in two chunks), lml_grad's (lml, dtheta, dZ) and grad_check and, for the arms without a
 linear term, predict_grad, loo, and joint's covariance and samples.  Plugin level: SparseGP(ARD) and SparseGP_RBFLinear
-learning their hyper-parameters and Z for 3 iterations.  Model level: two layers, the second sparse over an ARD base.
+learning their hyper-parameters and Z for 3 iterations; the seven queries of SGP_FITC(ARD); SVIGP_RBF at fixed
+hyper-parameters and after 3 iterations (params, elbo_grad, predict, predict_with_variance); BGPLVM on the shared-variance
+and the per-row route and after 3 iterations (elbo, kl_divergence, predict with and without test_var,
+predict_with_variance); GP_RBF(ARD)'s joint covariance and samples.  Model level: two layers, the second sparse over an ARD base.
 K() of both kernel classes, isotropic and ARD.  n = 300, m = 70, d = 3, q = 2, ns = 300: across the 64-column lane
 stride, the 256-row slice and chunk boundaries and one 128-column tile of the pair contraction.  Seconds in total.
 """
@@ -101,6 +104,30 @@ def dump(out_dir):
                      ("rbflinear", ca.SparseGP_RBFLinear(num_inducing=M, optimize=True, jac="analytic", max_iters=3))):
         gp.fit([xp, yp])
         save("plugin_" + name, gp.optimizer_result.x, *gp.predict_with_variance(xsp), gp.inducing_inputs)
+
+    # ---- plugin level: every query of a sparse plugin, the variational and the uncertain-input plugins, the exact plugin's joint
+    budget = 2 * dev.padded_ld(M) * 8 * 256                              # float64 chunks of 256 rows: two for ns = 300
+    gp = ca.SGP_FITC(num_inducing=M, ARD=True, lengthscale=ELLS)
+    gp.fit([xp, yp])
+    save("plugin_fitc_predict", gp.predict(xsp), *gp.predict_with_variance(xsp, include_noise=True, budget_bytes=budget))
+    save("plugin_fitc_gradients", *gp.predictive_gradients(xsp, budget_bytes=budget))
+    save("plugin_fitc_loo", *gp.leave_one_out(budget_bytes=budget), gp.loo_log_predictive_density(budget_bytes=budget))
+    save("plugin_fitc_joint", *gp.predict_with_covariance(xsp), gp.posterior_samples_f(xsp, size=2, seed=5), gp.inducing_inputs)
+    for optimize in (False, True):
+        gp = ca.SVIGP_RBF(num_inducing=M, optimize=optimize, max_iters=3)
+        gp.fit([xp, yp])
+        save("plugin_svigp_optimize%d" % optimize, gp.params, *gp.elbo_grad(), gp.predict(xsp),
+             *gp.predict_with_variance(xsp, budget_bytes=budget), gp.inducing_inputs)
+    x_var_rows = np.random.default_rng(3).uniform(0.0, 0.05, size=xp.shape)
+    for name, kw in (("shared", dict(X_var=0.02)), ("rows", dict(X_var=x_var_rows)), ("optimized", dict(optimize=True, max_iters=3))):
+        gp = ca.BGPLVM(num_inducing=M, **kw)
+        gp.fit([xp, yp])
+        save("plugin_bgplvm_" + name, gp.elbo(), gp.kl_divergence(), gp.predict(xsp),
+             *gp.predict_with_variance(xsp, include_noise=True, budget_bytes=budget), gp.predict(xsp, test_var=0.03, budget_bytes=budget),
+             gp.predict(xsp, test_var=np.full(xsp.shape, 0.03), budget_bytes=budget), gp.lengthscales, gp.inducing_inputs)
+    gp = ca.GP_RBF(lengthscale=0.9, ARD=True, optimize=False)
+    gp.fit([xp, yp])
+    save("plugin_gp_rbf_ard", *gp.predict_with_covariance(xsp), gp.posterior_samples_f(xsp, size=2, seed=5))
 
     # ---- model level: two layers, the second sparse over an ARD base
     from cimrgp_amd.Inputs import space_filling_order
