@@ -19,6 +19,11 @@ so prediction is ``SparseBlock.predict`` on the factors built here.  Two routes 
                                                                     C_jk = exp(-sum_e (z_je - z_ke)^2 s_e / (2 l_e^2 (l_e^2 + 2 s_e)))
 
 The n x m and n x m^2 work is those C calls; torch holds the buffers and does the m x m and m x q plumbing.
+
+``bound_grad`` / ``elbo_grad`` give the analytic gradient of F (and F - KL) w.r.t. the hyper-parameters, Z and the inputs'
+means and variances ("Gradients of the bound on uncertain inputs"): the weights dF/dPsi1, dF/dPsi2 and dF/dK_uu are
+m x m torch algebra on the fit's factors, their contractions cimrgp_psi1_grad, cimrgp_psi2_grad (include/cimrgp_psi_grad.h)
+and the covariance's pair contraction.  By either route of the fit the gradient takes the per-row kernels.
 """
 import numpy as np
 import torch
@@ -38,13 +43,15 @@ class UncertainInputBlock(SparseBlock):
     """Device-resident state of one sparse block whose training inputs are Gaussians: L_u, L_B, gamma as a
     :class:`~cimrgp_amd.Sparse.SparseBlock` keeps them ('vfe'), built from the psi statistics."""
 
-    def __init__(self, x_mean, x_var, z, kernel, jitter=1e-6, lengthscales=None):
+    def __init__(self, x_mean, x_var, z, kernel, jitter=1e-6, lengthscales=None, prior_mean=None, prior_var=None):
         """``x_mean`` (n x d), ``z`` (m x d): float64 device tensors in the same units; ``kernel``: an ``RBFKernel`` with its
         ``noise`` set; ``lengthscales``: as for ``SparseBlock`` (ARD; ``kernel.l`` must then be 1.0).  ``x_var``: the
         variances of the inputs in the squared units of ``x_mean`` -- a scalar or a (d,) vector (every row has that
         variance: the shared-variance route, checked non-negative and finite here) or an (n, d) device tensor (the psi
         kernels; a negative or non-finite entry is found by the device and raises ValueError in :meth:`fit`).  A Matern
-        covariance has no closed-form psi statistics and is refused, as are float32 blocks."""
+        covariance has no closed-form psi statistics and is refused, as are float32 blocks.  ``prior_mean``, ``prior_var``
+        (gpflow's ``X_prior_mean`` and ``X_prior_var``): (n, d) device tensors, the prior N(prior_mean, diag prior_var) of the
+        inputs that :meth:`kl` and :meth:`elbo_grad` are taken against; None: 0 and 1, gpflow's default."""
         if getattr(kernel, 'cov', None) != COV_RBF or not hasattr(kernel, 'with_noise'):
             raise TypeError('the psi statistics of %s are not yet supported (RBFKernel only)' % type(kernel).__name__)
         if x_mean.dtype != torch.float64:
@@ -55,7 +62,19 @@ class UncertainInputBlock(SparseBlock):
         self.ell = np.full(d, float(kernel.l)) if self.lengthscales is None else self.lengthscales
         self._ell_dev = torch.as_tensor(self.ell, dtype=torch.float64).to(x_mean.device)
         self.x_var = self._variance(x_var, self.n, x_mean)
-        self.bad = self._f_terms = None
+        self.prior_mean, self.prior_var = self._prior(prior_mean, 'prior_mean'), self._prior(prior_var, 'prior_var')
+        self.bad = self._f_terms = self._fitted = None
+
+    def _prior(self, t, what):
+        """A prior's (n, d) tensor on the block's device, or None; the variances positive, both finite."""
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(self.x.shape):
+            raise ValueError('%s must be an (n, d) tensor' % what)
+        t = t.to(device=self.x.device, dtype=torch.float64).contiguous()
+        if not bool(torch.isfinite(t).all()) or (what == 'prior_var' and not bool((t > 0).all())):
+            raise ValueError('%s must be finite%s' % (what, ' and positive' if what == 'prior_var' else ''))
+        return t
 
     @staticmethod
     def _variance(x_var, n, like):
@@ -131,6 +150,7 @@ class UncertainInputBlock(SparseBlock):
         self.lb[:m, :m] = t / s2
         self.lb[:m, :m].diagonal().add_(1.0)
         self._enqueue_solve(torch.linalg.solve_triangular(lu, g / s2, upper=False).contiguous())
+        self._fitted = (y, t)                              # what bound_grad() starts from beside the factors: Y and T
         self._f_terms = (dict(half_logdet_b=dev.logdet_half(self.lb, m), yy=(y.double() ** 2).sum(), gg=(self.gamma.double() ** 2).sum(),
                               tr_t=torch.diagonal(t).double().sum()), q)
         flags = dict(info_u=self.info_u, info_b=self.info_b)
@@ -158,6 +178,8 @@ class UncertainInputBlock(SparseBlock):
     def kl(self):
         """KL(q(X) || N(0, I)) over the entries with a positive variance (s_ie = 0 is an observed input)."""
         var, mu = self.x_var, self.x.double()
+        if self.prior_mean is not None or self.prior_var is not None:
+            return float(self._kl_parts()[0].item())
         if isinstance(var, torch.Tensor):
             v = var.double()
             pos = v > 0
@@ -171,6 +193,87 @@ class UncertainInputBlock(SparseBlock):
 
     def elbo(self):
         return self.bound() - self.kl()
+
+    def _rows_var(self):
+        """``x_var`` as an (n, d) device tensor: a shared variance vector is broadcast."""
+        var = self.x_var
+        if isinstance(var, torch.Tensor):
+            return var
+        return torch.as_tensor(var, dtype=self.x.dtype).to(self.x.device).expand(self.n, -1).contiguous()
+
+    def _kl_parts(self):
+        """(KL, dKL/dmu, dKL/ds) against the prior on the device, float64: 1/2 [(s + (mu - m0)^2) / v0 - 1 - log(s / v0)] over
+        the entries with s > 0; the gradients are zero at the others (observed inputs)."""
+        v, mu = self._rows_var().double(), self.x.double()
+        pm = torch.zeros_like(mu) if self.prior_mean is None else self.prior_mean
+        pv = torch.ones_like(mu) if self.prior_var is None else self.prior_var
+        pos = v > 0
+        safe, zero = torch.where(pos, v, torch.ones_like(v)), torch.zeros_like(v)
+        kl = 0.5 * torch.where(pos, (safe + (mu - pm) ** 2) / pv - 1.0 - torch.log(safe / pv), zero).sum()
+        return kl, torch.where(pos, (mu - pm) / pv, zero), torch.where(pos, 0.5 * (1.0 / pv - 1.0 / safe), zero)
+
+    # ---- the gradient of the bound ------------------------------------------------------------------------------
+    def bound_grad(self, want_z=True, want_inputs=True):
+        """After :meth:`fit`: ``(F, dtheta, dZ, dmu, ds)`` -- :meth:`bound`'s value, its gradient w.r.t. (log sf, log l, log
+        noise) as a NumPy array (one log l, or d of them with ``lengthscales``), w.r.t. the inducing inputs (m x d) and
+        w.r.t. the inputs' means and variances (n x d each), device tensors in the block's own input units, None where not
+        wanted ("Gradients of the bound on uncertain inputs").  With P = Psi2, A = K_uu + P / s2 = L_u B L_u^T,
+        u = L_B^-T gamma and v = L_u^-T u the weights are
+            G1 = Y v^T / s2        G2 = L_u^-T [q / (2 s2) (I - B^-1) - u u^T / (2 s2)] L_u^-1
+            G_uu = L_u^-T [q/2 (I - B^-1) - 1/2 u u^T - q / (2 s2) T] L_u^-1
+        contracted by cimrgp_psi1_grad, cimrgp_psi2_grad and, for K_uu + eps sf I, the covariance's pair contraction.  The
+        m x m solves are torch's, as in :meth:`fit`.  A shared variance vector is broadcast to (n, d) and takes the per-row
+        kernels: ds is then per row, and the caller sums it over the rows."""
+        if self._fitted is None:
+            raise RuntimeError('call fit() before bound_grad()')
+        y, t = self._fitted
+        k, n, m, q = self.kernel, self.n, self.m, int(y.shape[1])
+        s2, sf, dt, device = k.noise, k.sf, self.z.dtype, self.z.device
+        f = self.bound()
+        lu, lb = torch.tril(self.lu[:m, :m]), torch.tril(self.lb[:m, :m])
+        eye = torch.eye(m, dtype=dt, device=device)
+        u = torch.linalg.solve_triangular(lb.t(), self.gamma, upper=True)
+        v = torch.linalg.solve_triangular(lu.t(), u, upper=True)
+        lb_inv = torch.linalg.solve_triangular(lb, eye, upper=False)
+        i_binv = eye - lb_inv.t() @ lb_inv
+        uu = u @ u.t()
+
+        def between_lu(inner):                      # L_u^-T inner L_u^-1 for a symmetric inner, symmetrised
+            half = torch.linalg.solve_triangular(lu.t(), inner, upper=True)
+            full = torch.linalg.solve_triangular(lu.t(), half.t().contiguous(), upper=True)
+            return 0.5 * (full + full.t())
+
+        g1 = (y @ v.t() / s2).contiguous()
+        g2 = between_lu((0.5 * q / s2) * i_binv - uu / (2.0 * s2)).contiguous()
+        guu = dev.alloc_matrix(m, m, dt, device)
+        guu.zero_()
+        guu[:m, :m] = between_lu(0.5 * q * i_binv - 0.5 * uu - (0.5 * q / s2) * t)
+        var = self._rows_var()
+        dmu, ds, dz, sums1 = devp.psi1_grad(self.x, var, self.z, self._ell_dev, sf, g1)
+        del g1
+        dmu2, ds2, dz2, sums2, bad = devp.psi2_grad(self.x, var, self.z, self._ell_dev, sf, g2)
+        psums, _, dzu = self.cov.pair_grad(self._zs, self._zs, guu, want_z, scale=2.0)
+        h = read_back(dict(tr_guu=torch.diagonal(guu[:m, :m]).double().sum(), tr_ib=torch.diagonal(i_binv).double().sum(),
+                           uu=(u.double() ** 2).sum(), bad=bad, **self._f_terms[0]), dict(sums1=sums1, sums2=sums2, psums=psums))
+        if h['bad'] > 0:
+            raise ValueError('%d of the input rows have a negative or non-finite variance' % int(h['bad']))
+        dsf = h['sums1'][0] + h['sums2'][0] + h['psums'][0] + self.jitter * sf * h['tr_guu'] - 0.5 * q * n * sf / s2
+        dl = h['sums1'][1:] + h['sums2'][1:]
+        dl = dl + h['psums'][1:] if self.lengthscales is not None else np.array([dl.sum() + h['psums'][1]])
+        dnoise = (-0.5 * n * q + 0.5 * q * h['tr_ib'] + 0.5 * h['yy'] / s2 - 0.5 * h['gg'] - 0.5 * h['uu']
+                  + 0.5 * q * (n * sf - h['tr_t']) / s2)
+        dtheta = np.concatenate([[dsf], dl, [dnoise]])
+        if want_z:
+            dz = dz + dz2 + self.cov.chain_rule(dz=dzu)
+        return f, dtheta, dz if want_z else None, dmu + dmu2 if want_inputs else None, ds + ds2 if want_inputs else None
+
+    def elbo_grad(self, want_z=True, want_inputs=True):
+        """:meth:`bound_grad` of F - KL: the KL term's gradient is taken from dmu and ds over the entries with s > 0."""
+        f, dtheta, dz, dmu, ds = self.bound_grad(want_z, want_inputs)
+        kl, kmu, ks = self._kl_parts()
+        if want_inputs:
+            dmu, ds = dmu - kmu.to(dmu.dtype), ds - ks.to(ds.dtype)
+        return f - float(kl.item()), dtheta, dz, dmu, ds
 
     # ---- prediction ---------------------------------------------------------------------------------------------
     def predict(self, xs, mean=None, var=None, include_noise=False, budget_bytes=None, xs_var=None):

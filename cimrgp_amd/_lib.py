@@ -191,6 +191,15 @@ PSI_SIGNATURES = {
     "cimrgp_psi2": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _dbl, _vp, _i64, _vp, _sz, _vp, _vp]),
 }
 
+# include/cimrgp_psi_grad.h: the derivatives of the psi statistics contracted with a weight matrix
+PSI_GRAD_ROW_WGS = 1024
+PSI_GRAD_SIGNATURES = {
+    "cimrgp_psi1_grad_scratch_bytes": (_sz, [_i32, _i64, _i64, _i32]),
+    "cimrgp_psi1_grad": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _dbl, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cimrgp_psi2_grad_scratch_bytes": (_sz, [_i32, _i64, _i64, _i32]),
+    "cimrgp_psi2_grad": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _dbl, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+}
+
 #: header -> its table, in the include order of include/cimrgp.h
 HEADERS = {
     "cimrgp.h": SIGNATURES,
@@ -206,6 +215,7 @@ HEADERS = {
     "cimrgp_sparse_post.h": SPARSE_POST_SIGNATURES,
     "cimrgp_sparse_linear.h": SPARSE_LINEAR_SIGNATURES,
     "cimrgp_psi.h": PSI_SIGNATURES,
+    "cimrgp_psi_grad.h": PSI_GRAD_SIGNATURES,
     "cimrgp_svgp.h": SVGP_SIGNATURES,
 }
 

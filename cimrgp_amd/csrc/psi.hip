@@ -19,10 +19,8 @@
 // tile off the diagonal and inside m (FULL) has no such test, so its 16 exponentials per row interleave freely.
 // Every partial sum is taken in one fixed order: a thread adds its slice's rows in row order, k_psi2_reduce the slices
 // in slice order.
-#include "abi.hpp"
+#include "psi_common.hpp"
 #include "reduce.hpp"
-
-#include <math.h>
 
 namespace cimrgp {
 
@@ -33,43 +31,13 @@ constexpr int PR = 4;                         // pairs per thread and side: 16 x
 constexpr int PCHUNK = 64;                    // rows whose constants are staged at a time
 static_assert(PT == 16 * PR, "a 16 x 16 workgroup of PR x PR register tiles covers the tile");
 
-static __device__ __forceinline__ float t_exp(float x) { return expf(x); }
-static __device__ __forceinline__ double t_exp(double x) { return exp(x); }
-
-// the input dimension as a compile-time D = d exactly, 1 .. MAXD (validated by the entry points)
-template <typename F> static inline auto with_dim_exact(int d, F&& f)
-{
-    switch (d) {
-        case 1: return f(std::integral_constant<int, 1>());
-        case 2: return f(std::integral_constant<int, 2>());
-        case 3: return f(std::integral_constant<int, 3>());
-        case 4: return f(std::integral_constant<int, 4>());
-        case 5: return f(std::integral_constant<int, 5>());
-        case 6: return f(std::integral_constant<int, 6>());
-        case 7: return f(std::integral_constant<int, 7>());
-        default: return f(std::integral_constant<int, 8>());
-    }
-}
-
-// S(n, m) and the slice length: the rule of include/cimrgp_psi.h, a function of n and m alone.
-static inline int64_t psi2_tiles_1d(int64_t m) { return (m + PT - 1) / PT; }
-static inline int64_t psi2_tiles(int64_t m) { const int64_t t = psi2_tiles_1d(m); return t * (t + 1) / 2; }
-static inline int64_t psi2_slice_len(int64_t n, int64_t m)
-{
-    int64_t s = CIMRGP_PSI2_TARGET_WGS / psi2_tiles(m);
-    const int64_t smax = (n + CIMRGP_PSI2_MIN_SLICE - 1) / CIMRGP_PSI2_MIN_SLICE;
-    if (s > smax) s = smax;
-    if (s < 1) s = 1;
-    const int64_t len = (n + s - 1) / s;
-    return (len + CIMRGP_PSI2_SLICE_ALIGN - 1) / CIMRGP_PSI2_SLICE_ALIGN * CIMRGP_PSI2_SLICE_ALIGN;
-}
-static inline int64_t psi2_slices(int64_t n, int64_t m) { const int64_t len = psi2_slice_len(n, m); return (n + len - 1) / len; }
-static inline bool psi2_sizes_ok(int64_t n, int64_t m) { return n >= 1 && n <= CIMRGP_PSI2_MAX_N && m >= 1 && m <= CIMRGP_PSI2_MAX_M; }
+// S(n, m) and the slice length: the rule of include/cimrgp_psi.h, a function of n and m alone (psi_common.hpp).
+static inline int64_t psi2_tiles_1d(int64_t m) { return psi_tiles_1d(m, PT); }
+static inline int64_t psi2_tiles(int64_t m) { return psi_tiles(m, PT); }
+static inline int64_t psi2_slice_len(int64_t n, int64_t m) { return psi_slice_len(n, psi2_tiles(m), CIMRGP_PSI2_TARGET_WGS); }
+static inline int64_t psi2_slices(int64_t n, int64_t m) { return psi_slice_count(n, psi2_slice_len(n, m)); }
 
 // the three parts of the scratch in bytes, each a multiple of 16: the counts, the rows' constants, the partial tiles
-static inline int64_t round16(int64_t b) { return (b + 15) / 16 * 16; }
-static inline int64_t psi2_count_blocks(int64_t n) { return (n + 255) / 256; }
-static inline int64_t psi2_count_bytes(int64_t n) { return round16(psi2_count_blocks(n) * 8); }
 static inline int64_t psi2_rows_bytes(int dtype, int64_t n, int d) { return round16(n * (2 * d + 1) * (int64_t)elem_bytes(dtype)); }
 static inline int64_t psi2_part_bytes(int dtype, int64_t n, int64_t m)
 {
@@ -141,15 +109,6 @@ void k_psi2_rows(const T* __restrict__ mu, const T* __restrict__ s, int n, const
     }
     bad = block_sum(bad, red);
     if (threadIdx.x == 0) badpart[blockIdx.x] = bad;
-}
-
-// tile number -> (ti, tj), tj <= ti: column tj of the triangle holds tiles1d - tj tiles, the diagonal one first
-static __device__ __forceinline__ void psi2_tile_of(int tile, int tiles1d, int& ti, int& tj)
-{
-    int first = 0;
-    tj = 0;
-    while (tile >= first + (tiles1d - tj)) { first += tiles1d - tj; ++tj; }
-    ti = tj + (tile - first);
 }
 
 template <typename T, int D, bool FULL>

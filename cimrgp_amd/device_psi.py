@@ -47,3 +47,44 @@ def psi2(mu, s, z, ell, sf2, out=None, scratch=None, bad=None):
     scratch = _byte_scratch(psi2_scratch_bytes(n, m, d, mu.dtype), mu.device, scratch)
     _call("cimrgp_psi2", mu.dtype, mu, s, z, n, m, d, ell, sf2, out, out.stride(0), scratch, scratch.numel(), bad)
     return out, bad
+
+
+def _weights(g, rows, cols, like):
+    """``g``: the weight matrix of a gradient call, at least (rows, cols), of ``like``'s dtype, unit column stride."""
+    if g.dim() != 2 or g.shape[0] < rows or g.shape[1] < cols or g.dtype != like.dtype or g.device != like.device or g.stride(1) != 1:
+        raise ValueError("the weight matrix must be a (%d x %d) row-major matrix of the operands' dtype on their device" % (rows, cols))
+
+
+def psi1_grad_scratch_bytes(n, m, d, dtype):
+    return _size("cimrgp_psi1_grad_scratch_bytes", dtype, n, m, d)
+
+
+def psi1_grad(mu, s, z, ell, sf2, g1, dmu=None, ds=None, dz=None, sums=None, scratch=None):
+    """The derivatives of sum g1 o Psi1 for the weights g1 (n x m, any pitch) (cimrgp_psi1_grad, include/cimrgp_psi_grad.h).
+    Returns (dmu (n, d), ds (n, d), dz (m, d), sums): sums device float64[d + 1] = [d/dlog sf2, d/dlog l_e ..]; every output
+    is overwritten and allocated if None, the scratch for this call only if None."""
+    n, m, d = _operands(mu, s, z, ell)
+    _weights(g1, n, m, mu)
+    dmu, ds, dz = _given(dmu, (n, d), mu), _given(ds, (n, d), mu), _given(dz, (m, d), mu)
+    sums = _given(sums, (d + 1,), mu, torch.float64)
+    scratch = _byte_scratch(psi1_grad_scratch_bytes(n, m, d, mu.dtype), mu.device, scratch)
+    _call("cimrgp_psi1_grad", mu.dtype, mu, s, z, n, m, d, ell, sf2, g1, g1.stride(0), dmu, ds, dz, sums, scratch, scratch.numel())
+    return dmu, ds, dz, sums
+
+
+def psi2_grad_scratch_bytes(n, m, d, dtype):
+    return _size("cimrgp_psi2_grad_scratch_bytes", dtype, n, m, d)
+
+
+def psi2_grad(mu, s, z, ell, sf2, g2, dmu=None, ds=None, dz=None, sums=None, scratch=None, bad=None):
+    """The derivatives of sum g2 o Psi2 for the SYMMETRIC weights g2 (m x m, any pitch; only its lower triangle is read)
+    (cimrgp_psi2_grad).  Returns (dmu, ds, dz, sums, bad) as :func:`psi1_grad` and :func:`psi2` have them: sums[0] =
+    2 sum g2 o Psi2; a row with a negative or non-finite variance is counted in bad and has zeros in dmu and ds."""
+    n, m, d = _operands(mu, s, z, ell)
+    _weights(g2, m, m, mu)
+    dmu, ds, dz = _given(dmu, (n, d), mu), _given(ds, (n, d), mu), _given(dz, (m, d), mu)
+    sums = _given(sums, (d + 1,), mu, torch.float64)
+    bad = _given(bad, (1,), mu, torch.float64)
+    scratch = _byte_scratch(psi2_grad_scratch_bytes(n, m, d, mu.dtype), mu.device, scratch)
+    _call("cimrgp_psi2_grad", mu.dtype, mu, s, z, n, m, d, ell, sf2, g2, g2.stride(0), dmu, ds, dz, sums, scratch, scratch.numel(), bad)
+    return dmu, ds, dz, sums, bad

@@ -510,6 +510,10 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
  * include/cimrgp_psi.h. */
 #include "cimrgp_psi.h"
 
+/* The derivatives of the psi statistics contracted with a weight matrix, for the analytic gradient of the bound on
+ * uncertain inputs: include/cimrgp_psi_grad.h. */
+#include "cimrgp_psi_grad.h"
+
 /* The variational sparse GP with a non-conjugate likelihood (Gaussian or Student-t): the Gauss-Hermite row pass over A
  * and W: include/cimrgp_svgp.h. */
 #include "cimrgp_svgp.h"
