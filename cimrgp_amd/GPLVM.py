@@ -27,7 +27,8 @@ class BayesianGPLVM(BGPLVM):
     ``optimize=True`` runs one L-BFGS-B over [log sf, log l (d under ARD), log noise, (Z.ravel()), (mu and then log s of the
     learned entries)], maximising F - KL.  After the fit: ``input_means`` and ``input_variances`` ((n, d), the caller's units),
     and ``inducing_inputs``, ``lengthscales``, ``kernel`` and ``optimizer_result`` as on the parent.  What the parent does not
-    build -- float32, the five further posterior queries, the variance at uncertain test inputs -- is not built here."""
+    build -- float32, the five further posterior queries -- is not built here; the variance at uncertain test inputs, which
+    the parent's ``predict_with_variance(test_var=)`` refuses (here too), is :meth:`predict_uncertain`."""
     name = 'BayesianGPLVM'
 
     def __init__(self, num_inducing=100, X_var=None, noise=1.0, lengthscale=1., variance=1., ARD=True, Z=None, seed=0, jitter=1e-6,
@@ -129,6 +130,25 @@ class BayesianGPLVM(BGPLVM):
         self.input_means = mu * std + self.data_mean if self.preprocess else mu
         self.input_variances = s * std ** 2
         return True
+
+    def predict_uncertain(self, test_data, test_var, include_noise=False, budget_bytes=None):
+        """``(mean, var)`` at the uncertain test inputs N(test_data, diag test_var); ``test_var``: a scalar, (d,) or (ns, d), in
+        the caller's (squared) units.  The mean (ns, q) is un-z-scored, as ``predict(test_data, test_var=)`` returns it; the
+        variance is (ns, q) -- the spread of the posterior mean over the input's distribution differs from output to output --
+        and is left in z-scored label units, as ``predict_with_variance`` leaves it (latent; ``include_noise`` adds the noise)
+        (:meth:`~cimrgp_amd.Psi.UncertainInputBlock.predict_moments`).  ``budget_bytes``: work area of the chunked
+        prediction."""
+        blk = self._fitted_block('predict_uncertain')
+        test_data = np.atleast_2d(np.asarray(test_data, dtype=np.float64))
+        xs_var = self._variances(test_var, test_data.shape[0], test_data.shape[1], 'test_var')
+        if self.preprocess:
+            test_data = self._preprocess(test_data, False)
+        xs = self._test_inputs(test_data)
+        mean = torch.empty((xs.shape[0], self._y.shape[1]), dtype=self.dtype, device=xs.device)
+        var = torch.empty_like(mean)
+        blk.predict_moments(xs, xs_var, mean, var, include_noise=include_noise, budget_bytes=budget_bytes)
+        mean = mean.double().cpu().numpy()
+        return self._reverse_trans_labels(mean) if self.preprocess else mean, var.double().cpu().numpy()
 
     def kl_divergence(self):
         """KL(q(X) || the inputs' prior) of the (z-scored) inputs' distributions (``input_prior``)."""

@@ -24,6 +24,10 @@ The n x m and n x m^2 work is those C calls; torch holds the buffers and does th
 means and variances ("Gradients of the bound on uncertain inputs"): the weights dF/dPsi1, dF/dPsi2 and dF/dK_uu are
 m x m torch algebra on the fit's factors, their contractions cimrgp_psi1_grad, cimrgp_psi2_grad (include/cimrgp_psi_grad.h)
 and the covariance's pair contraction.  By either route of the fit the gradient takes the per-row kernels.
+
+``predict_moments`` gives the predictive mean and variance at uncertain TEST inputs ("Predictive variance at
+uncertain test inputs"): the law of total variance over the input's distribution, whose n m^2 / 2 exponentials are
+cimrgp_psi2_rows_quad (include/cimrgp_psi_rows.h) -- a row's own Psi2 contracted with two weights and never stored.
 """
 import numpy as np
 import torch
@@ -37,6 +41,13 @@ from .Sparse import SparseBlock, read_back
 
 def _not_built(what):
     raise TypeError('%s of a block with uncertain inputs is not yet supported' % what)
+
+
+def _between(lu, inner):
+    """L_u^-T inner L_u^-1 for a symmetric ``inner`` (m x m), symmetrised; ``lu``: L_u as a lower-triangular tensor."""
+    half = torch.linalg.solve_triangular(lu.t(), inner, upper=True)
+    full = torch.linalg.solve_triangular(lu.t(), half.t().contiguous(), upper=True)
+    return 0.5 * (full + full.t())
 
 
 class UncertainInputBlock(SparseBlock):
@@ -238,11 +249,7 @@ class UncertainInputBlock(SparseBlock):
         i_binv = eye - lb_inv.t() @ lb_inv
         uu = u @ u.t()
 
-        def between_lu(inner):                      # L_u^-T inner L_u^-1 for a symmetric inner, symmetrised
-            half = torch.linalg.solve_triangular(lu.t(), inner, upper=True)
-            full = torch.linalg.solve_triangular(lu.t(), half.t().contiguous(), upper=True)
-            return 0.5 * (full + full.t())
-
+        between_lu = lambda inner: _between(lu, inner)
         g1 = (y @ v.t() / s2).contiguous()
         g2 = between_lu((0.5 * q / s2) * i_binv - uu / (2.0 * s2)).contiguous()
         guu = dev.alloc_matrix(m, m, dt, device)
@@ -279,7 +286,8 @@ class UncertainInputBlock(SparseBlock):
     def predict(self, xs, mean=None, var=None, include_noise=False, budget_bytes=None, xs_var=None):
         """``SparseBlock.predict`` at exact test inputs.  ``xs_var`` (a scalar, a (d,) vector or an (ns, d) device
         tensor): the test inputs are Gaussians too and the mean is E_x* [k(x*, Z)] K_uu^-1 .. = Psi1* L_u^-T L_B^-T gamma;
-        the variance at uncertain test inputs is not built."""
+        the variance at uncertain test inputs is (ns, q), not this method's (ns,): it is :meth:`predict_moments`', and
+        ``var`` with ``xs_var`` stays refused here."""
         if xs_var is None:
             return SparseBlock.predict(self, xs, mean, var, include_noise, budget_bytes)
         if var is not None:
@@ -292,6 +300,56 @@ class UncertainInputBlock(SparseBlock):
             cross = lambda s0, s1, out: self._psi1(xs[s0:s1], rows(s0, s1), out=out)
             for s0, s1, _, wstar in self._star_chunks(xs, budget_bytes, cross=cross):
                 dev.sparse_tail(None, wstar, s1 - s0, self.m, self.gamma, self.kernel.sf, 0.0, mean[s0:s1], None, False)
+        return mean, var
+
+    def predict_moments(self, xs, xs_var, mean=None, var=None, include_noise=False, budget_bytes=None):
+        """Predictive mean into ``mean`` and variance into ``var`` (both (ns, q) device tensors, either may be None) at the
+        uncertain test inputs x*_i ~ N(xs_i, diag xs_var_i); ``xs_var``: a scalar, a (d,) vector or an (ns, d) device tensor
+        ("Predictive variance at uncertain test inputs").  By the law of total variance, with
+        C = L_u^-T (I - B^-1) L_u^-1, a = L_u^-T L_B^-T gamma and Psi2*_i the row's own Psi2,
+            var_ic = sf - sum C o Psi2*_i  +  a_c^T Psi2*_i a_c - mean_ic^2   (+ noise with ``include_noise``)
+        the latent variance averaged over the input, and the variance of the posterior mean over it, which depends on the
+        output column.  C and a are m x m torch algebra on the fit's factors, once per call; the two contractions are
+        cimrgp_psi2_rows_quad (include/cimrgp_psi_rows.h), chunk by chunk beside the mean, which is :meth:`predict`'s own
+        path (the same bits as ``predict(xs, mean, xs_var=xs_var)`` for a per-row ``xs_var``).  A shared variance is
+        broadcast to (ns, d) and takes the per-row kernels, as in :meth:`bound_grad`: a factorised shared route is not
+        built.  A row's results do not depend on the chunking.  One host read at the end, the count of rows with a negative
+        or non-finite variance: ValueError if there are any."""
+        ns = int(xs.shape[0])
+        sv = self._variance(xs_var, ns, xs)
+        if self.gamma is None:
+            raise RuntimeError('call fit() before predict_moments()')
+        if not isinstance(sv, torch.Tensor):
+            sv = torch.as_tensor(sv, dtype=xs.dtype).to(xs.device).expand(ns, -1).contiguous()
+        if var is None:
+            return self.predict(xs, mean, None, budget_bytes=budget_bytes, xs_var=sv)
+        k, m, q, dt, device = self.kernel, self.m, int(self.gamma.shape[1]), self.z.dtype, self.z.device
+        if mean is None:
+            mean = torch.empty((ns, q), dtype=dt, device=device)
+        lu, lb = torch.tril(self.lu[:m, :m]), torch.tril(self.lb[:m, :m])
+        eye = torch.eye(m, dtype=dt, device=device)
+        lb_inv = torch.linalg.solve_triangular(lb, eye, upper=False)
+        c = _between(lu, eye - lb_inv.t() @ lb_inv).contiguous()
+        a = torch.empty((m, q), dtype=dt, device=device)         # row-major whatever q is (a solve's (m, 1) result need not be)
+        a.copy_(torch.linalg.solve_triangular(lu.t(), torch.linalg.solve_triangular(lb.t(), self.gamma, upper=True), upper=True))
+        tr = torch.empty(ns, dtype=dt, device=device)
+        bad, bad_chunk, scratch = torch.zeros(1, dtype=torch.float64, device=device), torch.empty(1, dtype=torch.float64, device=device), None
+        xs = xs.contiguous()
+        cross = lambda s0, s1, out: self._psi1(xs[s0:s1], sv[s0:s1], out=out)
+        for s0, s1, _, wstar in self._star_chunks(xs, budget_bytes, cross=cross):
+            dev.sparse_tail(None, wstar, s1 - s0, m, self.gamma, k.sf, 0.0, mean[s0:s1], None, False)
+            if scratch is None:
+                scratch = torch.empty(max(16, devp.psi2_rows_quad_scratch_bytes(s1 - s0, m, int(xs.shape[1]), q, dt)), dtype=torch.uint8,
+                                      device=device)
+            devp.psi2_rows_quad(xs[s0:s1], sv[s0:s1], self.z, self._ell_dev, k.sf, c, a, tr=tr[s0:s1], quad=var[s0:s1], scratch=scratch,
+                                bad=bad_chunk)
+            bad += bad_chunk
+        var.sub_(mean * mean).add_((k.sf - tr)[:, None])
+        if include_noise:
+            var.add_(k.noise)
+        count = float(bad.item())
+        if count > 0:
+            raise ValueError('%d of the test rows have a negative or non-finite variance' % int(count))
         return mean, var
 
     # ---- what a block with uncertain inputs does not answer ---------------------------------------------------------

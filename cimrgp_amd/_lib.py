@@ -200,6 +200,14 @@ PSI_GRAD_SIGNATURES = {
     "cimrgp_psi2_grad": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _dbl, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
 }
 
+# include/cimrgp_psi_rows.h: one row's own Psi2 contracted with weights (the variance at uncertain test inputs)
+PSI_ROWS_GROUPS = 16
+PSI_ROWS_SIGNATURES = {
+    "cimrgp_psi2_rows_quad_scratch_bytes": (_sz, [_i32, _i64, _i64, _i32, _i32]),
+    "cimrgp_psi2_rows_quad": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _dbl, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp,
+                                     _sz, _vp, _vp]),
+}
+
 #: header -> its table, in the include order of include/cimrgp.h
 HEADERS = {
     "cimrgp.h": SIGNATURES,
@@ -216,6 +224,7 @@ HEADERS = {
     "cimrgp_sparse_linear.h": SPARSE_LINEAR_SIGNATURES,
     "cimrgp_psi.h": PSI_SIGNATURES,
     "cimrgp_psi_grad.h": PSI_GRAD_SIGNATURES,
+    "cimrgp_psi_rows.h": PSI_ROWS_SIGNATURES,
     "cimrgp_svgp.h": SVGP_SIGNATURES,
 }
 

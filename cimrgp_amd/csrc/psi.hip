@@ -75,42 +75,7 @@ void k_psi1(const T* __restrict__ mu, const T* __restrict__ s, const T* __restri
 }
 
 // ----------------------------------------------------------------------- psi2 ----
-// rc[i] = (mu_i0 .. mu_i,D-1, r_i0 .. r_i,D-1, c0_i); badpart[blockIdx.x] = the workgroup's count of bad rows.
-template <typename T, int D>
-__global__ __launch_bounds__(256)
-void k_psi2_rows(const T* __restrict__ mu, const T* __restrict__ s, int n, const double* __restrict__ ell, T* __restrict__ rc,
-                 double* __restrict__ badpart)
-{
-    constexpr int RS = 2 * D + 1;
-    __shared__ double red[16];
-    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
-    double bad = 0.0;
-    if (i < n) {
-        T o[RS];
-        double lg = 0.0;
-        bool ok = true;
-#pragma unroll
-        for (int e = 0; e < D; ++e) {
-            const double sv = (double)s[(int64_t)i * D + e], l2 = ell[e] * ell[e];
-            ok = ok && sv >= 0.0 && sv - sv == 0.0;              // not negative, not NaN, not infinite
-            o[e] = mu[(int64_t)i * D + e];
-            o[D + e] = (T)(1.0 / (l2 + 2.0 * sv));
-            lg += log1p(2.0 * sv / l2);
-        }
-        o[2 * D] = (T)(-0.5 * lg);
-        if (!ok) {
-            bad = 1.0;
-#pragma unroll
-            for (int k = 0; k < 2 * D; ++k) o[k] = (T)0;
-            o[2 * D] = -(T)INFINITY;
-        }
-#pragma unroll
-        for (int k = 0; k < RS; ++k) rc[(int64_t)i * RS + k] = o[k];
-    }
-    bad = block_sum(bad, red);
-    if (threadIdx.x == 0) badpart[blockIdx.x] = bad;
-}
-
+// (k_psi2_rows, the pass over the rows: psi_common.hpp)
 template <typename T, int D, bool FULL>
 static __device__ __forceinline__ void psi2_tile(T* __restrict__ lds, const T* __restrict__ z, int m, const T* __restrict__ rc, int ti,
                                                  int tj, int k0, int k1, T* __restrict__ ctile)

@@ -1,5 +1,6 @@
-"""Wrappers of include/cimrgp_psi.h: the psi statistics of the RBF covariance under Gaussian inputs ("Sparse GP
-regression on uncertain inputs").  Each is one ``device._call``, as the wrappers of ``device.py`` are."""
+"""Wrappers of include/cimrgp_psi.h, cimrgp_psi_grad.h and cimrgp_psi_rows.h: the psi statistics of the RBF covariance under
+Gaussian inputs ("Sparse GP regression on uncertain inputs").  Each is one ``device._call``, as the wrappers of
+``device.py`` are."""
 import torch
 
 from .device import _byte_scratch, _call, _given, _size, alloc_matrix
@@ -88,3 +89,30 @@ def psi2_grad(mu, s, z, ell, sf2, g2, dmu=None, ds=None, dz=None, sums=None, scr
     scratch = _byte_scratch(psi2_grad_scratch_bytes(n, m, d, mu.dtype), mu.device, scratch)
     _call("cimrgp_psi2_grad", mu.dtype, mu, s, z, n, m, d, ell, sf2, g2, g2.stride(0), dmu, ds, dz, sums, scratch, scratch.numel(), bad)
     return dmu, ds, dz, sums, bad
+
+
+def psi2_rows_quad_scratch_bytes(n, m, d, q, dtype):
+    return _size("cimrgp_psi2_rows_quad_scratch_bytes", dtype, n, m, d, q)
+
+
+def psi2_rows_quad(mu, s, z, ell, sf2, c, a, tr=None, quad=None, scratch=None, bad=None):
+    """Per row i its own Psi2_i = E k(Z, x_i) k(x_i, Z), contracted and never stored (cimrgp_psi2_rows_quad,
+    include/cimrgp_psi_rows.h): tr[i] = sum c o Psi2_i for the SYMMETRIC weights c (m x m, any pitch; only its lower triangle
+    is read) and quad[i][k] = a_k^T Psi2_i a_k for the columns of a (m x q, any pitch).  Returns (tr (n,), quad (n, q), bad):
+    every output is overwritten and allocated if None, the scratch for this call only if None; a row with a negative or
+    non-finite variance is counted in bad (device float64 (1,)) and has zeros in tr and quad.  A row's results do not
+    depend on n or on where the row lies in the operands."""
+    n, m, d = _operands(mu, s, z, ell)
+    _weights(c, m, m, mu)
+    if a.dim() != 2 or a.shape[0] < m:
+        raise ValueError("a must be an (m x q) matrix")
+    q = int(a.shape[1])
+    _weights(a, m, q, mu)
+    tr, quad = _given(tr, (n,), mu), _given(quad, (n, q), mu)
+    if quad.dim() != 2 or quad.stride(1) != 1 or tr.dim() != 1 or tr.stride(0) != 1:
+        raise ValueError("tr must be a contiguous (n,) vector and quad a row-major (n x q) matrix")
+    bad = _given(bad, (1,), mu, torch.float64)
+    scratch = _byte_scratch(psi2_rows_quad_scratch_bytes(n, m, d, q, mu.dtype), mu.device, scratch)
+    _call("cimrgp_psi2_rows_quad", mu.dtype, mu, s, z, n, m, d, ell, sf2, c, c.stride(0), a, a.stride(0), q, tr, quad, quad.stride(0),
+          scratch, scratch.numel(), bad)
+    return tr, quad, bad

@@ -514,6 +514,10 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
  * uncertain inputs: include/cimrgp_psi_grad.h. */
 #include "cimrgp_psi_grad.h"
 
+/* One row's own Psi2 contracted with weights, for the predictive variance at uncertain test inputs:
+ * include/cimrgp_psi_rows.h. */
+#include "cimrgp_psi_rows.h"
+
 /* The variational sparse GP with a non-conjugate likelihood (Gaussian or Student-t): the Gauss-Hermite row pass over A
  * and W: include/cimrgp_svgp.h. */
 #include "cimrgp_svgp.h"
