@@ -97,6 +97,38 @@ def test_psi_grad_kernels_match_the_longdouble_oracle(ca, dt, n, m, d):
         assert pg._slices_for(n, 1)[0] >= 3 and n % pg._slices_for(n, 1)[1] != 0
 
 
+#: cimrgp_psi1_grad with slices longer than one 64-row chunk: m = 4096 gives 64 column blocks and so at most 32 slices, and
+#: n = 2113 then 27 slices of 80 rows, a chunk of 64 and one of 16 (asserted below)
+CHUNKED = (2113, 4096, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def _chunked_case():
+    """The problem at CHUNKED with g1 and the longdouble psi1_grad and its bounds' weights, once for both dtypes."""
+    n, m, d = CHUNKED
+    mu, s, z, _ = po.problem(n, m, d, 100 * n + m, ell0=ELLS[0])
+    mu, s, z = _f32(mu), _f32(s), _f32(z)
+    ell, g1 = np.array(ELLS[:d]), _f32(np.random.RandomState(7 * n + m).randn(n, m))
+    return dict(mu=mu, s=s, z=z, ell=ell, g1=g1,
+                ref=(pg.psi1_grad(mu, s, z, ell, SF, g1, LD), pg.psi1_grad(mu, s, z, ell, SF, g1, LD, bound=True)))
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+def test_psi1_grad_over_slices_of_several_chunks_matches_the_longdouble_oracle(ca, dt):
+    """The bound of test_psi_grad_kernels_match_the_longdouble_oracle at the one cheap shape whose slices span two chunks."""
+    from cimrgp_amd import device_psi as devp
+    n, m, d = CHUNKED
+    assert pg._slices_for(n, -(-m // 64)) == (27, 80)
+    c = _chunked_case()
+    mu, s, z, ell = _dev(c["mu"], dt), _dev(c["s"], dt), _dev(c["z"], dt), _ell_dev(c["ell"])
+    g1 = torch.full((n, ca.device.padded_ld(m)), float("nan"), dtype=TDT[dt], device="cuda")
+    g1[:, :m] = _dev(c["g1"], dt)
+    one, again = devp.psi1_grad(mu, s, z, ell, SF, g1), devp.psi1_grad(mu, s, z, ell, SF, g1)
+    for a, b in zip(one, again):
+        assert torch.equal(_bits(a), _bits(b))
+    assert _show("psi1_grad %s (%d, %d, %d)" % (dt, n, m, d), _ratios(_host(one), c["ref"], UNIT[dt])) <= 1.0
+
+
 @pytest.mark.parametrize("dt", ["f64", "f32"])
 @pytest.mark.parametrize("n,m,d", [(300, 65, 3), (150, 40, 2)])
 def test_bad_rows_are_counted_zeroed_and_add_nothing(ca, dt, n, m, d):

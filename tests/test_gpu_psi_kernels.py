@@ -17,8 +17,9 @@ torch = pytest.importorskip("torch")
 TDT = {"f64": torch.float64, "f32": torch.float32}
 UNIT = {"f64": 2.0 ** -53, "f32": 2.0 ** -24}
 #: (n, m, d): one of each; ragged tiles of 64; m one past a tile and d = 3; two tile rows and the largest d; and n = 150, which
-#: the header's rule cuts into three slices of 64 rows, the last one ragged (asserted below)
-SHAPES = [(1, 1, 1), (255, 63, 2), (300, 65, 3), (257, 130, 8), (150, 40, 2)]
+#: the header's rule cuts into three slices of 64 rows, the last one ragged (asserted below); then the remaining instances of
+#: d at (130, 70): two tile rows at edge 64 and three at edge 32 with a ragged last tile, three slices
+SHAPES = [(1, 1, 1), (255, 63, 2), (300, 65, 3), (257, 130, 8), (150, 40, 2)] + [(130, 70, d) for d in (4, 5, 6, 7)]
 SLICED = (150, 40, 2)
 #: exactly representable in float32, so that both dtypes see the same problem and share one reference
 SF = 1.375

@@ -166,11 +166,27 @@ def test_psi_grad_header_symbols_are_exported_and_registered():
     assert order.index("cimrgp_psi_grad.h") == order.index("cimrgp_psi.h") + 1
     assert " psi_grad " in open(os.path.join(ROOT, "cimrgp_amd", "csrc", "build.sh")).read()
     assert int(re.search(r"#define CIMRGP_PSI_GRAD_ROW_WGS (\d+)", text).group(1)) == _lib.PSI_GRAD_ROW_WGS
-    # the helpers both sources need live in one header, and psi.hip keeps none of its own
-    common = open(os.path.join(ROOT, "cimrgp_amd", "csrc", "psi_common.hpp")).read()
-    psi = open(os.path.join(ROOT, "cimrgp_amd", "csrc", "psi.hip")).read()
-    for helper in ("with_dim_exact(int d", "psi_slice_len(int64_t n", "void psi2_tile_of(int tile", "t_exp(double x)"):
-        assert helper in common and helper not in psi, helper
+    # the helpers the three sources need live in one header, and none of the sources keeps a copy of its own
+    csrc = os.path.join(ROOT, "cimrgp_amd", "csrc")
+    common = open(os.path.join(csrc, "psi_common.hpp")).read()
+    sources = {name: open(os.path.join(csrc, name)).read() for name in ("psi.hip", "psi_grad.hip", "psi_rows.hip")}
+    for helper in ("with_dim_exact(int d", "psi_slice_len(int64_t n", "void psi2_tile_of(int tile", "t_exp(double x)",
+                   "void k_psi2_rows(const T* __restrict__ mu", "psi2_rows_bytes(int dtype", "T psi_ordered_sum(const T* __restrict__ part",
+                   "void psi2_count_bad(const double* __restrict__ badpart", "T psi1_row_consts(const T* __restrict__ mu",
+                   "T psi1_exponent(T c0, const T* mv, const T* z, const T* hr, T* df)", "T psi2_exponent(T c0",
+                   "T psi2_own_row(const T* __restrict__ rc", "void psi2_stage_points(const T* __restrict__ z",
+                   "void psi2_stage_chunk(T* lds", "void psi2_pair_points(const T* __restrict__ z"):
+        assert common.count(helper) == 1, helper
+        for name, text in sources.items():
+            assert helper not in text, (name, helper)
+    for name, text in sources.items():
+        # one pass over the rows for every Psi2 call; the bad-row count and the chunk staging are written in the header only
+        assert "k_psi2g_rows" not in text and "psirq_rc_bytes" not in text, name
+        assert "b += badpart[i]" not in text and "rc[(int64_t)kb * RS + idx]" not in text, name
+        assert "log1p(" not in text and "dl * dl" not in text and "(T)0.5 * z[" not in text, name
+        assert "rc[(int64_t)i * RS + D + e]" not in text, name
+        assert '#include "psi_common.hpp"' in text, name
+    assert common.count("b += badpart[i]") == 1 and "lds_settle(lds + idx)" in common
 
 
 # ---- refusals --------------------------------------------------------------------------------------------------------
