@@ -265,9 +265,13 @@ class SparseKernel(object):
     A region of n rows gets m = min(n, ``num_inducing``) inducing inputs, rows of the region's own (normalised, warped)
     inputs picked by ``inducing``: ``'stride'`` -- rows floor((k + 0.5) n / m), k = 0 .. m - 1 (every row, in order, when
     m = n) -- or ``'random'`` -- ``numpy.random.RandomState([seed, layer, region]).permutation(n)[:m]``.  Either is a
-    function of (seed, layer, region, n) alone.  ``jitter``: eps of K_uu + eps sf I.  ``ard`` is the wrapped kernel's too:
+    function of (seed, layer, region, n) alone.  ``'greedy'`` picks the m rows of largest conditional variance under the
+    wrapped kernel as the layer was constructed (``Inducing.greedy_rows``; DESIGN.md, "Greedy inducing-point selection"): a
+    function of the region's inputs and that kernel alone, made once per region on the device and kept, so
+    ``Sparse.SparsePosterior.inducing_rows`` has them and :meth:`inducing_rows`, which has no data, does not.
+    ``jitter``: eps of K_uu + eps sf I.  ``ard`` is the wrapped kernel's too:
     a base with per-dimension length-scales makes an ARD sparse layer."""
-    INDUCING = ('stride', 'random')
+    INDUCING = ('stride', 'random', 'greedy')
 
     def __init__(self, kernel, num_inducing=1000, approximation='fitc', jitter=1e-6, inducing='stride', seed=0):
         from .Sparse import APPROXIMATIONS
@@ -280,7 +284,7 @@ class SparseKernel(object):
         if not float(jitter) >= 0:
             raise ValueError('jitter must not be negative')
         if inducing not in self.INDUCING:
-            raise ValueError("inducing must be 'stride' or 'random', got %r" % (inducing,))
+            raise ValueError("inducing must be 'stride', 'random' or 'greedy', got %r" % (inducing,))
         self.kernel = kernel
         self.num_inducing = int(num_inducing)
         self.approximation = str(approximation).lower()
@@ -314,7 +318,10 @@ class SparseKernel(object):
 
     def inducing_rows(self, layer, region, n):
         """Row numbers (int64, length min(n, num_inducing)) of the inducing inputs of region ``region`` of layer ``layer``
-        with ``n`` rows."""
+        with ``n`` rows.  ``'greedy'`` rows depend on the region's inputs, which this object never sees: TypeError."""
+        if self.inducing == 'greedy':
+            raise TypeError("the rows of inducing='greedy' are a function of the region's inputs: "
+                            "ask SparsePosterior.inducing_rows(region) after the fit")
         n = int(n)
         m = min(n, self.num_inducing)
         if self.inducing == 'stride':

@@ -535,6 +535,8 @@ class SparsePosterior(object):
         self.blocks = [None] * self.n_regions
         self._z = {}                     # region -> (key of its inputs, Z on the device)
         self._scale = {}                 # region -> 1 / l on the device, of the last fit under an ARD base kernel
+        self._greedy = {}                # inducing='greedy': region -> (key of its inputs, rows on the device, Z)
+        self._greedy_kernel = kernel.kernel      # ... under the base kernel of the layer as constructed
 
     def needs_whole_layer(self):
         """As ``DensePosterior.needs_whole_layer``: a shared bias, or a shared noise taken from the targets."""
@@ -542,12 +544,36 @@ class SparsePosterior(object):
 
     def inducing_rows(self, region):
         """Row numbers, within region ``region``, of its inducing inputs: a function of the kernel's (inducing, seed), the
-        layer, the region and its number of rows alone -- never of the rank count or of ownership."""
+        layer, the region and its number of rows alone -- never of the rank count or of ownership.  ``inducing='greedy'``:
+        the rows selected at the region's first fit, read back from the device here (a function of the region's inputs
+        and the constructor's kernel alone); RuntimeError before that."""
+        if self.kernel.inducing == 'greedy':
+            if region not in self._greedy:
+                raise RuntimeError('region %d of layer %d has no greedy rows yet: they are selected at its first fit'
+                                   % (region, self.layer))
+            return self._greedy[region][1].cpu().numpy()
         return self.kernel.inducing_rows(self.layer, region, self.n_rows[region])
+
+    def _greedy_inputs(self, l, x_l):
+        """Z of region l under ``inducing='greedy'``: the rows ``Inducing.greedy_rows`` picks among its inputs ``x_l`` under
+        the kernel the layer was CONSTRUCTED with (an ARD base: on x / l at l = 1, as :meth:`_block` runs), selected once
+        and kept on the device -- nothing is read back, the rows feed ``index_select``.  Trial and learned hyper-parameters
+        leave them where they are (``self.kernel`` changes, ``self._greedy_kernel`` does not): the objective stays a smooth
+        function of the hyper-parameters."""
+        key = (x_l.data_ptr(), tuple(x_l.shape), x_l.dtype)
+        if l not in self._greedy or self._greedy[l][0] != key:
+            from .Inducing import greedy_rows
+            if int(x_l.shape[0]) != self.n_rows[l]:
+                raise ValueError('region %d of layer %d has %d rows, not %d' % (l, self.layer, x_l.shape[0], self.n_rows[l]))
+            rows = greedy_rows(x_l.double(), self.kernel.num_inducing, self._greedy_kernel).rows
+            self._greedy[l] = (key, rows, x_l.index_select(0, rows).contiguous())
+        return self._greedy[l][2]
 
     def _inducing_inputs(self, l, x_l):
         """Z of region l: the rows :meth:`inducing_rows` of its inputs ``x_l``, gathered once and kept (the inputs of a
         model do not change; the learned hyper-parameters leave Z where it is)."""
+        if self.kernel.inducing == 'greedy':
+            return self._greedy_inputs(l, x_l)
         rows = self.inducing_rows(l)
         key = (x_l.data_ptr(), tuple(x_l.shape), x_l.dtype, rows.tobytes())
         if l not in self._z or self._z[l][0] != key:

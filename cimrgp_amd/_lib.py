@@ -208,6 +208,14 @@ PSI_ROWS_SIGNATURES = {
                                      _sz, _vp, _vp]),
 }
 
+# include/cimrgp_inducing.h: greedy inducing-point selection (the matrix-free pivoted Cholesky factorisation)
+PIVCHOL_ROWS = 64
+INDUCING_SIGNATURES = {
+    "cimrgp_pivoted_cholesky_scratch_bytes": (_sz, [_i64, _i64]),
+    "cimrgp_pivoted_cholesky": (_i32, [_i32, _i32, _vp, _i64, _i32, _dbl, _dbl, _vp, _i64, _dbl, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz,
+                                       _vp]),
+}
+
 #: header -> its table, in the include order of include/cimrgp.h
 HEADERS = {
     "cimrgp.h": SIGNATURES,
@@ -225,6 +233,7 @@ HEADERS = {
     "cimrgp_psi.h": PSI_SIGNATURES,
     "cimrgp_psi_grad.h": PSI_GRAD_SIGNATURES,
     "cimrgp_psi_rows.h": PSI_ROWS_SIGNATURES,
+    "cimrgp_inducing.h": INDUCING_SIGNATURES,
     "cimrgp_svgp.h": SVGP_SIGNATURES,
 }
 

@@ -6,7 +6,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
 OBJS=()
 pids=()
-for f in api block gemm_nt potrf gram solve misc reduced layer comm joint grad loo svgp psi psi_grad psi_rows sparse sparse_post sparse_grad; do
+for f in api block gemm_nt potrf gram solve misc reduced layer comm joint grad loo svgp psi psi_grad psi_rows inducing sparse sparse_post sparse_grad; do
     stale=0
     if [ ! -f "$f.o" ] || [ "$f.hip" -nt "$f.o" ]; then stale=1; fi
     for h in *.hpp ../../include/*.h; do

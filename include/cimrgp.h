@@ -518,6 +518,10 @@ int cimrgp_profile_collect_bytes(double* total_ms, double* total_flops, double* 
  * include/cimrgp_psi_rows.h. */
 #include "cimrgp_psi_rows.h"
 
+/* Greedy inducing-point selection: the matrix-free pivoted Cholesky factorisation of K(X, X), stopped after m columns:
+ * include/cimrgp_inducing.h. */
+#include "cimrgp_inducing.h"
+
 /* The variational sparse GP with a non-conjugate likelihood (Gaussian or Student-t): the Gauss-Hermite row pass over A
  * and W: include/cimrgp_svgp.h. */
 #include "cimrgp_svgp.h"
